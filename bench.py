@@ -9,6 +9,12 @@ gridpoints) per GPU, SSPRK33 stage sequence, synthetic structured mesh, data res
    torch.distributed(gloo) only carries the 128-byte RCCL id, the barriers and the max-reduction)
 
 Prints ONE JSON line on rank 0. `value` = k * N_q(all ranks) * K / t_max-over-ranks / 1e6.
+
+A plain run does what `value` and `ms_per_step` need and nothing else: mesh, developed state, W warm-up updates, ONE
+timed pass of exactly K updates, the line. `--full` adds the other measurements and checks: the median of --reps
+passes, the per-sweep breakdown and rooflines (a second, instrumented pass), the committed PMC traffic, the limiter
+and layout statistics, the RCCL counts, the host-mirrored binding and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed update computed (see dump_outputs()).
 """
 from __future__ import annotations
 
@@ -250,6 +256,38 @@ def self_launch_command(n_gpus: int, argv: list) -> list:
             "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), *argv]
 
 
+DUMP_MAX_ROWS = 1 << 20  # 1 Mi rows of U (k <= 5 doubles) and alpha: at most 48 MB
+
+
+def dump_outputs(directory: str, drv) -> None:
+    """What the last timed update computed, as its caller receives it (rank 0's owned rows): U.npy, the new state
+    vector [rows, k]; alpha.npy, the indicator of that update [rows]; tau.npy, the step size [1]. Meshes of more
+    than DUMP_MAX_ROWS owned rows are sampled: the same seeded rows in every run on the same mesh."""
+    import numpy as np
+    m = drv.m
+    # Ssprk33Stages: stage 1 and 2 updates write T[0] and T[1]; the update that completes an SSPRK33 step ends in U
+    new = {0: drv.U, 1: drv.T[0], 2: drv.T[1]}[drv.stage]
+    rows = np.arange(m.n_owned)
+    if m.n_owned > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(m.n_owned, size=DUMP_MAX_ROWS, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "U.npy"), new.download()[rows])
+    np.save(os.path.join(directory, "alpha.npy"), m.alpha()[rows])
+    np.save(os.path.join(directory, "tau.npy"), np.array([drv.tau], dtype=np.float64))
+
+
+def print_line(saved_stdout: int, out: dict) -> None:
+    """The ONE JSON line, on the stdout main() set aside (library banners went to fd 2)"""
+    import ctypes as C
+    sys.stdout.flush()
+    C.CDLL(None).fflush(None)  # C stdio of librccl (version banner) is block-buffered on a pipe: drain it to fd 2
+    os.dup2(saved_stdout, 1)
+    print(json.dumps(out), flush=True)
+    # anything a library prints at exit must not follow the JSON line on stdout
+    sys.stdout.flush()
+    os.dup2(2, 1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -292,9 +330,17 @@ def main():
     ap.add_argument("--probe-launch", action="store_true",
                     help="(test hook) initialise torch.distributed, print the rank layout as the JSON line and exit "
                          "before anything touches a GPU")
-    ap.add_argument("--reps", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the median of --reps timed passes, the per-sweep breakdown "
+                         "and rooflines, limiter / layout statistics, RCCL counts, the host-mirrored binding and the "
+                         "CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed update computed to DIR/<name>.npy "
+                         "(float64, at most 64 MB; rank 0's rows)")
+    ap.add_argument("--reps", type=int, default=None,
                     help="timed passes of exactly --steps steps each (barrier + synchronise on both sides of "
-                         "every pass); the JSON line reports the median pass and the min/max spread")
+                         "every pass); the JSON line reports the median pass and the min/max spread (default: 1, "
+                         "5 with --full)")
     ap.add_argument("--system-events", action="store_true",
                     help="create the events between the compute and the exchange stream with the system-scope "
                          "fence (ryujin_hip_params::system_scope_events)")
@@ -310,6 +356,10 @@ def main():
                     help="abort the process after this many seconds (a hung collective must not hang the box)")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
 
     # Library banners (gloo, RCCL) go to fd 1; keep stdout clean for the ONE JSON line.
     sys.stdout.flush()
@@ -477,7 +527,8 @@ def main():
         drv.t = t_p
         for _ in range(6):
             drv.update()
-    U_developed = drv.U.download() if (n_gpus == 1 and (not args.no_cpu_baseline or args.save_state)) else None
+    U_developed = (drv.U.download() if n_gpus == 1 and ((args.full and not args.no_cpu_baseline) or args.save_state)
+                   else None)
     if args.save_state and n_gpus == 1:
         while drv.stage != 0:
             drv.update()
@@ -562,6 +613,48 @@ def main():
     wall = walls[median_pass]
     ev_ms = C.c_double(evs[median_pass])
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, drv)
+
+    n_q_local = off.n_owned
+    if dist is not None:
+        import torch
+        nn = torch.tensor([n_q_local], dtype=torch.int64)
+        dist.all_reduce(nn, op=dist.ReduceOp.SUM)
+        n_q_total = int(nn[0])
+    else:
+        n_q_total = n_q_local
+
+    k = m.k
+    rs = off.row_starts
+    S = float(rs[off.n_owned]) / off.n_owned
+    headline = {
+        "metric": "MDoF-updates/s per Euler forward step; achieved HBM GB/s vs roofline",
+        "value": k * n_q_total * args.steps / wall / 1e6,
+        "unit": "MDoF-updates/s",
+        "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": wall / args.steps * 1e3,
+        "reps": len(walls), "ms_per_step_min": min(walls) / args.steps * 1e3,
+        "ms_per_step_max": max(walls) / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": workload_name,
+                   "gridpoints_per_gpu": n_q_local, "gridpoints_total": n_q_total,
+                   "dofs_total": k * n_q_total, "nnz_per_row": round(S, 3),
+                   "cells_per_unit": (args.cells_per_unit if args.workload.startswith("step2d") else n), "partition": f"x-slabs x{n_gpus}, equal gridpoint counts",
+                   "cfl": 0.9, "limiter_iterations": 2,
+                   # how the state the timed updates start from was made: run to develop_time on the coarse mesh,
+                   # interpolated, develop_updates updates on this mesh (develop_time 0: from the initial state)
+                   "develop_time": develop_time, "coarse_run": coarse, "develop_updates": n_develop,
+                   "simulated_time_at_start": t_at_start, "simulated_time_at_end": drv.t, "perturbation": args.perturbation,
+                   "perturbed_fraction": args.perturbed_fraction if args.perturbation != 0.0 else None},
+        "mq_per_s": n_q_total * args.steps / wall / 1e6,
+    }
+    if not args.full:
+        if rank == 0:
+            print_line(saved_stdout, dict(headline, n_warnings=m.n_warnings(), events=events))
+        return
+
     # ---- pass 2, the roofline breakdown: the same K steps again with hipEvent pairs around every sweep
     while drv.stage != 0:
         drv.update()
@@ -617,15 +710,6 @@ def main():
         for x in T3 + [sv]:
             x.free()
 
-    n_q_local = off.n_owned
-    if dist is not None:
-        import torch
-        nn = torch.tensor([n_q_local], dtype=torch.int64)
-        dist.all_reduce(nn, op=dist.ReduceOp.SUM)
-        n_q_total = int(nn[0])
-    else:
-        n_q_total = n_q_local
-
     # what RCCL and the library themselves report about the multi-rank run (rank 0's view + neighbour counts
     # of all ranks): "RCCL saw N ranks" can be read off the JSON line
     rccl = None
@@ -648,9 +732,6 @@ def main():
     if rank != 0:
         return
 
-    k = m.k
-    rs = off.row_starts
-    S = float(rs[off.n_owned]) / off.n_owned
     alg = algorithmic_bytes(off.dim, k, S, n_prec=m.n_prec, n_bounds=m.n_bounds)
     if equation == capi.EQ_SHALLOW_WATER:  # + bathymetry (8 B) and m_ij (8S) in step 4, SURVEY 8d
         alg["4 low_order"] += 8 + 8 * S
@@ -700,27 +781,9 @@ def main():
                        args.develop_time is None and args.develop is None and args.coarse_factor == 4)
     traffic, traffic_file, traffic_note = (pmc_traffic_bytes(dom, args.workload) if default_problem
                                            else (None, None, "not the default problem of the workload"))
+    headline["config"]["simulated_time_at_end"] = drv.t  # after the instrumented pass and the binding legs
     out = {
-        "metric": "MDoF-updates/s per Euler forward step; achieved HBM GB/s vs roofline",
-        "value": k * n_q_total * args.steps / wall / 1e6,
-        "unit": "MDoF-updates/s",
-        "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": wall / args.steps * 1e3,
-        "reps": len(walls), "ms_per_step_min": min(walls) / args.steps * 1e3,
-        "ms_per_step_max": max(walls) / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": workload_name,
-                   "gridpoints_per_gpu": n_q_local, "gridpoints_total": n_q_total,
-                   "dofs_total": k * n_q_total, "nnz_per_row": round(S, 3),
-                   "cells_per_unit": (args.cells_per_unit if args.workload.startswith("step2d") else n), "partition": f"x-slabs x{n_gpus}, equal gridpoint counts",
-                   "cfl": 0.9, "limiter_iterations": 2,
-                   # how the state the timed updates start from was made: run to develop_time on the coarse mesh,
-                   # interpolated, develop_updates updates on this mesh (develop_time 0: from the initial state)
-                   "develop_time": develop_time, "coarse_run": coarse, "develop_updates": n_develop,
-                   "simulated_time_at_start": t_at_start, "simulated_time_at_end": drv.t, "perturbation": args.perturbation,
-                   "perturbed_fraction": args.perturbed_fraction if args.perturbation != 0.0 else None},
-        "mq_per_s": n_q_total * args.steps / wall / 1e6,
+        **headline,
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": dom_gbs, "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": dom_gbs / HBM_PEAK_GBS,
                      "traffic": traffic,
@@ -762,13 +825,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline(spec, U_developed, dirichlet, args.cpu_budget, equation)
         except Exception as e:  # the baseline must never take the GPU number down with it
             out["cpu_baseline"] = {"value": None, "error": repr(e)}
-    sys.stdout.flush()
-    C.CDLL(None).fflush(None)  # C stdio of librccl (version banner) is block-buffered on a pipe: drain it to fd 2
-    os.dup2(saved_stdout, 1)
-    print(json.dumps(out), flush=True)
-    # anything a library prints at exit must not follow the JSON line on stdout
-    sys.stdout.flush()
-    os.dup2(2, 1)
+    print_line(saved_stdout, out)
 
 
 if __name__ == "__main__":

@@ -14,7 +14,7 @@ cd "$R"
 run() { # name, arguments
   local name=$1; shift
   if [ "$ONLY" != "  " ] && [[ "$ONLY" != *" $name "* ]]; then return; fi
-  timeout 600 python bench.py "$@" > "$OUT/${TAG}_bench_$name.json" 2> "$OUT/${TAG}_bench_$name.err"
+  timeout 600 python bench.py --full "$@" > "$OUT/${TAG}_bench_$name.json" 2> "$OUT/${TAG}_bench_$name.err"
   python - "$OUT/${TAG}_bench_$name.json" "$name" <<'PY'
 import json, sys
 try:

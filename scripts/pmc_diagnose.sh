@@ -9,7 +9,7 @@ TAG=$1; W=$2
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out; mkdir -p "$OUT"
 export TMPDIR=/tmp; cd /tmp
-BENCH="python $R/bench.py --workload $W"
+BENCH="python $R/bench.py --full --workload $W"
 STATE=/tmp/state_$W.npz
 [ -f $STATE ] || timeout 900 $BENCH --save-state $STATE --steps 3 --warmup 0 --reps 1 --no-cpu-baseline --binding device > /tmp/state.log 2>&1
 rm -rf /tmp/pmcd_*

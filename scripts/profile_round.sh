@@ -19,7 +19,7 @@ cd /tmp
 FP=$(cd $R && python -c "import bench; print(bench.source_fingerprint())")
 for W in $WORKLOADS; do
   SUF=""; [ "$W" != step2d ] && SUF="_$W"
-  BENCH="python $R/bench.py --workload $W"
+  BENCH="python $R/bench.py --full --workload $W"
   STATE=/tmp/state_$W.npz
   timeout 600 $BENCH --save-state $STATE --steps 3 --warmup 0 --reps 1 --no-cpu-baseline --binding device > /tmp/state_$W.log 2>&1
   PMCARGS="--steps 6 --warmup 3 --load-state $STATE --no-cpu-baseline --binding device"
@@ -40,6 +40,6 @@ for W in $WORKLOADS; do
 done
 cd $R
 case " $WORKLOADS " in *" step2d "*)
-  timeout 500 python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+  timeout 500 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
   tail -c 600 $OUT/${TAG}_bench.json;;
 esac

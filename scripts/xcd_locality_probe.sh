@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out; mkdir -p "$OUT"
 export TMPDIR=/tmp; cd /tmp
 SUF=""; [ -n "$TILE" ] && { export RYUJIN_SYNTH_TILE=$TILE; SUF="_tile$(echo $TILE | tr , x)"; }
-BENCH="python $R/bench.py --workload $W"
+BENCH="python $R/bench.py --full --workload $W"
 STATE=/tmp/state_${W}${SUF}.npz
 [ -f $STATE ] || timeout 900 $BENCH --save-state $STATE --steps 3 --warmup 0 --reps 1 --no-cpu-baseline --binding device > /tmp/state.log 2>&1
 MD=$OUT/${TAG}_xcd_probe_${W}${SUF}.md

@@ -1,6 +1,6 @@
 """bench.py's accounting, checked without a GPU: the algorithmic bytes per gridpoint-update are the ones
 SURVEY.md section 8d derives (3164 / 10020 / 2844 B), and the committed bench lines in profiles/ carry every
-field of the driver's contract."""
+field of the driver's contract. On the GPU: the plain line and its output dump."""
 import glob
 import json
 import os
@@ -163,3 +163,39 @@ def test_comments_do_not_change_the_fingerprint_of_the_kernel_sources(tmp_path, 
     assert bench.source_fingerprint() == one
     (csrc / "a.hpp").write_text("int f(int x) { return x + 2; }\n")
     assert bench.source_fingerprint() != one
+
+
+@pytest.mark.gpu
+def test_plain_line_times_exactly_the_steps_asked_for_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run (no --full): ONE timed pass of exactly --steps updates, the headline fields and nothing measured
+    beside them; --dump-outputs writes what the last timed update computed, identically in two runs of the same
+    command."""
+    import subprocess
+    import sys
+
+    import numpy as np
+    lines = []
+    for run in ("a", "b"):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7",
+                              "--warmup", "2", "--cells-per-unit", "200", "--develop-time", "0.3", "--develop", "30",
+                              "--watchdog", "500", "--dump-outputs", str(tmp_path / run)],
+                             capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-4000:]
+        out = [ln for ln in res.stdout.splitlines() if ln.strip()]
+        assert len(out) == 1, res.stdout
+        lines.append(json.loads(out[0]))
+    d = lines[0]
+    assert d["metric"] == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
+    assert d["unit"] == "MDoF-updates/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["reps"] == 1 and d["n_warnings"] == 0
+    assert abs(d["value"] - d["config"]["dofs_total"] / (d["ms_per_step"] * 1e-3) / 1e6) < 1e-6 * d["value"]
+    for key in ("roofline", "roofline_update", "sweep_ms", "limiter", "layout", "binding", "cpu_baseline", "rccl"):
+        assert key not in d, key
+    n = d["config"]["gridpoints_per_gpu"]
+    U, alpha, tau = (np.load(tmp_path / "a" / f"{name}.npy") for name in ("U", "alpha", "tau"))
+    assert U.shape == (n, 4) and alpha.shape == (n,) and tau.shape == (1,)
+    assert U.dtype == alpha.dtype == tau.dtype == np.float64
+    assert np.isfinite(U).all() and (U[:, 0] > 0).all() and tau[0] > 0
+    for name in ("U", "alpha", "tau"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")), name
+    assert lines[0]["config"]["simulated_time_at_end"] == lines[1]["config"]["simulated_time_at_end"]

@@ -34,6 +34,11 @@ def build_stub():
     return STUB
 
 
+def stub_preload():
+    """the stub in front of whatever the environment already preloads"""
+    return ":".join([STUB] + ([os.environ["LD_PRELOAD"]] if os.environ.get("LD_PRELOAD") else []))
+
+
 def launch(world, args, tmp_path, timeout=600):
     """`world` processes of rccl_worker.py on device 0, the stub in front of RCCL; kills the whole group on a hang"""
     import signal
@@ -42,7 +47,7 @@ def launch(world, args, tmp_path, timeout=600):
     os.makedirs(rendezvous, exist_ok=True)
     procs = []
     for rank in range(world):
-        env = dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), LD_PRELOAD=STUB, RYUJIN_RCCL_STUB_DIR=rendezvous,
+        env = dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), LD_PRELOAD=stub_preload(), RYUJIN_RCCL_STUB_DIR=rendezvous,
                    OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "rccl_worker.py"), *args], env=env,
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
@@ -118,7 +123,7 @@ def _bench(args, preload=True, timeout=900):
     build_stub()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     if preload:
-        env["LD_PRELOAD"] = STUB
+        env["LD_PRELOAD"] = stub_preload()
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), *args]
     proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                             start_new_session=True)
@@ -143,7 +148,7 @@ def test_bench_scaling_run_dress_rehearsal_on_one_gpu(n, extra):
     by the library, the watchdog, ONE JSON line from rank 0 -- with all ranks on device 0 over the RCCL test double.
     Asserts what tests/test_multigpu_rccl.py::test_bench_self_launches_its_ranks asserts on a multi-GPU box."""
     d = _bench(["--gpus", str(n), "--steps", "6", "--warmup", "3", "--develop-time", "0.3", "--develop", "30",
-                "--reps", "2", "--watchdog", "800", *extra])
+                "--reps", "2", "--watchdog", "800", "--full", *extra])
     assert d["n_gpus"] == n and d["scaling"] == "weak" and d["value"] > 0 and d["n_warnings"] == 0
     assert d["rccl"]["ranks"] == n and len(d["rccl"]["n_neighbours_per_rank"]) == n
     # x-slabs: the two end ranks have one neighbour, the others two
@@ -161,7 +166,7 @@ def test_bench_line_under_the_launcher_agrees_with_the_plain_line():
     """the N = 1 point of the scaling curve (torch.distributed + an RCCL communicator of one rank, --force-dist) must
     be the bench line: same mesh, same state, same kernels; ms_per_step within the spread of two runs on one box"""
     common = ["--steps", "30", "--warmup", "6", "--develop-time", "0.3", "--develop", "60", "--cells-per-unit", "400",
-              "--no-cpu-baseline", "--binding", "device"]
+              "--no-cpu-baseline", "--binding", "device", "--full"]
     plain = _bench(common, preload=False)
     dist = _bench(["--force-dist", *common], preload=False)  # real RCCL: one rank on one device is allowed
     assert dist["n_gpus"] == 1 and dist["rccl"]["ranks"] == 1 and "rccl" not in plain
