@@ -170,7 +170,6 @@ HIP_SYMBOLS = [
     "ryujin_hip_time_step_fn", "ryujin_hip_debug_addresses",
     "ryujin_hip_host_register", "ryujin_hip_host_unregister", "ryujin_hip_state_download_owned",
     "ryujin_hip_state_download_prepared", "ryujin_hip_layout_info", "ryujin_hip_chain_info", "ryujin_hip_tile_statistics",
-    "ryujin_hip_deferred_slices",
     "ryujin_hip_default_params", "ryujin_hip_create", "ryujin_hip_destroy",
     "ryujin_hip_state_alloc", "ryujin_hip_state_free", "ryujin_hip_state_upload",
     "ryujin_hip_state_download", "ryujin_hip_state_download_precomputed", "ryujin_hip_state_integrals",
@@ -251,7 +250,6 @@ def load_hip():
         lib.ryujin_hip_layout_info.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
         lib.ryujin_hip_chain_info.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
         lib.ryujin_hip_tile_statistics.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
-        lib.ryujin_hip_deferred_slices.argtypes = [vp, C.POINTER(C.c_uint)]
         lib.ryujin_hip_host_register.argtypes = [vp, C.c_void_p, C.c_size_t]
         lib.ryujin_hip_host_unregister.argtypes = [vp, C.c_void_p]
         lib.ryujin_hip_state_download_owned.argtypes = [vp, C.c_int, c_double_p]

@@ -101,9 +101,6 @@ namespace ryujin_hip
     unsigned int n_sampled_tiles, n_sampled_tiles_stored;
     /* ... those step 6 read, and those of them it had to form itself (step 5 had not stored them) */
     unsigned int n_sampled_tiles_needed, n_sampled_tiles_formed;
-    /* slices on the list of the launch behind step 6 (SliceFlags::deferred; [0] the export or only part of the sweep,
-     * [1] the interior part of a split sweep); reset by step_begin() */
-    unsigned int n_deferred[2];
   };
   constexpr int kStageCode = 100;
 
@@ -125,23 +122,17 @@ namespace ryujin_hip
     scalars->tau_in = M.begin.tau_in;
     scalars->use_device_tau = M.begin.use_device_tau;
     scalars->stage = M.begin.stage;
-    scalars->n_deferred[0] = scalars->n_deferred[1] = 0;
   }
 
 
   /* minimum waves per SIMD requested from the register allocator for the heavy sweeps (second
    * __launch_bounds__ argument): 512 registers / waves. Tuned on MI355X, see DESIGN.md. */
-#ifndef RYUJIN_PIN_WAITS
-#define RYUJIN_PIN_WAITS 1 /* arrived() in the column loops (0: A/B, the compiler's own placement of the waits) */
-#endif
 #ifndef RYUJIN_HO_CP_3D
-#define RYUJIN_HO_CP_3D 2 /* step 6 in 3-D: 0 = two-pass kernel, n = l_ij and the first n P_ij columns in registers (the others are read a second time, unless the whole tile is unlimited). Round 1, all at 2 waves/SIMD: 3.07 ms (0), 2.43 (8), 2.24 (14), 2.36 (18); round 2 see RYUJIN_OCC_HO_3D; round 4 (developed C4 state, all slices limited, limited update from V_i with tile-predicated P loads, 3 waves): whole update 8.30 ms (6), 8.06 (3), 8.02 (2), 8.13 (1) -- the second read of an unlimited tile is skipped anyway, fewer held columns leave the registers to the loads in flight */
+#define RYUJIN_HO_CP_3D 2 /* step 6 in 3-D: l_ij and the first n >= 1 P_ij columns in registers (the others are read a second time, unless the whole tile is unlimited). Round 1, all at 2 waves/SIMD: 3.07 ms (the two-pass kernel, retired), 2.43 (8), 2.24 (14), 2.36 (18); round 2 see RYUJIN_OCC_HO_3D; round 4 (developed C4 state, all slices limited, limited update from V_i with tile-predicated P loads, 3 waves): whole update 8.30 ms (6), 8.06 (3), 8.02 (2), 8.13 (1) -- the second read of an unlimited tile is skipped anyway, fewer held columns leave the registers to the loads in flight */
 #endif
+  static_assert(RYUJIN_HO_CP_3D >= 1, "step 6 in 3-D keeps at least one P_ij column in registers");
 #ifndef RYUJIN_OCC_DIJ_NODE_RECORD
 #define RYUJIN_OCC_DIJ_NODE_RECORD 3 /* step 2 on the combined node record (3-D Euler): 168 registers without scratch; C4 share 1.47 ms at 2 waves (184 registers), 1.35 at 3 */
-#endif
-#ifndef RYUJIN_DIJ_PREFETCH_RECORD
-#define RYUJIN_DIJ_PREFETCH_RECORD 1 /* step 2 on node records: the next neighbour's record is loaded one column ahead */
 #endif
 #ifndef RYUJIN_HO_CP_2D
 #define RYUJIN_HO_CP_2D 9 /* step 6 in 2-D: P_ij columns kept in registers between the update and the second limiter pass (9: all) */
@@ -161,9 +152,6 @@ namespace ryujin_hip
 #ifndef RYUJIN_OCC_DIJ
 #define RYUJIN_OCC_DIJ 2
 #endif
-#ifndef RYUJIN_LOW_PARK
-#define RYUJIN_LOW_PARK 1 /* step 4 (1-D, 2-D, no stage vectors): f(U_i) in LDS across the column loop */
-#endif
 #ifndef RYUJIN_OCC_LOW
 #define RYUJIN_OCC_LOW 3 /* C2, profiles/r05e_ab_low_order_2d.log: 0.2496 ms at 2 waves per SIMD, 0.2751 at 3 (36 B per lane of
                             scratch), 0.2408 at 3 with f(U_i) parked in LDS (two 8-byte spills per column left) */
@@ -171,32 +159,14 @@ namespace ryujin_hip
 #ifndef RYUJIN_OCC_LOW_AEOS
 #define RYUJIN_OCC_LOW_AEOS 2 /* k_low_order_aeos, kernels_euler_aeos.hpp */
 #endif
-#ifndef RYUJIN_OCC_LOW_SW
-#define RYUJIN_OCC_LOW_SW 2 /* k_low_order_sw, kernels_shallow_water.hpp */
-#endif
-#ifndef RYUJIN_OCC_LOW_3D_ALL
-#define RYUJIN_OCC_LOW_3D_ALL 0
-#endif
-#ifndef RYUJIN_OCC_LOW_3D_STAGES
-#define RYUJIN_OCC_LOW_3D_STAGES 1 /* 3-D multi-stage step 4: 1 wave/SIMD without spills instead of 2 with 212 B/lane of scratch */
-#endif
 #ifndef RYUJIN_OCC_PIJ
 #define RYUJIN_OCC_PIJ 2
 #endif
 #ifndef RYUJIN_OCC_HO
 #define RYUJIN_OCC_HO 2
 #endif
-#ifndef RYUJIN_STAGE0_PIJ
-#define RYUJIN_STAGE0_PIJ 1 /* Euler, stages == 0: P_ij formed once, in step 5 (kernels_limiter_stage0.hpp) */
-#endif
-#ifndef RYUJIN_PER_SLICE_PIJ
-#define RYUJIN_PER_SLICE_PIJ 1 /* stages == 0, two limiter passes: step 5 stores P_ij only in the slices steps 6/7 will read it in (kernels_limiter_stage0.hpp); 0: everywhere */
-#endif
 #ifndef RYUJIN_PER_SLICE_MAX_LIMITED
 #define RYUJIN_PER_SLICE_MAX_LIMITED 0.8 /* ... while at most this fraction of the slices held a limited pair in the latest measured update. Break-even on the developed Mach-3 step (profiles/r04f_ab_per_slice_vs_plain_real_flow_2d.log): per slice -1.9 % per update at 53 % limited slices, -0.5 % at 71 %, +1.2 % at 93 % */
-#endif
-#ifndef RYUJIN_FUSE_PRECOMPUTE
-#define RYUJIN_FUSE_PRECOMPUTE 1 /* device-resident RK driver: the last sweep of a stage leaves the precomputed values and Riemann records of the next one (FusedPrecompute) */
 #endif
 
   constexpr int kBlock = 256;
@@ -235,31 +205,20 @@ namespace ryujin_hip
     }
   }
 
-#ifndef RYUJIN_NT
-#define RYUJIN_NT 3 /* non-temporal hints on the single-use multi-component matrix streams (c_ij, P_ij):
-                       bit 0 loads, bit 1 stores. A/B on MI355X: -2..3 % per update (the streams no longer
-                       evict the gathered U_j / l_ji lines from L2) */
-#endif
+  /* non-temporal hints on the single-use multi-component matrix streams (c_ij, P_ij), loads and stores. A/B on
+   * MI355X: -2..3 % per update (the streams no longer evict the gathered U_j / l_ji lines from L2). The single-use
+   * scalar streams (column indices, m_ij, l'_ij) keep ordinary loads and stores; the other variants were retired. */
   typedef double v2d_t __attribute__((ext_vector_type(2)));
 
-  /* single-use scalar streams (column indices, m_ij, l'_ij): bits 2 (loads) and 3 (stores) */
   template <typename T>
   RYUJIN_DEV T ld_stream(const T *p)
   {
-#if RYUJIN_NT & 4
-    return __builtin_nontemporal_load(p);
-#else
     return *p;
-#endif
   }
   template <typename T, typename V>
   RYUJIN_DEV void st_stream(T *p, const V v)
   {
-#if RYUJIN_NT & 8
-    __builtin_nontemporal_store((T)v, p);
-#else
     *p = (T)v;
-#endif
   }
 
   /* entry of an NC-component matrix in the paired SELL layout; colbase = slice_off + col_idx */
@@ -270,11 +229,7 @@ namespace ryujin_hip
     const double *b = m + colbase * 64 * NC;
 #pragma unroll
     for (int g = 0; g < NC / 2; ++g) {
-#if RYUJIN_NT & 1
       const v2d_t t = __builtin_nontemporal_load(reinterpret_cast<const v2d_t *>(b + g * 128 + lane * 2));
-#else
-      const double2 t = *reinterpret_cast<const double2 *>(b + g * 128 + lane * 2);
-#endif
       v[2 * g] = t.x;
       v[2 * g + 1] = t.y;
     }
@@ -305,17 +260,10 @@ namespace ryujin_hip
     double *b = m + colbase * 64 * NC;
 #pragma unroll
     for (int g = 0; g < NC / 2; ++g) {
-#if RYUJIN_NT & 2
       v2d_t t;
       t.x = v[2 * g];
       t.y = v[2 * g + 1];
       __builtin_nontemporal_store(t, reinterpret_cast<v2d_t *>(b + g * 128 + lane * 2));
-#else
-      double2 t;
-      t.x = v[2 * g];
-      t.y = v[2 * g + 1];
-      *reinterpret_cast<double2 *>(b + g * 128 + lane * 2) = t;
-#endif
     }
     if (NC & 1)
       b[(NC / 2) * 128 + lane] = v[NC - 1];
@@ -366,26 +314,14 @@ namespace ryujin_hip
 
   /* A tile descriptor through the CONSTANT address space (the map is written at create() and by no kernel): with a
    * wave-uniform address that is a scalar load -- no vector-memory round trip in front of the gathers that need it,
-   * nothing in vmcnt -- whatever the kernel stores or pins around it. RYUJIN_TILE_DESC_SCALAR = 0: the global loads of
-   * rounds 5 - 6 (A/B). */
-#ifndef RYUJIN_DIAG_PINS
-#define RYUJIN_DIAG_PINS 1 /* step 3: 1 = the gathers of a row in flight together, 2 = its stores as well. Same process
-                             (profiles/r06ar_ab_step3_pins_c{2,5}.log): C2 0.0767 -> 0.0710 (1) / 0.0727 (2) / 0.0911 ms (3: a
-                             row's eight reads and four writes at once), C5 0.1024 -> 0.0951 / 0.0989 / 0.0960 */
-#endif
-#ifndef RYUJIN_TILE_DESC_SCALAR
-#define RYUJIN_TILE_DESC_SCALAR 1
-#endif
+   * nothing in vmcnt -- whatever the kernel stores or pins around it. (The global loads of rounds 5 - 6 were
+   * retired.) */
   RYUJIN_DEV int4 load_tile_desc(const TileDesc *t)
   {
-#if RYUJIN_TILE_DESC_SCALAR
     typedef int v4i __attribute__((ext_vector_type(4)));
     typedef const v4i __attribute__((address_space(4))) *const_ptr;
     const v4i v = *(const_ptr)(uintptr_t)t;
     return int4{v.x, v.y, v.z, v.w};
-#else
-    return *reinterpret_cast<const int4 *>(t);
-#endif
   }
 
   template <bool USE = true>
@@ -425,9 +361,6 @@ namespace ryujin_hip
    * neighbours i - 1 and i + 1 are the slice's own rows. The lanes for which that does not hold -- the end of the
    * wave, the end of a lattice row, boundary rows: the tile's mask -- fetch their node as ever. Same values, same
    * bits. ---- */
-#ifndef RYUJIN_CHAINED_GATHERS
-#define RYUJIN_CHAINED_GATHERS 1
-#endif
   struct TileChain {
     uint32_t kind;  /* kChainNone / kChainPrevColumn / kChainOwnPrev / kChainOwnNext, wave-uniform */
     uint64_t loads; /* the lanes that fetch their node from memory */
@@ -444,21 +377,19 @@ namespace ryujin_hip
   RYUJIN_DEV TileChain tile_chain(const DeviceMesh &M, const uint64_t colbase)
   {
     TileChain t{kChainNone, ~0ull};
-    if constexpr (RYUJIN_CHAINED_GATHERS != 0) {
-      if (M.tiles != nullptr) {
-        typedef const uint32_t __attribute__((address_space(4))) *const_ptr;
-        typedef const uint64_t __attribute__((address_space(4))) *const_ptr64;
-        const uint32_t code = __builtin_amdgcn_readfirstlane(*(const_ptr)(uintptr_t)&M.tiles[colbase].chain);
-        if constexpr (MASKS) {
-          t.kind = code & kChainKindMask;
-          if (t.kind != kChainNone) {
-            const uint64_t m = *(const_ptr64)(uintptr_t)(M.chain_loads + colbase);
-            t.loads = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(m >> 32)) << 32) |
-                      (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)m);
-          }
-        } else {
-          t.kind = (code & kChainEndLaneOnly) != 0u ? (code & kChainKindMask) : kChainNone;
+    if (M.tiles != nullptr) {
+      typedef const uint32_t __attribute__((address_space(4))) *const_ptr;
+      typedef const uint64_t __attribute__((address_space(4))) *const_ptr64;
+      const uint32_t code = __builtin_amdgcn_readfirstlane(*(const_ptr)(uintptr_t)&M.tiles[colbase].chain);
+      if constexpr (MASKS) {
+        t.kind = code & kChainKindMask;
+        if (t.kind != kChainNone) {
+          const uint64_t m = *(const_ptr64)(uintptr_t)(M.chain_loads + colbase);
+          t.loads = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(m >> 32)) << 32) |
+                    (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)m);
         }
+      } else {
+        t.kind = (code & kChainEndLaneOnly) != 0u ? (code & kChainKindMask) : kChainNone;
       }
     }
     return t;
@@ -496,9 +427,7 @@ namespace ryujin_hip
      * to where the two paths meet -- every tile's path -- and, behind a load the compiler cannot count, becomes
      * vmcnt(0): each column of step 3 then waited for the gather of the column before, scripts/isa_loop_waits.sh) */
     uint32_t pos = M.idx_t[colbase * 64 + lane];
-#if (RYUJIN_DIAG_PINS & 1)
     asm volatile("" : "+v"(pos));
-#endif
     return pos;
   }
 
@@ -1006,8 +935,7 @@ namespace ryujin_hip
       uint32_t j_nn = r.width > 1 ? ld_stream(cols + (((uint64_t)r.base + 1) * 64 + r.lane)) : i;
       double c_n[DIM], rec_n[RS];
       load_entry<DIM>(cij, r.base, r.lane, c_n);
-      if constexpr (RYUJIN_DIJ_PREFETCH_RECORD)
-        load_record<RS>(rec, j_n, rec_n);
+      load_record<RS>(rec, j_n, rec_n);
       double d_pending = 0.; /* the d_ij of the column before, stored behind this column's loads (see arrived()) */
       bool d_pending_on = false;
       for (uint32_t c = 0; c < r.width; ++c) {
@@ -1017,23 +945,16 @@ namespace ryujin_hip
 #pragma unroll
         for (int d = 0; d < DIM; ++d)
           c_ij[d] = c_n[d];
-        if constexpr (RYUJIN_DIJ_PREFETCH_RECORD) {
 #pragma unroll
-          for (int q = 0; q < RS; ++q)
-            rec_j[q] = rec_n[q];
-        } else {
-          load_record<RS>(rec, j, rec_j);
-        }
-        if constexpr (RYUJIN_PIN_WAITS) {
-          arrived(c_ij);
-          arrived(rec_j);
-          arrived(j_nn);
-        }
+        for (int q = 0; q < RS; ++q)
+          rec_j[q] = rec_n[q];
+        arrived(c_ij);
+        arrived(rec_j);
+        arrived(j_nn);
         if (c + 1 < r.width) {
           j_n = j_nn;
           load_entry<DIM>(cij, colbase + 1, r.lane, c_n);
-          if constexpr (RYUJIN_DIJ_PREFETCH_RECORD)
-            load_record<RS>(rec, j_n, rec_n);
+          load_record<RS>(rec, j_n, rec_n);
           j_nn = (c + 2 < r.width) ? ld_stream(cols + ((colbase + 2) * 64 + r.lane)) : i;
         }
         if (d_pending_on)
@@ -1180,9 +1101,10 @@ namespace ryujin_hip
       return;
     const bool row_active = r.len > 1;
     uint32_t mask = row_active ? lower_mask[r.row] : 0u;
-#if (RYUJIN_DIAG_PINS & 1)
     asm volatile("" : "+v"(mask)); /* (arrived: the per-column blocks below must not each wait for it, and with it for the gather of the column before) */
-#endif
+    /* the gathers of a row in flight together (the pins above and in tile_transposed). Same process
+     * (profiles/r06ar_ab_step3_pins_c{2,5}.log): C2 0.0767 -> 0.0710 ms, C5 0.1024 -> 0.0951. Pinning the row's stores
+     * as well was retired: C2 0.0727, C5 0.0989; a row's eight reads and four writes at once 0.0911 / 0.0960 */
     double d[MAXW];
 #pragma unroll
     for (int c = 1; c < MAXW; ++c) {
@@ -1194,13 +1116,6 @@ namespace ryujin_hip
         d[c] = dij[src];
       }
     }
-    /* ONE wait for the row's values: left to the compiler, every column of the loop below waits for the one it uses --
-     * behind conditional stores it cannot count, with vmcnt(0): for the store of the column before as well */
-#if (RYUJIN_DIAG_PINS & 2)
-#pragma unroll
-    for (int c = 1; c < MAXW; ++c)
-      asm volatile("" : "+v"(d[c]));
-#endif
     double d_sum = 0.;
 #pragma unroll
     for (int c = 1; c < MAXW; ++c) {
@@ -1263,9 +1178,10 @@ namespace ryujin_hip
 
   /* STORE_P = false: the first part of P_ij is not written here but recomputed -- with the identical
    * operation sequence, hence bit-identical -- by k_pij_lij_recompute (saves the 8kS B/row store of
-   * this sweep and the 8kS B/row load of step 5 for 8dS+8S B/row of c_ij, d_ij loads there). */
+   * this sweep and the 8kS B/row load of step 5 for 8dS+8S B/row of c_ij, d_ij loads there).
+   * 3-D with stage vectors runs at 1 wave/SIMD without spills instead of 2 with 212 B/lane of scratch. */
   template <int DIM, bool HAS_STAGES, bool STORE_P = true, bool DG = false>
-  __global__ void __launch_bounds__(kBlock, (DIM == 3 && (HAS_STAGES || RYUJIN_OCC_LOW_3D_ALL) && RYUJIN_OCC_LOW_3D_STAGES) ? 1 : ((DIM == 3 || HAS_STAGES || DG) ? 2 : RYUJIN_OCC_LOW))
+  __global__ void __launch_bounds__(kBlock, (DIM == 3 && HAS_STAGES) ? 1 : ((DIM == 3 || HAS_STAGES || DG) ? 2 : RYUJIN_OCC_LOW))
   k_low_order(const EulerParams P, const DeviceMesh M, DeviceScalars *scalars,
               const double weight, const StageArgs<DIM> S, const double *__restrict__ U,
               const double *__restrict__ prec, const double *__restrict__ alpha,
@@ -1293,10 +1209,10 @@ namespace ryujin_hip
     const double m_i_inv = M.mi_inv[i];
     double f_i[K][DIM];
     E::flux(P, U_i, f_i);
-    /* RYUJIN_LOW_PARK: the row's flux f(U_i) -- K x DIM doubles that are only read, once per column -- lives in LDS
+    /* the row's flux f(U_i) -- K x DIM doubles that are only read, once per column -- lives in LDS
      * across the column loop, [entry][lane] (conflict free): 16 registers (2-D) that separate the sweep from 3 waves
      * per SIMD. The same operands into the same operations: the same bits. */
-    constexpr bool kParkFlux = RYUJIN_LOW_PARK && !HAS_STAGES && !DG && DIM >= 2;
+    constexpr bool kParkFlux = !HAS_STAGES && !DG && DIM >= 2;
     __shared__ double parked_flux[kParkFlux ? kWavesPerBlock * K * DIM * 64 : 1];
     double *const parked = parked_flux + (kParkFlux ? (threadIdx.x >> 6) * K * DIM * 64 : 0);
     if constexpr (kParkFlux) {

@@ -219,7 +219,7 @@ namespace ryujin_hip
   /* STORE_P = false (stages == 0): P_ij is formed in step 5 (kernels_limiter_stage0.hpp), nothing is stored here */
   /* DG: discontinuous ansatz, the incidence matrix enters the high-order viscosity (hyperbolic_module.template.h:733-737) */
   template <int DIM, bool HAS_STAGES, bool STORE_P = true, bool DG = false>
-  __global__ void __launch_bounds__(kBlock, (DIM == 3 && RYUJIN_OCC_LOW_3D_STAGES) ? 1 : RYUJIN_OCC_LOW_AEOS)
+  __global__ void __launch_bounds__(kBlock, DIM == 3 ? 1 : RYUJIN_OCC_LOW_AEOS)
   k_low_order_aeos(const EulerAeosParams P, const DeviceMesh M, DeviceScalars *scalars,
                    const double weight, const StageArgs<DIM> S, const double *__restrict__ U,
                    const double *__restrict__ prec, const double *__restrict__ alpha,

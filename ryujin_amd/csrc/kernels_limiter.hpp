@@ -201,9 +201,6 @@ namespace ryujin_hip
   /* DG: full inverse of the (block-diagonal) consistent mass matrix instead of the Neumann series
    * (hyperbolic_module.template.h:976-986): b_ij = m_i (M^-1)_ij, b_ji = m_j (M^-1)_ij */
   /* WIDE: rows of more than 64 entries (cG Q2 / Q3, dG in 3-D), the columns in blocks of 63 */
-#ifndef RYUJIN_PIJ_LIJ_CHAINED
-#define RYUJIN_PIJ_LIJ_CHAINED 1 /* step 5 with a stored first part of P_ij (shallow water, stage vectors, scalar, dG): chained gathers */
-#endif
   template <typename E, bool DG = false, bool WIDE = false>
   __global__ void __launch_bounds__(kBlock, RYUJIN_OCC_PIJ)
   k_pij_lij(const typename E::Params P, const DeviceMesh M, DeviceScalars *__restrict__ scalars,
@@ -286,7 +283,7 @@ namespace ryujin_hip
         /* chained gathers (kernels_euler.hpp): r_j and the nodal mass of most columns are the previous column's, or
          * the slice's own rows', one lane over */
         constexpr bool kMasks = chain_masks_pay<E::DIMENSION>();
-        const TileChain chain = RYUJIN_PIJ_LIJ_CHAINED != 0 ? tile_chain<kMasks>(M, colbase + 1) : TileChain{kChainNone, ~0ull};
+        const TileChain chain = tile_chain<kMasks>(M, colbase + 1);
         if (chain.kind == kChainNone) {
           load_state<K>(r_in, j_n, F_n);
           mjinv_n = node_j[j_n];
@@ -550,10 +547,10 @@ namespace ryujin_hip
   }
 
   /* The node data of the pair for a CHAINED tile (kernels_euler.hpp, chained gathers): `p` still holds the previous
-   * column's (kChainPrevColumn), `row` the slice's own rows' -- or, where step 5 parks them there (PARK as
-   * pij_stage0_parked: 1 F_i, 2 and U_i, 3 and the scalars), the wave's rows in LDS, [component][lane], where the
+   * column's (kChainPrevColumn), `row` the slice's own rows' -- or, where step 5 parks them there (PARK, as
+   * pij_stage0_parked: F_i, U_i and the scalars), the wave's rows in LDS, [component][lane], where the
    * neighbouring row is the neighbouring word; d_ij and m_ij are the entry's own and stream as ever. */
-  template <int K, int PARK = 0, bool MASKS = false>
+  template <int K, bool PARK = false, bool MASKS = false>
   RYUJIN_DEV void load_pair_chained(const DeviceMesh &M, const double *__restrict__ old_U,
                                     const double *__restrict__ r_in, const double *__restrict__ alpha,
                                     const double *__restrict__ dij, const uint64_t pos, const uint32_t j,
@@ -576,11 +573,11 @@ namespace ryujin_hip
       const double *src = parked + (next ? lane + 1u : (lane == 0u ? 0u : lane - 1u));
 #pragma unroll
       for (int q = 0; q < K; ++q) {
-        p.F_j[q] = PARK >= 1 ? src[q * 64] : (next ? lane_next(row.F_i[q]) : lane_prev(row.F_i[q]));
-        p.U_j[q] = PARK >= 2 ? src[(K + q) * 64] : (next ? lane_next(row.U_i[q]) : lane_prev(row.U_i[q]));
+        p.F_j[q] = PARK ? src[q * 64] : (next ? lane_next(row.F_i[q]) : lane_prev(row.F_i[q]));
+        p.U_j[q] = PARK ? src[(K + q) * 64] : (next ? lane_next(row.U_i[q]) : lane_prev(row.U_i[q]));
       }
-      p.alpha_j = PARK == 3 ? src[(2 * K + 0) * 64] : (next ? lane_next(row.alpha_i) : lane_prev(row.alpha_i));
-      p.m_j_inv = PARK == 3 ? src[(2 * K + 1) * 64] : (next ? lane_next(row.m_i_inv) : lane_prev(row.m_i_inv));
+      p.alpha_j = PARK ? src[(2 * K + 0) * 64] : (next ? lane_next(row.alpha_i) : lane_prev(row.alpha_i));
+      p.m_j_inv = PARK ? src[(2 * K + 1) * 64] : (next ? lane_next(row.m_i_inv) : lane_prev(row.m_i_inv));
     }
     if (chain_lane_loads<MASKS>(chain, lane)) {
       load_state<K>(old_U, j, p.U_j);
@@ -607,10 +604,10 @@ namespace ryujin_hip
     }
   }
 
-  /* The same with the row's F_i (and, PARK_U, U_i) parked in LDS, [component][lane] (conflict free): the same
-   * operations on the same operands in the same order -- bit for bit pij_stage0() -- with 2 K (4 K) registers fewer
+  /* The same with the row's F_i, U_i, alpha_i, 1/m_i and factor parked in LDS, [component][lane] (conflict free): the
+   * same operations on the same operands in the same order -- bit for bit pij_stage0() -- with 4 K + 6 registers fewer
    * held across the column loop. Step 5 in 3-D: what separates the sweep from 3 waves per SIMD. */
-  template <int K, bool PARK_U, bool PARK_SCALARS = false>
+  template <int K>
   RYUJIN_DEV void pij_stage0_parked(const RowData<K> &row, const double *parked_, const uint32_t lane,
                                     const PairData<K> &p, double (&P_ij)[K])
   {
@@ -619,17 +616,17 @@ namespace ryujin_hip
     uint32_t off = lane;
     asm volatile("" : "+v"(off));
     const double *parked = parked_ + off;
-    /* PARK_SCALARS: the row's alpha_i, 1/m_i and factor wait in LDS as well (rows 2 K, 2 K + 1, 2 K + 2) */
-    const double alpha_i = PARK_SCALARS ? parked[(2 * K + 0) * 64] : row.alpha_i;
-    const double m_i_inv = PARK_SCALARS ? parked[(2 * K + 1) * 64] : row.m_i_inv;
-    const double factor = PARK_SCALARS ? parked[(2 * K + 2) * 64] : row.factor;
+    /* rows 0 .. K - 1 F_i, K .. 2 K - 1 U_i, then alpha_i, 1/m_i and factor */
+    const double alpha_i = parked[(2 * K + 0) * 64];
+    const double m_i_inv = parked[(2 * K + 1) * 64];
+    const double factor = parked[(2 * K + 2) * 64];
     const double d_ijH = p.d_ij * ((alpha_i + p.alpha_j) * .5);
     const double dd = d_ijH - p.d_ij;
     const double b_ij = 0. - p.m_ij * p.m_j_inv;
     const double b_ji = 0. - p.m_ij * m_i_inv;
 #pragma unroll
     for (int q = 0; q < K; ++q) {
-      const double U_iq = PARK_U ? parked[(K + q) * 64] : row.U_i[q];
+      const double U_iq = parked[(K + q) * 64];
       double v = dd * (p.U_j[q] - U_iq);
       v += b_ij * p.F_j[q] - b_ji * parked[q * 64];
       P_ij[q] = v * factor;
@@ -638,26 +635,6 @@ namespace ryujin_hip
 
   /* where the repair launch of step 6 (k_pij_repair) and the debug fetch take P_ij from for the columns step 5 did
    * not store: the operands of pij_stage0 */
-#ifndef RYUJIN_TILE_PIJ_MAXDIM
-#define RYUJIN_TILE_PIJ_MAXDIM 3 /* per-tile P_ij is BUILT up to this dimension; the host selects it by default up to RYUJIN_TILE_PIJ_DEFAULT_MAXDIM */
-#endif
-#ifndef RYUJIN_TILE_PIJ_DEFAULT_MAXDIM
-#define RYUJIN_TILE_PIJ_DEFAULT_MAXDIM 2 /* 3-D: built, measured and NOT the default (debug_pij_storage = 3 selects it). C4 share, every slice limited,
-                                            56 % of the tiles stored: step 5 2.18 against 2.23 - 2.32 ms (its L2-miss traffic falls by 4.5 %, not by
-                                            the 24 % of its own bytes the tiles are: profiles/r06f_pmc_c4_*.md), step 6 1.68 against 1.45 ms
-                                            -- 7.74 against 7.60 ms per update; C3, 38 % of the slices limited, 22 % of the tiles stored: 12.4 - 12.5
-                                            against 12.2 ms per slice (profiles/r06b/d/e_ab_*) */
-#endif
-#ifndef RYUJIN_TILE_DEFER_MINDIM
-#define RYUJIN_TILE_DEFER_MINDIM 3 /* from this dimension on the tiles step 5 did not store are formed OUTSIDE the sweep of step 6: the wave
-                                      of a slice that misses a tile puts the slice on a list and retires, a small launch behind the sweep
-                                      runs the listed slices with the repair (k_high_order_next_deferred). In 3-D the repair inside the
-                                      kernel costs EVERY wave of the sweep: 124 -> 163 registers inlined (the fourth wave per SIMD gone), as
-                                      a function call spills in the common path -- step 6 on the C4 share 1.74 - 1.76 ms either way against
-                                      1.45 without the repair code (profiles/r06e_ab_repair_variants_c4.log). The launch behind the sweep
-                                      takes 156 us for 85 slices (C4) and 316 us for 140 (C3) whether a slice gets a wave or a block of its
-                                      own (profiles/r06c/r06d_kernel_trace_*.md): 1.68 ms in all -- the cheapest of the three, still a loss */
-#endif
   struct Stage0Src {
     DeviceScalars *scalars; /* tau; and the limited-slice counters of step 6 */
     const double *old_U, *alpha, *dij, *r_in;
@@ -879,20 +856,6 @@ namespace ryujin_hip
         store_entry<K>(pij, (uint64_t)base + c, lane, P_t);
     }
   }
-  /* ... as a FUNCTION CALL (3-D): the registers of the repair are the callee's, saved and restored around the rare
-   * call, instead of being added to what every wave of the sweep holds (inlined: 124 -> 163 registers, the fourth wave
-   * per SIMD gone). Plain pointer arguments: a reference to the kernel's DeviceMesh would make every wave write a copy
-   * of it to its stack at the top of the kernel. */
-  template <int K>
-  __device__ __attribute__((noinline)) void
-  repair_missing_tiles_out_of_line(const uint32_t *cols, const double *mij, const double *mi_inv, const double *old_U,
-                                   const double *r_in, const double *alpha, const double *dij, const double tau,
-                                   const uint32_t i, const uint32_t len, const uint32_t base, const uint32_t width,
-                                   const uint32_t lane, const bool row_active, const uint32_t missing, double *pij)
-  {
-    repair_missing_tiles<K>(cols, mij, mi_inv, old_U, r_in, alpha, dij, tau, i, len, base, width, lane, row_active,
-                            missing, pij);
-  }
 
   /* Per-slice bookkeeping of the limiter sweeps of an update without stage vectors (kernels_limiter_stage0.hpp):
    * one byte per 64-row slice each, written by exactly one wave per launch.
@@ -911,63 +874,33 @@ namespace ryujin_hip
     uint8_t *unlimited, *first_stored, *todo;
     /* the tiles step 6 read P_ij of in the last updates (an SSPRK33 step is three updates, and what its stages limit
      * differs). Stencils of up to 10 columns (1-D, 2-D Q1): [n_slices] words, bit c: the (slice, column c) tile in the
-     * last update; bits 10 + c, 20 + c: in the update before, and the one before that. Wider stencils (3-D Q1: 27
-     * columns): one word per generation, [generation][hist_stride] (tiles_predicted / tiles_remember below). */
+     * last update; bits 10 + c, 20 + c: in the update before, and the one before that (tiles_predicted /
+     * tiles_remember below). */
     uint32_t *needed_tiles;
-    uint32_t hist_stride; /* >= n_slices */
-    /* where the missing tiles are formed outside the sweep of step 6 (RYUJIN_TILE_DEFER_MINDIM): the slices whose wave
-     * retired, [n_slices]; the launch over the slices [slice_begin, slice_end) appends from entry slice_begin on,
-     * counted in DeviceScalars::n_deferred[slice_begin != 0] (the export and the interior part of a split sweep) */
-    uint32_t *deferred;
   };
 
 #ifndef RYUJIN_GATHER_GROUP_3D
 #define RYUJIN_GATHER_GROUP_3D 6 /* columns whose l_ij / l_ji are fetched in one batch where the row has more than 9 (steps 6, 7 in 3-D). C4 share, same process (profiles/r06v_ab_batched_gathers_c4.log): step 6 1.497 -> 1.379 (9) / 1.327 (6) / 1.413 (13) ms, step 7 0.857 -> 0.789 / 0.761 / 0.801 */
 #endif
-#ifndef RYUJIN_TILE_PIJ_GENERATIONS
-#define RYUJIN_TILE_PIJ_GENERATIONS 3
-#endif
-#ifndef RYUJIN_TILE_REPAIR_CALL
-#define RYUJIN_TILE_REPAIR_CALL 1 /* 3-D: the repair of step 6 as a function call (repair_missing_tiles_out_of_line) */
-#endif
-  /* the tiles step 5 stores on the strength of the last updates; MAXW: the widest row of the stencil family */
+  /* the tiles step 5 stores on the strength of the last updates; MAXW: the widest row of the stencil family. One word
+   * per slice, which the host allocates and sets to all ones: the first update stores every tile */
   template <int MAXW>
   RYUJIN_DEV uint32_t tiles_predicted(const SliceFlags &W, const uint32_t slice)
   {
-    if constexpr (MAXW <= 10) {
-      const uint32_t word = W.needed_tiles[slice];
-      uint32_t m = word & 0x3ffu;
-      if (RYUJIN_TILE_PIJ_GENERATIONS >= 2)
-        m |= (word >> 10) & 0x3ffu;
-      if (RYUJIN_TILE_PIJ_GENERATIONS >= 3)
-        m |= (word >> 20) & 0x3ffu;
-      return m;
-    } else {
-      static_assert(MAXW <= 32, "one bit per column");
-      uint32_t m = W.needed_tiles[slice];
-      if (RYUJIN_TILE_PIJ_GENERATIONS >= 2)
-        m |= W.needed_tiles[(size_t)W.hist_stride + slice];
-      if (RYUJIN_TILE_PIJ_GENERATIONS >= 3)
-        m |= W.needed_tiles[2 * (size_t)W.hist_stride + slice];
-      return m;
-    }
+    static_assert(MAXW <= 10, "P_ij per tile up to two dimensions");
+    const uint32_t word = W.needed_tiles[slice];
+    uint32_t m = word & 0x3ffu;
+    m |= (word >> 10) & 0x3ffu;
+    m |= (word >> 20) & 0x3ffu;
+    return m;
   }
   /* step 6 (one lane): `needed` becomes the newest generation, the oldest is forgotten */
   template <int MAXW>
   RYUJIN_DEV void tiles_remember(const SliceFlags &W, const uint32_t slice, const uint32_t needed)
   {
-    if constexpr (MAXW <= 10) {
-      W.needed_tiles[slice] = ((W.needed_tiles[slice] << 10) | (needed & 0x3ffu)) & 0x3fffffffu;
-    } else {
-      if (RYUJIN_TILE_PIJ_GENERATIONS >= 3)
-        W.needed_tiles[2 * (size_t)W.hist_stride + slice] = W.needed_tiles[(size_t)W.hist_stride + slice];
-      if (RYUJIN_TILE_PIJ_GENERATIONS >= 2)
-        W.needed_tiles[(size_t)W.hist_stride + slice] = W.needed_tiles[slice];
-      W.needed_tiles[slice] = needed;
-    }
+    static_assert(MAXW <= 10, "P_ij per tile up to two dimensions");
+    W.needed_tiles[slice] = ((W.needed_tiles[slice] << 10) | (needed & 0x3ffu)) & 0x3fffffffu;
   }
-  /* words of history per slice the host allocates (and sets to all ones: the first update stores every tile) */
-  constexpr int tile_history_words(const int maxw) { return maxw <= 10 ? 1 : 3; }
 
   /* form and store the P_ij of the columns [1, c_end) of the row (the repair launch of step 6,
    * ryujin_hip_debug_fetch): exactly the value step 5 formed (same function, same operands) */
@@ -1136,16 +1069,12 @@ namespace ryujin_hip
    * differences of a few ulp of lambda |P_ij|, orders inside the 1e-11 contract on the new state. Rows whose
    * columns are ALL in limited tiles (the strongly limited ones) take the reference's form in the reference's
    * order instead: see the branch below. */
-  /* P_ij stored per tile and the missing tiles formed outside the sweep (RYUJIN_TILE_DEFER_MINDIM):
-   *   kHoDefer   the whole sweep in one launch, but the wave of a slice that needs a tile step 5 did not store appends
-   *              the slice to SliceFlags::deferred and retires before it has written anything;
-   *   kHoRepair  the launch behind it (k_high_order_next_deferred): forms and stores the missing tiles of the listed
-   *              slices -- as kHoPlain does inside the sweep up to two dimensions -- and runs the sweep on them. */
-  constexpr int kHoPlain = 0, kHoLight = 1, kHoHeavy = 2, kHoDefer = 3, kHoRepair = 4;
+  /* P_ij stored per tile (up to two dimensions): kHoPlain forms the tiles step 5 did not store inside the sweep. */
+  constexpr int kHoPlain = 0, kHoLight = 1, kHoHeavy = 2;
   template <int DIM, int MODE>
   constexpr bool forms_missing_tiles()
   {
-    return DIM <= RYUJIN_TILE_PIJ_MAXDIM && ((MODE == kHoPlain && DIM < RYUJIN_TILE_DEFER_MINDIM) || MODE == kHoRepair);
+    return DIM <= 2 && MODE == kHoPlain;
   }
 
   template <typename E, int MAXW, int CP, bool SPLIT, int MODE>
@@ -1159,7 +1088,7 @@ namespace ryujin_hip
     constexpr int K = E::K;
     constexpr int NB = E::NB;
     static_assert(!SPLIT || CP == MAXW, "the split variant caches the whole row");
-    static_assert(!SPLIT || MODE == kHoPlain || MODE == kHoRepair, "small meshes keep the stored P_ij");
+    static_assert(!SPLIT || MODE == kHoPlain, "small meshes keep the stored P_ij");
     const bool row_active = r.len > 1;
     const uint32_t i = row_active ? r.row : (r.row < M.n_owned ? r.row : M.n_owned - 1);
     const uint32_t *__restrict__ idx_t = M.idx_t;
@@ -1233,11 +1162,13 @@ namespace ryujin_hip
     uint32_t own_limited = 0; /* ... <=> one of the tile's OWN l_ij is (the tiles step 5 stored with Stage0Src::tile_store) */
     if (V_unlimited != nullptr) {
       /* what step 5 stored besides: the tiles this sweep needed in the previous updates (read before it is replaced) */
-      constexpr bool kTileMode = ((MODE == kHoPlain || MODE == kHoDefer) && !SPLIT) || MODE == kHoRepair;
+      constexpr bool kTileMode = forms_missing_tiles<E::DIMENSION, MODE>() && !SPLIT;
       const bool tiles = kTileMode && S0.tile_store != 0 && W.needed_tiles != nullptr;
-      const uint32_t predicted = tiles ? tiles_predicted<MAXW>(W, r.slice) : 0u;
+      uint32_t predicted = 0u;
+      if constexpr (kTileMode)
+        predicted = tiles ? tiles_predicted<MAXW>(W, r.slice) : 0u;
       bool limited = false;
-      /* the row's l = min(l_ij, l_ji) and the tile masks (`lane`: see the second call below) */
+      /* the row's l = min(l_ij, l_ji) and the tile masks */
       auto fetch_l = [&](const uint32_t lane) {
         needed = own_limited = 0u;
         /* in groups of up to 9 columns: all transposed positions, all l_ij and l_ji, then the masks
@@ -1292,14 +1223,6 @@ namespace ryujin_hip
        * the symmetrisation -- that step 5 did not store -- none of its OWN l_ij limited and not read in the last
        * updates: the limit came from the neighbour's l_ji, which step 5 cannot see. Wave-uniform. */
       const uint32_t missing = (kTileMode && S0.tile_store != 0) ? (needed & ~(own_limited | predicted)) : 0u;
-      if constexpr (MODE == kHoDefer) {
-        /* formed outside this sweep: the slice goes on the list before anything of it is written */
-        if (missing != 0u) {
-          if (r.lane == 0)
-            W.deferred[M.slice_begin + atomicAdd(&S0.scalars->n_deferred[M.slice_begin != 0u ? 1 : 0], 1u)] = r.slice;
-          return;
-        }
-      }
       /* (slices the light launch found limited, todo = 3, were counted there) */
       if (S0.scalars != nullptr && (r.slice & 15u) == 0 && r.lane == 0 && (!SPLIT || group == 0) &&
           !(MODE == kHoHeavy && todo == 3)) {
@@ -1309,10 +1232,9 @@ namespace ryujin_hip
       }
       if (W.unlimited != nullptr && r.lane == 0 && (!SPLIT || group == 0))
         W.unlimited[r.slice] = slice_limited ? 0 : 1;
-      if constexpr (SPLIT && MODE == kHoRepair)
-        __syncthreads(); /* every wave of the block has read the history */
-      if (tiles && r.lane == 0 && (!SPLIT || group == 0))
-        tiles_remember<MAXW>(W, r.slice, needed);
+      if constexpr (kTileMode)
+        if (tiles && r.lane == 0 && (!SPLIT || group == 0))
+          tiles_remember<MAXW>(W, r.slice, needed);
       load_state<K>(V_unlimited, i, U_i_new);
       if (!slice_limited) {
         if (row_active) {
@@ -1329,30 +1251,14 @@ namespace ryujin_hip
         atomicAdd(&S0.scalars->n_sampled_tiles_needed, (unsigned int)__popc(needed));
         atomicAdd(&S0.scalars->n_sampled_tiles_formed, (unsigned int)__popc(missing));
       }
-      if constexpr (kTileMode && forms_missing_tiles<E::DIMENSION, MODE>()) {
+      if constexpr (kTileMode) {
         /* the missing tiles are formed here, exactly as step 5 forms them (pij_stage0 on the same operands: the same
          * bits), and stored: the loads below, the second limiter pass, its Newton tail and step 7 then find them in
          * the matrix like every other tile. (A tile whose own pairs all went to the tail and came back with l = 1 is
-         * stored already and merely written again. SPLIT: each of the block's waves forms and stores them -- the same
-         * bits four times -- and reads back what it stored itself.)
-         * The rare wave that comes here FETCHES ITS l AGAIN afterwards (through a lane index the compiler cannot see
-         * through, or it would keep the first copy): the 2 (MAXW - 1) registers of l are then dead across the repair
-         * and serve it -- in 3-D the repair would otherwise raise the kernel from 124 to 156 registers and cost every
-         * wave of the sweep its fourth wave per SIMD (rounds 4 - 5 kept 3-D off per-tile storage for that reason). */
-        if (missing != 0u) {
-          if constexpr (MAXW > 9 && RYUJIN_TILE_REPAIR_CALL != 0)
-            repair_missing_tiles_out_of_line<K>(M.cols, M.mij, M.mi_inv, S0.old_U, S0.r_in, S0.alpha, S0.dij,
-                                                S0.scalars->tau, i, r.len, r.base, r.width, r.lane, row_active,
-                                                missing, pij);
-          else
-            repair_missing_tiles<K>(M.cols, M.mij, M.mi_inv, S0.old_U, S0.r_in, S0.alpha, S0.dij, S0.scalars->tau, i,
-                                    r.len, r.base, r.width, r.lane, row_active, missing, pij);
-          if constexpr (MAXW > 9) {
-            uint32_t lane_again = r.lane;
-            asm volatile("" : "+v"(lane_again));
-            fetch_l(lane_again);
-          }
-        }
+         * stored already and merely written again.) */
+        if (missing != 0u)
+          repair_missing_tiles<K>(M.cols, M.mij, M.mi_inv, S0.old_U, S0.r_in, S0.alpha, S0.dij, S0.scalars->tau, i,
+                                  r.len, r.base, r.width, r.lane, row_active, missing, pij);
       }
       if constexpr (E::kLimitedUpdateFromV) {
         /* U_i = V_i - sum over the limited tiles of (1 - l_ij) lambda P_ij: P_ij of those tiles only.
@@ -1591,28 +1497,5 @@ namespace ryujin_hip
     }
     next_cached_slice<E, MAXW, CP, SPLIT, MODE>(P, M, r, group, new_U, bounds, pij, lij, lij_next, V_unlimited, S0,
                                                 W, todo);
-  }
-
-  /* the launch behind the sweep of step 6 where the tiles step 5 did not store are formed outside it (kHoDefer): the
-   * listed slices, with the repair. A few dozen to a few hundred slices of a developed flow on an otherwise idle device:
-   * what counts is the length of one slice's chain of dependent loads, not throughput (one wave per slice through the
-   * kernel of the sweep: 157 us for 85 slices, profiles/r06c_kernel_trace_cylinder3d.md). Hence ONE BLOCK PER SLICE in
-   * the SPLIT form of the small meshes -- every wave forms the update, wave w runs the second limiter pass of every
-   * fourth column -- with ALL of the row's P_ij in registers (one wave per SIMD: the register file is the wave's) so
-   * that its loads are issued back to back. */
-  template <typename E, int MAXW>
-  __global__ void __launch_bounds__(kBlock, 1)
-  k_high_order_next_deferred(const typename E::Params P, const DeviceMesh M, double *__restrict__ new_U,
-                             const double *__restrict__ bounds, double *__restrict__ pij,
-                             const double *__restrict__ lij, double *__restrict__ lij_next,
-                             const double *__restrict__ V_unlimited, const Stage0Src S0, const SliceFlags W)
-  {
-    const uint32_t n = S0.scalars->n_deferred[M.slice_begin != 0u ? 1 : 0];
-    const uint32_t group = threadIdx.x >> 6;
-    for (uint32_t q = blockIdx.x; q < n; q += gridDim.x) { /* (uniform over the block: the barriers in the body are safe) */
-      const RowCtx r = row_context_of_slice(M, W.deferred[M.slice_begin + q]);
-      next_cached_slice<E, MAXW, MAXW, true, kHoRepair>(P, M, r, group, new_U, bounds, pij, lij, lij_next,
-                                                        V_unlimited, S0, W);
-    }
   }
 } // namespace ryujin_hip

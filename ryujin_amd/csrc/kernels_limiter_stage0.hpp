@@ -51,21 +51,6 @@ namespace ryujin_hip
 #ifndef RYUJIN_OCC_LIJ0
 #define RYUJIN_OCC_LIJ0 3 /* waves per SIMD asked of the register allocator */
 #endif
-#ifndef RYUJIN_LIJ0_UNCOND
-#define RYUJIN_LIJ0_UNCOND 1 /* step 5 where P_ij is stored everywhere: unconditional stores (see kUnconditionalStores) */
-#endif
-#ifndef RYUJIN_LIJ0_DELAY_L_MAXDIM
-#define RYUJIN_LIJ0_DELAY_L_MAXDIM 3 /* step 5: l_ij of column c stored in iteration c + 1 up to this dimension. 3-D: 2 until the chained
-                                         gathers took the scratch out of the kernel (the three registers came back as spill reloads inside
-                                         the loop); now C3's per-slice kernel 3.17 -> 2.88 ms, C4's (unconditional stores) unchanged
-                                         (profiles/r06aw_ab_delay_l_3d_c{3,4}.log) */
-#endif
-#ifndef RYUJIN_LIJ0_PARK_3D
-#define RYUJIN_LIJ0_PARK_3D 3 /* step 5 in 3-D: 1 = the row's F_i in LDS, 2 = F_i and U_i, 3 = and alpha_i, 1 / m_i, factor; 0 = all in registers */
-#endif
-#ifndef RYUJIN_LIJ0_CHAIN_3D
-#define RYUJIN_LIJ0_CHAIN_3D 3 /* step 5 in 3-D: chained gathers from 1 = the previous column, 2 = the slice's own rows (kernels_euler.hpp) */
-#endif
 #ifndef RYUJIN_OCC_LIJ0_3D
 #define RYUJIN_OCC_LIJ0_3D 3 /* rounds 1-4: 2 waves (at 3 the kernel spilled 28-56 B per lane and lost). Round 5: slice context in scalar
                                  registers + F_i / U_i parked in LDS leave 12 B per lane outside the column loop: 2.22 -> 1.97 ms on the
@@ -130,27 +115,25 @@ namespace ryujin_hip
      * (TailScratch: the two are never alive together), which is what makes room for the three scalars: without them
      * the kernel reloads a spilled register INSIDE the loop, and a scratch load counts in vmcnt like any other --
      * the compiler follows it with vmcnt(0), which drains the prefetch of the next column a third of the way
-     * into the iteration (scripts/isa_loop_waits.sh). */
-    constexpr int kPark = (E::DIMENSION == 3 && NY == 1) ? RYUJIN_LIJ0_PARK_3D : 0; /* 0 none, 1 F_i, 2 F_i and U_i, 3 and the scalars */
-    constexpr int kParkedDoubles = kPark == 0 ? 0 : (2 * K + (kPark == 3 ? 3 : 0)) * 64;
+     * into the iteration (scripts/isa_loop_waits.sh). Parking fewer of them (F_i alone, F_i and U_i) or none was
+     * retired. */
+    constexpr bool kPark = E::DIMENSION == 3 && NY == 1;
+    constexpr int kParkedDoubles = kPark ? (2 * K + 3) * 64 : 0;
     constexpr int kRowDoubles = kParkedDoubles > TailScratch<E>::kRowDoubles ? kParkedDoubles : TailScratch<E>::kRowDoubles;
     __shared__ double lds_rows[kWavesPerBlock * kRowDoubles];
     double *const parked = lds_rows + (threadIdx.x >> 6) * kRowDoubles;
     row.alpha_i = alpha[i];
     row.m_i_inv = M.mi_inv[i];
     row.factor = scalars->tau * row.m_i_inv * (double)(r.len - 1);
-    if constexpr (kPark != 0) {
+    if constexpr (kPark) {
 #pragma unroll
       for (int q = 0; q < K; ++q) {
         parked[q * 64 + r.lane] = row.F_i[q];
-        if (kPark >= 2)
-          parked[(K + q) * 64 + r.lane] = row.U_i[q];
+        parked[(K + q) * 64 + r.lane] = row.U_i[q];
       }
-      if (kPark == 3) {
-        parked[(2 * K + 0) * 64 + r.lane] = row.alpha_i;
-        parked[(2 * K + 1) * 64 + r.lane] = row.m_i_inv;
-        parked[(2 * K + 2) * 64 + r.lane] = row.factor;
-      }
+      parked[(2 * K + 0) * 64 + r.lane] = row.alpha_i;
+      parked[(2 * K + 1) * 64 + r.lane] = row.m_i_inv;
+      parked[(2 * K + 2) * 64 + r.lane] = row.factor;
     }
     const double lambda = 1. / (double)(r.len - 1);
     bool all_ok = true;
@@ -169,18 +152,20 @@ namespace ryujin_hip
      * slices but 43 % of the tiles hold a limited pair: most of the 8 k S bytes per row this sweep used to write were
      * never read. */
     constexpr bool tile_mode = TILE;
+    static_assert(!TILE || E::DIMENSION <= 2, "P_ij per tile up to two dimensions");
     /* gfx9 has ONE counter for vector loads and stores (vmcnt), decremented in issue order. A store the compiler sees
      * on some paths of the column loop only -- `if (active) store` -- makes it wait for vmcnt(0) before the first use of
      * the next column's operands: every column then pays the round trip of the stores of the column before
      * (profiles/r06i_*). Where everything is stored anyway, every lane stores, every column: the number of
      * stores behind the loads is the same on every path and the wait becomes vmcnt(n > 0). */
-    constexpr bool kUnconditionalStores = RYUJIN_LIJ0_UNCOND != 0 && !PER_SLICE && !TILE && NY == 1;
+    constexpr bool kUnconditionalStores = !PER_SLICE && !TILE && NY == 1;
     uint32_t tiles_stored = 0;
     /* ... or step 6 of the PREVIOUS update needed it (SliceFlags::needed_tiles, bit c of the slice's word): fronts
      * move a fraction of a cell per update, so this predicts nearly every tile that is limited through l_ji alone,
      * and step 6 forms what is left (a tile predicted in vain costs its store, as before). */
-    constexpr int kMaxWidth = E::DIMENSION == 1 ? 3 : (E::DIMENSION == 2 ? 9 : 27);
-    const uint32_t predicted = (tile_mode && W.needed_tiles != nullptr) ? tiles_predicted<kMaxWidth>(W, r.slice) : 0u;
+    uint32_t predicted = 0u;
+    if constexpr (tile_mode)
+      predicted = W.needed_tiles != nullptr ? tiles_predicted<E::DIMENSION == 1 ? 3 : 9>(W, r.slice) : 0u;
 
     /* SOFTWARE PIPELINE, arranged around gfx9's single in-order counter for vector loads and stores (vmcnt): whatever
      * the wave waits for, it waits for everything it issued before that as well, and where the compiler cannot count
@@ -203,8 +188,9 @@ namespace ryujin_hip
       load_pair<K>(M, old_U, r_in, alpha, dij, ((uint64_t)r.base + c0) * 64 + r.lane, j_n, next);
     /* the l_ij of the previous column, not stored yet (l_pending_on: there is one). (3-D: until the chained gathers
      * the kernel sat at the register limit of three waves per SIMD and the three registers this takes came back as
-     * spill reloads INSIDE the loop -- scratch loads count in vmcnt as well; RYUJIN_LIJ0_DELAY_L_MAXDIM) */
-    constexpr bool kDelayL = RYUJIN_LIJ0_DELAY_L_MAXDIM >= E::DIMENSION;
+     * spill reloads INSIDE the loop -- scratch loads count in vmcnt as well. Now C3's per-slice kernel 3.17 -> 2.88 ms,
+     * C4's (unconditional stores) unchanged, profiles/r06aw_ab_delay_l_3d_c{3,4}.log; storing it in its own iteration
+     * was retired) */
     double l_pending = 1.;
     bool l_pending_on = false;
 
@@ -213,8 +199,8 @@ namespace ryujin_hip
       const uint64_t pos = colbase * 64 + r.lane;
       const bool active = row_active && c < r.len;
       double P_ij[K];
-      if constexpr (kPark != 0)
-        pij_stage0_parked<K, kPark >= 2, kPark == 3>(row, parked, r.lane, next, P_ij);
+      if constexpr (kPark)
+        pij_stage0_parked<K>(row, parked, r.lane, next, P_ij);
       else
         pij_stage0<K>(row, next, P_ij);
       if (c + NY < r.width) {
@@ -223,17 +209,11 @@ namespace ryujin_hip
          * slice's own rows', moved by a lane) */
         constexpr bool kMasks = chain_masks_pay<E::DIMENSION>();
         TileChain chain = kChained ? tile_chain<kMasks>(M, colbase + NY) : TileChain{kChainNone, ~0ull};
-        if constexpr (E::DIMENSION == 3) {
-          if ((RYUJIN_LIJ0_CHAIN_3D & 1) == 0 && chain.kind == kChainPrevColumn)
-            chain.kind = kChainNone;
-          if ((RYUJIN_LIJ0_CHAIN_3D & 2) == 0 && chain.kind != kChainPrevColumn)
-            chain.kind = kChainNone;
-        }
         if (chain.kind == kChainNone)
           load_pair<K>(M, old_U, r_in, alpha, dij, (colbase + NY) * 64 + r.lane, j_n, next);
         else {
           uint32_t lane_c = r.lane;
-          if constexpr (kPark != 0) {
+          if constexpr (kPark) {
             /* (the parked rows are read once P_ij is complete and `next` is free: read earlier -- the scheduler would
              * -- the new operands need registers of their own next to the old ones, and the kernel has none) */
 #pragma unroll
@@ -247,13 +227,11 @@ namespace ryujin_hip
         j_nn = c + 2 * NY < r.width ? tile_column<kTileMap>(M, colbase + 2 * NY, i, r.lane) : i;
       }
       /* the l_ij of the column before */
-      if constexpr (kDelayL) {
-        if constexpr (kUnconditionalStores) {
-          if (c > c0)
-            lij[pos - NY * 64] = l_pending;
-        } else if (l_pending_on)
+      if constexpr (kUnconditionalStores) {
+        if (c > c0)
           lij[pos - NY * 64] = l_pending;
-      }
+      } else if (l_pending_on)
+        lij[pos - NY * 64] = l_pending;
       /* a slice that stores already: as soon as P_ij is formed (the store overlaps the limiter) */
       const bool stored_early = storing && (!tile_mode || ((predicted >> c) & 1u) != 0u);
       if (tile_mode && stored_early)
@@ -290,19 +268,14 @@ namespace ryujin_hip
       }
       /* (an undecided pair's entry: a placeholder in the unconditional form, which the Newton tail overwrites behind
        * its fence; nothing otherwise) */
-      if constexpr (kDelayL) {
-        l_pending = (active && !undecided) ? l_ij : 1.;
-        l_pending_on = active && !undecided;
-      } else if constexpr (kUnconditionalStores)
-        lij[pos] = (active && !undecided) ? l_ij : 1.;
-      else if (active && !undecided)
-        lij[pos] = l_ij;
+      l_pending = (active && !undecided) ? l_ij : 1.;
+      l_pending_on = active && !undecided;
       if (active && undecided)
         undecided_mask |= 1ull << c;
       all_ok = all_ok && (!active || undecided || success);
     }
     /* the l_ij of the last column */
-    if (kDelayL && r.width > c0) {
+    if (r.width > c0) {
       const uint32_t c_last = c0 + ((r.width - 1 - c0) / NY) * NY;
       if (kUnconditionalStores || l_pending_on)
         lij[((uint64_t)r.base + c_last) * 64 + r.lane] = l_pending;

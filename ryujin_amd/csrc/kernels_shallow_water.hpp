@@ -9,9 +9,6 @@
 #include "shallow_water_device.hpp"
 
 
-#ifndef RYUJIN_SW_SINGLE_WALK
-#define RYUJIN_SW_SINGLE_WALK 1 /* A/B on MI355X: see DESIGN.md section 3 */
-#endif
 #ifndef RYUJIN_OCC_LOW_SW
 #define RYUJIN_OCC_LOW_SW 2 /* waves per SIMD asked of the register allocator for the single-walk kernel */
 #endif
@@ -461,17 +458,15 @@ namespace ryujin_hip
       for (int q = 0; q < K; ++q)
         U_j[q] = U_n[q];
       double d_ij = d_n, m_ij = m_n, alpha_j = alpha_n, Z_j = Z_n, h_star_j = h_star_n;
-      if constexpr (RYUJIN_PIN_WAITS) {
-        arrived(c_ij);
-        arrived(U_j);
-        arrived(d_ij);
-        arrived(alpha_j);
-        arrived(Z_j);
-        arrived(j_nn);
-        if constexpr (FRICTION) {
-          arrived(m_ij);
-          arrived(h_star_j);
-        }
+      arrived(c_ij);
+      arrived(U_j);
+      arrived(d_ij);
+      arrived(alpha_j);
+      arrived(Z_j);
+      arrived(j_nn);
+      if constexpr (FRICTION) {
+        arrived(m_ij);
+        arrived(h_star_j);
       }
       if (c + 1 < r.width) {
         j_n = j_nn;

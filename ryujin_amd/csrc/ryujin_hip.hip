@@ -28,10 +28,6 @@
 
 #include "ryujin_hip.h"
 
-#ifndef RYUJIN_TILE_PIJ
-#define RYUJIN_TILE_PIJ 1 /* the plain kernels (most slices limited) store P_ij per (slice, column) tile */
-#endif
-#ifndef RYUJIN_BAND_DEFAULT
 #ifndef RYUJIN_XCD_CHUNK_3D
 #define RYUJIN_XCD_CHUNK_3D 8 /* XCD-local block ranges (ryujin_hip_params::debug_xcd_chunk == 0), blocks per XCD and chunk. Counted and timed
                                  (profiles/r06a_xcd_probe_sedov3d.md, r06g_xcd_probe_*.md): the L2-miss read traffic of the sweeps falls
@@ -40,12 +36,6 @@
                                  -2.1 %); C4 +-1 %, C2 and C5 +-0.2 %. The sweeps are not bound by the bytes their gathers re-fetch
                                  across XCDs (HBM itself delivers 5.8 - 6.7 TB/s for their read/write mixes,
                                  profiles/r06h_hbm_mix.md): on in 3-D, where it is a gain or a wash, off below */
-#endif
-#define RYUJIN_BAND_DEFAULT 1 /* stacked blocks chosen from the mesh when ryujin_hip_params::debug_band_stride == 0, in 2-D:
-                                 C2 (G = 47) -1.1 % per update, every sweep a little; in 3-D stacking lattice planes (G = 365
-                                 on the C4 share) LOSES 1.7 % and stacking lattice rows (G = 2) is noise -- the re-fetches of
-                                 neighbour data across XCDs that the counters show are not what limits the sweeps
-                                 (profiles/r05p_ab_band_2d.log, r05p_ab_band_3d.log) */
 #endif
 
 #include "host_layout.hpp"
@@ -245,6 +235,20 @@ namespace
   constexpr uint32_t kBcFoldMaxSlices = 4096;
 
   int grid_for(size_t n, int block = kBlock) { return (int)std::max<size_t>(1, (n + block - 1) / block); }
+
+  /* step 5 on small meshes: launch(std::integral_constant<int, NY>), NY = min(groups, 4) waves per slice, at least 1 */
+  template <typename F>
+  void with_groups(const uint32_t groups, F &&launch)
+  {
+    if (groups >= 4)
+      launch(std::integral_constant<int, 4>{});
+    else if (groups == 3)
+      launch(std::integral_constant<int, 3>{});
+    else if (groups == 2)
+      launch(std::integral_constant<int, 2>{});
+    else
+      launch(std::integral_constant<int, 1>{});
+  }
 } // namespace
 
 /* In-process transport (test facility): several contexts of ONE process, each driven by its own host
@@ -482,7 +486,6 @@ struct ryujin_hip_ctx {
    * context stores P_ij everywhere */
   DeviceBuffer<uint8_t> d_slice_unlimited, d_slice_first_stored, d_slice_todo;
   DeviceBuffer<uint32_t> d_slice_needed; /* SliceFlags::needed_tiles; starts as all ones: the first update stores every tile */
-  DeviceBuffer<uint32_t> d_slice_deferred; /* SliceFlags::deferred */
   /* fractions of the (sampled) slices in which the first high-order sweep found a limited pair / whose P_ij step 5
    * stored, from the device counters at the latest host synchronisation (DeviceScalars::n_sampled_*); 1 until the
    * first measurement. Diagnostics only: nothing is decided from them. */
@@ -657,6 +660,8 @@ void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params
     throw HipError(RYUJIN_ERR_ARG, "dim must be 1, 2 or 3");
   if (p.limiter_iterations < 0 || p.limiter_iterations > 2)
     throw HipError(RYUJIN_ERR_ARG, "The number of limiter iterations must be between [0,2]");
+  if (p.debug_pij_storage > 2)
+    throw HipError(RYUJIN_ERR_ARG, "debug_pij_storage must be < 0, 0, 1 or 2 (per-tile P_ij in 3-D was retired)");
   K = p.equation == RYUJIN_EQ_SHALLOW_WATER ? dim + 1 : dim + 2;
   NB = p.equation == RYUJIN_EQ_EULER ? 3 : (p.equation == RYUJIN_EQ_EULER_AEOS ? 4 : 5);
   NPREC = p.equation == RYUJIN_EQ_EULER_AEOS ? 4 : 2;
@@ -813,11 +818,14 @@ void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params
   mesh.tiles = d_tiles.n != 0 ? d_tiles.ptr : nullptr;
   mesh.chain_loads = d_chain_loads.n != 0 ? d_chain_loads.ptr : nullptr;
   mesh.tail_queue_columns = std::max<uint32_t>(1u, std::min<uint32_t>(63u, L.max_row_len - 1u));
-  /* stacked blocks (row_context(), kernels_euler.hpp): debug_band_stride < 0 off, > 0 that many slices, 0 from the mesh */
+  /* stacked blocks (row_context(), kernels_euler.hpp): debug_band_stride < 0 off, > 0 that many slices, 0 from the
+   * mesh, in 2-D: C2 (G = 47) -1.1 % per update, every sweep a little; in 3-D stacking lattice planes (G = 365 on the C4
+   * share) LOSES 1.7 % and stacking lattice rows (G = 2) is noise -- the re-fetches of neighbour data across XCDs that
+   * the counters show are not what limits the sweeps (profiles/r05p_ab_band_2d.log, r05p_ab_band_3d.log) */
   mesh.band_stride = 1;
   if (p.debug_band_stride > 0)
     mesh.band_stride = (uint32_t)p.debug_band_stride;
-  else if (p.debug_band_stride == 0 && RYUJIN_BAND_DEFAULT && dim == 2) {
+  else if (p.debug_band_stride == 0 && dim == 2) {
     const uint32_t stride = L.lattice_stride(dim);
     const uint32_t G = (stride + kWave / 2) / kWave;
     if (G >= 2 && (uint64_t)G * kWavesPerBlock * 4 <= L.n_slices)
@@ -1505,7 +1513,7 @@ int ryujin_hip_ctx::step(int h_old, int stages, const int *h_stage, const double
    * d_ij, m_ij and the per-node vectors, limits it and stores it for steps 6 and 7 (kernels_limiter_stage0.hpp)
    * -- any dimension */
   constexpr int kStage0Width = DIM == 1 ? 3 : (DIM == 2 ? 9 : 27);
-  const bool stage0_pij = RYUJIN_STAGE0_PIJ && (is_euler || is_aeos) && stages == 0 && params.limiter_iterations != 0 && !dg &&
+  const bool stage0_pij = (is_euler || is_aeos) && stages == 0 && params.limiter_iterations != 0 && !dg &&
                           L.max_row_len <= (uint32_t)kStage0Width;
   stage0_V = false;
   if (params.limiter_iterations == 2 && d_V.n == 0) {
@@ -1517,154 +1525,100 @@ int ryujin_hip_ctx::step(int h_old, int stages, const int *h_stage, const double
   const uint32_t step5_groups = std::min<uint32_t>(
       4u, resident_waves_step5 /
               std::max<uint32_t>(1u, (L.n_slices + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock));
-  /* ... and P_ij is stored per slice -- only where steps 6 and 7 will read it (kernels_limiter_stage0.hpp) -- where the
-   * update has two limiter passes and one wave per slice, WHILE that pays: its bookkeeping (the prediction and the
-   * trigger in step 5, step 6 as three launches) costs a few per cent of the three sweeps, the savings are
-   * proportional to the share of unlimited slices. Above RYUJIN_PER_SLICE_MAX_LIMITED (the measured break-even,
-   * profiles/r04*_ab_limited_fraction*) the plain kernels run: P_ij stored everywhere, step 6 in one launch. Same
-   * bits either way; the fraction is the one step 6 counted between the two latest host synchronisations (1 until
-   * the first: the first update of a context runs the plain kernels). */
-  const bool per_slice_possible =
-      RYUJIN_PER_SLICE_PIJ && stage0_pij && params.limiter_iterations == 2 && step5_groups < 2;
-  /* Up to two dimensions, finer still: PER TILE. Step 5 stores a (slice, column) tile iff one of its own l_ij comes
-   * out limited or step 6 read the tile in one of the last updates (SliceFlags::needed_tiles); step 6 -- one launch,
-   * the plain kernel -- forms the few tiles that are limited through the neighbour's l_ji alone and were not
-   * predicted (kernels_limiter_stage0.hpp, next_cached_slice). On the Mach-3 step a third to 45 % of the tiles are
-   * stored where 71 - 93 % of the slices would be, and the update is faster than with either alternative at every
-   * stage of the flow (profiles/r05t_ab_tile_*). debug_pij_storage: 0 this; 2 per tile with nothing predicted (tests:
-   * every tile the neighbour's l_ji limits goes through step 6's repair); 1 per slice, nothing predicted; < 0
-   * everywhere, as rounds 1 - 4. Not with the checked build (its kernels read all of P_ij). In 3-D per tile is built
-   * (the tiles step 5 did not store formed by a launch behind step 6, kernels_limiter.hpp: kHoDefer), measured as a
-   * small loss (RYUJIN_TILE_PIJ_DEFAULT_MAXDIM) and selected by debug_pij_storage = 3 (4: nothing predicted) only:
-   * per slice there while few slices are limited, everywhere after that. */
+  /* WHERE STEP 5 STORES P_ij, only where steps 6 and 7 will read it (kernels_limiter_stage0.hpp): where the update has
+   * two limiter passes and one wave per slice, and not in the checked build (its kernels read all of P_ij). Same bits
+   * in every case. debug_pij_storage (create() refuses other values): 0 the default; 1 per slice, nothing predicted;
+   * 2 per tile with nothing predicted (tests: every tile the neighbour's l_ji limits goes through step 6's repair), per
+   * slice as 1 in 3-D; < 0 everywhere, as rounds 1 - 4.
+   *   PER TILE, up to two dimensions: step 5 stores a (slice, column) tile iff one of its own l_ij comes out limited
+   *   or step 6 read the tile in one of the last updates (SliceFlags::needed_tiles); step 6 -- one launch, the plain
+   *   kernel -- forms the few tiles that are limited through the neighbour's l_ji alone and were not predicted
+   *   (kernels_limiter_stage0.hpp, next_cached_slice). On the Mach-3 step a third to 45 % of the tiles are stored
+   *   where 71 - 93 % of the slices would be, and the update is faster than with either alternative at every stage of
+   *   the flow (profiles/r05t_ab_tile_*). (In 3-D per tile was measured as a loss and retired: DESIGN_HISTORY.md.)
+   *   PER SLICE (3-D; debug_pij_storage = 1 in any dimension): WHILE that pays. Its bookkeeping (the prediction and
+   *   the trigger in step 5, step 6 as three launches) costs a few per cent of the three sweeps, the savings are
+   *   proportional to the share of unlimited slices. Above RYUJIN_PER_SLICE_MAX_LIMITED (the measured break-even,
+   *   profiles/r04*_ab_limited_fraction*) the plain kernels run: P_ij stored EVERYWHERE, step 6 in one launch. The
+   *   fraction is the one step 6 counted between the two latest host synchronisations (1 until the first: the first
+   *   update of a context runs the plain kernels). */
   const int storage = params.debug_pij_storage;
-  const bool tile_store = RYUJIN_TILE_PIJ && DIM <= RYUJIN_TILE_PIJ_MAXDIM && per_slice_possible &&
-                          (((storage == 0 || storage == 2) && DIM <= RYUJIN_TILE_PIJ_DEFAULT_MAXDIM) || storage == 3 ||
-                           storage == 4) &&
-                          !params.debug_expensive_bounds_check;
+  const bool selective = stage0_pij && params.limiter_iterations == 2 && step5_groups < 2 && storage >= 0 &&
+                         !params.debug_expensive_bounds_check;
+  const bool tile_store = DIM <= 2 && selective && storage != 1;
   const bool per_slice =
-      per_slice_possible && !tile_store && storage >= 0 && !params.debug_expensive_bounds_check &&
-      (storage == 1 || storage == 2 || limited_fraction <= (double)RYUJIN_PER_SLICE_MAX_LIMITED);
+      selective && !tile_store && (storage != 0 || limited_fraction <= (double)RYUJIN_PER_SLICE_MAX_LIMITED);
+  const bool tiles_predicted_from_history = tile_store && storage == 0;
   ensure_pij();
   if (per_slice && d_slice_first_stored.n == 0) {
     d_slice_first_stored.alloc(L.n_slices);
     d_slice_todo.alloc(L.n_slices);
   }
-  const SliceFlags slice_flags{d_slice_unlimited.ptr, d_slice_first_stored.ptr, d_slice_todo.ptr};
+  if (tiles_predicted_from_history && d_slice_needed.n == 0) { /* all ones: the first update stores every tile */
+    d_slice_needed.alloc(L.n_slices);
+    HIP_CHECK(hipMemsetAsync(d_slice_needed.ptr, 0xff, (size_t)L.n_slices * sizeof(uint32_t), launch_stream));
+  }
   last_per_slice = per_slice;
   last_tile_store = tile_store;
-  const bool tiles_predicted_from_history = tile_store && (storage == 0 || storage == 3);
-  constexpr int kHistoryWords = tile_history_words(kStage0Width);
-  if (tiles_predicted_from_history && d_slice_needed.n == 0) { /* all ones: the first update stores every tile */
-    d_slice_needed.alloc((size_t)L.n_slices * kHistoryWords);
-    HIP_CHECK(hipMemsetAsync(d_slice_needed.ptr, 0xff, (size_t)L.n_slices * kHistoryWords * sizeof(uint32_t),
-                             launch_stream));
-  }
-  /* the tiles step 5 did not store are formed outside the sweep of step 6 (kernels_limiter.hpp, kHoDefer) */
-  constexpr bool kDeferTiles = DIM >= RYUJIN_TILE_DEFER_MINDIM;
-  if (tile_store && kDeferTiles && d_slice_deferred.n == 0)
-    d_slice_deferred.alloc(L.n_slices);
-  const SliceFlags tile_flags{nullptr, nullptr, nullptr,
-                              tiles_predicted_from_history ? d_slice_needed.ptr : nullptr, L.n_slices,
-                              (tile_store && kDeferTiles) ? d_slice_deferred.ptr : nullptr};
+  const SliceFlags slice_flags{d_slice_unlimited.ptr, d_slice_first_stored.ptr, d_slice_todo.ptr};
+  const SliceFlags tile_flags{nullptr, nullptr, nullptr, tiles_predicted_from_history ? d_slice_needed.ptr : nullptr};
   last_s0 = Stage0Src{d_scalars.ptr, old.U.ptr, d_alpha.ptr, d_dij.ptr, d_r.ptr, tile_store ? 1 : 0};
+  /* step 4 stores the first part of P_ij unless step 5 forms it (recompute_p, stage0_pij: Euler and EulerAEOS) */
+  const bool store_p = !(recompute_p || stage0_pij);
   sweep([&](const DeviceMesh &mm, dim3 grid) {
-    if constexpr (is_euler) {
-      if (dg && stages == 0)
-        hipLaunchKernelGGL((k_low_order<DIM, false, true, true>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr,
-                           nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-      else if (dg)
-        hipLaunchKernelGGL((k_low_order<DIM, true, true, true>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr,
-                           nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-      else if (recompute_p || stage0_pij)
-        hipLaunchKernelGGL((k_low_order<DIM, false, false>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr,
-                           nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-      else if (stages == 0)
-        hipLaunchKernelGGL((k_low_order<DIM, false>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr,
-                           nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-      else
-        hipLaunchKernelGGL((k_low_order<DIM, true>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr,
-                           nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-    } else if constexpr (is_scalar) {
-      if (dg && stages == 0)
-        hipLaunchKernelGGL((k_low_order_sc<DIM, false, true>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr,
-                           nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-      else if (dg)
-        hipLaunchKernelGGL((k_low_order_sc<DIM, true, true>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr,
-                           nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-      else if (stages == 0)
-        hipLaunchKernelGGL((k_low_order_sc<DIM, false>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr,
-                           nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-      else
-        hipLaunchKernelGGL((k_low_order_sc<DIM, true>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr,
-                           nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-    } else if constexpr (is_aeos) {
-      if (dg && stages == 0)
-        hipLaunchKernelGGL((k_low_order_aeos<DIM, false, true, true>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr,
-                           nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-      else if (dg)
-        hipLaunchKernelGGL((k_low_order_aeos<DIM, true, true, true>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr,
-                           nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-      else if (stage0_pij)
-        hipLaunchKernelGGL((k_low_order_aeos<DIM, false, false>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr,
-                           nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-      else if (stages == 0)
-        hipLaunchKernelGGL((k_low_order_aeos<DIM, false>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr,
-                           nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-      else
-        hipLaunchKernelGGL((k_low_order_aeos<DIM, true>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr,
-                           nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-    } else {
+    if constexpr (is_sw) {
       /* rows of at most 3 / 9 columns (1-D, 2-D Q1): one walk over the stencil, the shift-free part of the
        * limiter's U_ij_bar parked in LDS (kernels_shallow_water.hpp); wider rows: the two walks of the reference */
       constexpr int kSwWidth = DIM == 1 ? 3 : 9;
-      const bool single_walk = RYUJIN_SW_SINGLE_WALK && !dg && L.max_row_len <= (uint32_t)kSwWidth;
       auto launch_single_walk = [&](auto has_stages, auto friction) {
         hipLaunchKernelGGL((k_low_order_sw_single_walk<DIM, decltype(has_stages)::value, kSwWidth,
                                                        decltype(friction)::value>),
                            grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr, weight, S, old.U.ptr,
                            old.prec.ptr, d_Z.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
       };
-      const bool friction = eparams.manning != 0.;
-      if (single_walk && stages == 0 && friction)
-        launch_single_walk(std::false_type{}, std::true_type{});
-      else if (single_walk && stages == 0)
-        launch_single_walk(std::false_type{}, std::false_type{});
-      else if (single_walk && friction)
-        launch_single_walk(std::true_type{}, std::true_type{});
-      else if (single_walk)
-        launch_single_walk(std::true_type{}, std::false_type{});
-      else if (dg && stages == 0)
-        hipLaunchKernelGGL((k_low_order_sw<DIM, false, true>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_Z.ptr, d_alpha.ptr,
-                           d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-      else if (dg)
-        hipLaunchKernelGGL((k_low_order_sw<DIM, true, true>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_Z.ptr, d_alpha.ptr,
-                           d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-      else if (stages == 0)
-        hipLaunchKernelGGL((k_low_order_sw<DIM, false>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_Z.ptr, d_alpha.ptr,
-                           d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-      else
-        hipLaunchKernelGGL((k_low_order_sw<DIM, true>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_Z.ptr, d_alpha.ptr,
-                           d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
+      if (!dg && L.max_row_len <= (uint32_t)kSwWidth) {
+        const bool friction = eparams.manning != 0.;
+        if (stages == 0 && friction)
+          launch_single_walk(std::false_type{}, std::true_type{});
+        else if (stages == 0)
+          launch_single_walk(std::false_type{}, std::false_type{});
+        else if (friction)
+          launch_single_walk(std::true_type{}, std::true_type{});
+        else
+          launch_single_walk(std::true_type{}, std::false_type{});
+        return;
+      }
     }
+    /* the kernel of the Description with stage vectors, the first part of P_ij stored (Euler, EulerAEOS), dG */
+    auto launch4 = [&](auto has_stages, auto stores_p, auto dg_) {
+      constexpr bool HS = decltype(has_stages)::value, SP = decltype(stores_p)::value, DG = decltype(dg_)::value;
+      if constexpr (is_euler)
+        hipLaunchKernelGGL((k_low_order<DIM, HS, SP, DG>), grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr,
+                           weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr,
+                           d_bounds.ptr, d_pij.ptr);
+      else if constexpr (is_aeos)
+        hipLaunchKernelGGL((k_low_order_aeos<DIM, HS, SP, DG>), grid, block, 0, launch_stream, eparams, mm,
+                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr,
+                           d_r.ptr, d_bounds.ptr, d_pij.ptr);
+      else if constexpr (is_scalar)
+        hipLaunchKernelGGL((k_low_order_sc<DIM, HS, DG>), grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr,
+                           weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr,
+                           d_bounds.ptr, d_pij.ptr);
+      else
+        hipLaunchKernelGGL((k_low_order_sw<DIM, HS, DG>), grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr,
+                           weight, S, old.U.ptr, old.prec.ptr, d_Z.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr,
+                           d_bounds.ptr, d_pij.ptr);
+    };
+    if (dg && stages == 0)
+      launch4(std::false_type{}, std::true_type{}, std::true_type{});
+    else if (dg)
+      launch4(std::true_type{}, std::true_type{}, std::true_type{});
+    else if (!store_p)
+      launch4(std::false_type{}, std::false_type{}, std::false_type{});
+    else if (stages == 0)
+      launch4(std::false_type{}, std::true_type{}, std::false_type{});
+    else
+      launch4(std::true_type{}, std::true_type{}, std::false_type{});
   });
   /* EXPENSIVE_BOUNDS_CHECK as a run-time option (Euler): is_admissible() of the low-order update (:851-855) */
   const bool checked = params.debug_expensive_bounds_check != 0;
@@ -1709,34 +1663,29 @@ int ryujin_hip_ctx::step(int h_old, int stages, const int *h_stage, const double
         if (stage0_pij) {
           /* small meshes: up to four waves per slice, each taking a share of the columns (decided for the whole
            * mesh, not per launch: the export and the interior part of a split sweep must agree on whether V_i exists) */
-          const uint32_t groups = step5_groups;
-          auto launch5 = [&](auto ny) {
-            constexpr int NY = decltype(ny)::value;
-            hipLaunchKernelGGL((k_lij_stage0<E, NY>), dim3(grid.x, NY), block, 0, launch_stream, eparams, mm,
-                               d_scalars.ptr, old.U.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr,
-                               d_pij.ptr, d_lij.ptr, NY == 1 ? d_V.ptr : nullptr, tile_flags, 0);
-            stage0_V = NY == 1 && d_V.ptr != nullptr;
-          };
-          if (tile_store && groups < 2) { /* (tile_store implies one wave per slice) */
-            hipLaunchKernelGGL((k_lij_stage0<E, 1, false, true>), grid, block, 0, launch_stream, eparams, mm,
-                               d_scalars.ptr, old.U.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr,
-                               d_pij.ptr, d_lij.ptr, d_V.ptr, tile_flags, 0);
-            stage0_V = d_V.ptr != nullptr;
-            return;
+          if constexpr (DIM <= 2) {
+            if (tile_store) { /* (tile_store implies one wave per slice) */
+              hipLaunchKernelGGL((k_lij_stage0<E, 1, false, true>), grid, block, 0, launch_stream, eparams, mm,
+                                 d_scalars.ptr, old.U.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr,
+                                 d_pij.ptr, d_lij.ptr, d_V.ptr, tile_flags, 0);
+              stage0_V = d_V.ptr != nullptr;
+              return;
+            }
           }
           if (per_slice) {
             hipLaunchKernelGGL((k_lij_stage0<E, 1, true>), grid, block, 0, launch_stream, eparams, mm,
                                d_scalars.ptr, old.U.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr,
                                d_pij.ptr, d_lij.ptr, d_V.ptr, slice_flags, params.debug_pij_storage);
             stage0_V = true;
-          } else if (groups >= 4)
-            launch5(std::integral_constant<int, 4>{});
-          else if (groups == 3)
-            launch5(std::integral_constant<int, 3>{});
-          else if (groups == 2)
-            launch5(std::integral_constant<int, 2>{});
-          else
-            launch5(std::integral_constant<int, 1>{});
+            return;
+          }
+          with_groups(step5_groups, [&](auto ny) {
+            constexpr int NY = decltype(ny)::value;
+            hipLaunchKernelGGL((k_lij_stage0<E, NY>), dim3(grid.x, NY), block, 0, launch_stream, eparams, mm,
+                               d_scalars.ptr, old.U.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr,
+                               d_pij.ptr, d_lij.ptr, NY == 1 ? d_V.ptr : nullptr, tile_flags, 0);
+            stage0_V = NY == 1 && d_V.ptr != nullptr;
+          });
           return;
         }
       }
@@ -1744,21 +1693,13 @@ int ryujin_hip_ctx::step(int h_old, int stages, const int *h_stage, const double
         if (recompute_p) {
           /* small meshes: up to four waves per slice, each taking a share of the columns (see the kernel), as
            * long as all of them are resident at once (256 CUs x 4 SIMDs x 2 waves of this kernel) */
-          const uint32_t groups = std::min<uint32_t>(4u, resident_waves_step5 / std::max<uint32_t>(1u, grid.x * kWavesPerBlock));
-          auto launch5 = [&](auto ny) {
+          const uint32_t groups = resident_waves_step5 / std::max<uint32_t>(1u, grid.x * kWavesPerBlock);
+          with_groups(groups, [&](auto ny) {
             constexpr int NY = decltype(ny)::value;
             hipLaunchKernelGGL((k_pij_lij_recompute<DIM, NY>), dim3(grid.x, NY), block, 0, launch_stream, eparams,
                                mm, d_scalars.ptr, weight, old.U.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr,
                                d_bounds.ptr, d_pij.ptr, d_lij.ptr);
-          };
-          if (groups >= 4)
-            launch5(std::integral_constant<int, 4>{});
-          else if (groups == 3)
-            launch5(std::integral_constant<int, 3>{});
-          else if (groups == 2)
-            launch5(std::integral_constant<int, 2>{});
-          else
-            launch5(std::integral_constant<int, 1>{});
+          });
           return;
         }
       }
@@ -1800,7 +1741,7 @@ int ryujin_hip_ctx::step(int h_old, int stages, const int *h_stage, const double
    * sweep of its own (large meshes: below bc_fold_max_slices the boundary conditions ride on that sweep) */
   bool fuse_precompute = false;
   if constexpr (E::kFusablePrecompute)
-    fuse_precompute = RYUJIN_FUSE_PRECOMPUTE && pending_precompute && n_iterations != 0 &&
+    fuse_precompute = pending_precompute && n_iterations != 0 &&
                       L.n_slices > bc_fold_max_slices &&
                       L.max_row_len <= (uint32_t)(DIM == 1 ? 3 : (DIM == 2 ? 9 : 27));
   pending_precompute = false;
@@ -1826,8 +1767,8 @@ int ryujin_hip_ctx::step(int h_old, int stages, const int *h_stage, const double
                              d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_lij_next.ptr, fused_sadd);
       });
     } else {
-      /* 3-D: cache all l_ij and the P_ij of the first RYUJIN_HO_CP_3D columns (0: two-pass kernel) */
-      constexpr int kCachedP = DIM == 3 ? (RYUJIN_HO_CP_3D > 0 ? RYUJIN_HO_CP_3D : 27)
+      /* 3-D: cache all l_ij and the P_ij of the first RYUJIN_HO_CP_3D columns */
+      constexpr int kCachedP = DIM == 3 ? RYUJIN_HO_CP_3D
                                         : (DIM == 2 ? (RYUJIN_HO_CP_2D < kCachedWidth ? RYUJIN_HO_CP_2D : kCachedWidth) : kCachedWidth);
       sweep([&](const DeviceMesh &mm, dim3 grid) {
         if constexpr (is_euler || is_aeos) {
@@ -1860,27 +1801,13 @@ int ryujin_hip_ctx::step(int h_old, int stages, const int *h_stage, const double
             return;
           }
         }
-        if ((DIM <= 2 || RYUJIN_HO_CP_3D > 0) && L.max_row_len <= (uint32_t)kCachedWidth) {
+        if (L.max_row_len <= (uint32_t)kCachedWidth) {
+          /* (with P_ij stored per tile the plain kernel forms the tiles step 5 left out: forms_missing_tiles) */
           SliceFlags flags6 = tile_flags;
           flags6.unlimited = stage0_V ? d_slice_unlimited.ptr : nullptr;
-          bool launched = false;
-          if constexpr (kDeferTiles && (is_euler || is_aeos)) {
-            if (tile_store && stage0_V) {
-              /* the sweep, and behind it the slices that missed a tile (a grid of fixed size walks the list) */
-              hipLaunchKernelGGL((k_high_order_next_cached<E, kCachedWidth, kCachedP, false, kHoDefer>), grid, block,
-                                 0, launch_stream, eparams, mm, nw.U.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr,
-                                 d_lij_next.ptr, d_V.ptr, last_s0, flags6);
-              hipLaunchKernelGGL((k_high_order_next_deferred<E, kCachedWidth>),
-                                 dim3(std::min<uint32_t>(grid.x * kWavesPerBlock, 512u)), block, 0, launch_stream, eparams, mm,
-                                 nw.U.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_lij_next.ptr, d_V.ptr, last_s0,
-                                 flags6);
-              launched = true;
-            }
-          }
-          if (!launched)
-            hipLaunchKernelGGL((k_high_order_next_cached<E, kCachedWidth, kCachedP>), grid, block, 0,
-                               launch_stream, eparams, mm, nw.U.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr,
-                               d_lij_next.ptr, stage0_V ? d_V.ptr : nullptr, last_s0, flags6);
+          hipLaunchKernelGGL((k_high_order_next_cached<E, kCachedWidth, kCachedP>), grid, block, 0, launch_stream,
+                             eparams, mm, nw.U.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_lij_next.ptr,
+                             stage0_V ? d_V.ptr : nullptr, last_s0, flags6);
           step6_flags = stage0_V;
         } else if (L.max_row_len > 64)
           hipLaunchKernelGGL((k_high_order<E, false, true>), grid, block, 0, launch_stream, eparams, mm, nw.U.ptr,
@@ -2916,16 +2843,6 @@ int ryujin_hip_tile_statistics(ryujin_hip_ctx *ctx, double *stored_fraction, dou
       *read_fraction = tiles ? ctx->tiles_needed_fraction : 1.;
     if (formed_by_step6_fraction)
       *formed_by_step6_fraction = tiles ? ctx->tiles_formed_fraction : 0.;
-    return RYUJIN_OK;
-  });
-}
-
-int ryujin_hip_deferred_slices(ryujin_hip_ctx *ctx, unsigned *n_slices)
-{
-  return guarded([&]() {
-    if (!ctx || !n_slices)
-      throw HipError(RYUJIN_ERR_ARG, "null argument");
-    *n_slices = ctx->h_scalars ? ctx->h_scalars->n_deferred[0] + ctx->h_scalars->n_deferred[1] : 0u;
     return RYUJIN_OK;
   });
 }

@@ -164,14 +164,26 @@ def test_step_parity_3d_radial_contrast(oracle, n=12, warm=(4,)):
     spec = offline.box_3d(n)
     off0 = offline.SyntheticOffline(spec)
     U0 = euler_radial_contrast(off0.positions, radius=0.4)
-    deferred = []
     for n_warm in warm:
         off, mods = _both(spec, U0, oracle, n_warm=n_warm)
         _compare_step(off, mods)
-        deferred.append(mods[0][0].limiter_statistics().get("deferred_slices_last_update"))
-    if HyperbolicModule.library_switches.get("debug_pij_storage") == 4:
-        # nothing predicted: every tile the neighbour's l_ji alone limits goes through the launch behind step 6
-        assert min(deferred) > 0, deferred
+
+
+def test_create_refuses_the_retired_pij_storage_modes():
+    """debug_pij_storage 3 and 4 selected P_ij per tile in 3-D, measured as a loss and retired
+    (profiles/variant_r06_tile_pij_3d_deferred.patch): create() refuses them."""
+    import ctypes as C
+    lib = capi.load_hip()
+    off = offline.SyntheticOffline(offline.box_3d(4))
+    for storage in (3, 4):
+        p = capi.Params()
+        lib.ryujin_hip_default_params(C.byref(p), capi.EQ_EULER, 3)
+        p.debug_pij_storage = storage
+        ctx = C.c_void_p()
+        rc = lib.ryujin_hip_create(C.byref(ctx), off.c, C.byref(p), None, 0)
+        if rc >= 0:
+            lib.ryujin_hip_destroy(ctx)
+        assert rc == capi.RYUJIN_ERR_ARG, (storage, rc)
 
 
 def test_step_parity_1d(oracle):
@@ -2009,8 +2021,8 @@ def test_unstructured_p1_mesh_scalar_conservation(oracle):
                                    "aeos_2d:no_prediction", "euler_2d:always_store", "aeos_2d:always_store",
                                    "euler_2d:no_tile_prediction", "euler_1d:no_tile_prediction",
                                    "aeos_2d:no_tile_prediction",
-                                   "euler_3d", "euler_3d:tile", "euler_3d:tile_unpredicted", "euler_3d:no_prediction",
-                                   "euler_3d:always_store", "aeos_3d:tile", "aeos_3d:tile_unpredicted"])
+                                   "euler_3d", "euler_3d:no_prediction", "euler_3d:always_store", "aeos_3d",
+                                   "aeos_3d:no_prediction"])
 def test_step_parity_with_the_kernels_of_large_meshes(oracle, monkeypatch, which):
     """The meshes of this file do not fill an MI355X, so they take the small-mesh branches of the library
     (boundary conditions folded into the pre-pass, steps 5 and 6 with the columns of a slice spread over several
@@ -2018,10 +2030,9 @@ def test_step_parity_with_the_kernels_of_large_meshes(oracle, monkeypatch, which
     run (also covered at full size for Euler and shallow water in test_gpu_parity_fullsize.py).
     An update without stage vectors stores P_ij only where steps 6 and 7 read it (kernels_limiter_stage0.hpp): per
     (slice, column) tile -- the default up to two dimensions: where one of the tile's own l_ij comes out limited or
-    step 6 read the tile in one of the last updates, step 6 forming what is missing (inside the sweep up to two
-    dimensions; in 3-D, where the scheme is built but not the default, `:tile`, in a launch of its own over the slices
-    that missed a tile); `:no_tile_prediction` / `:tile_unpredicted` predict no tile
-    (every tile that the neighbour's l_ji alone limits goes through step 6's repair). Per 64-row slice
+    step 6 read the tile in one of the last updates, step 6 forming what is missing inside its sweep;
+    `:no_tile_prediction` predicts no tile (every tile that the neighbour's l_ji alone limits goes through step 6's
+    repair). Per 64-row slice
     (3-D, and `:no_prediction` here): where the slice
     held a limited pair in the previous update -- the first update of a context stores everywhere --, or where one
     of its own l_ij comes out limited (stored from that column on, the columns before it formed a second time);
@@ -2032,8 +2043,7 @@ def test_step_parity_with_the_kernels_of_large_meshes(oracle, monkeypatch, which
     switches = {"debug_no_small_mesh_split": 1, "debug_bc_fold_max_slices": -1}
     which, _, variant = which.partition(":")
     if variant:
-        switches["debug_pij_storage"] = {"no_prediction": 1, "always_store": -1, "no_tile_prediction": 2, "tile": 3,
-                                         "tile_unpredicted": 4}[variant]
+        switches["debug_pij_storage"] = {"no_prediction": 1, "always_store": -1, "no_tile_prediction": 2}[variant]
     monkeypatch.setattr(HyperbolicModule, "library_switches", switches)
     {
         "euler_2d": lambda: test_step_parity_2d_step_geometry(oracle),

@@ -10,7 +10,8 @@ memory, behind a workgroup-scope fence. VERDICT round 5 asked for evidence inste
     no lane ever reads another lane's stores) -- the same function on the same operands: the same bits.
 
 Step 5 (first limiter pass, P_ij formed and stored in the same kernel), step 6 (second pass; in 2-D including the tiles
-it forms itself) and, through U, step 7 are covered; 2-D with P_ij per tile, stored everywhere and per slice, and 3-D."""
+it forms itself) and, through U, step 7 are covered; 2-D with P_ij per tile, stored everywhere and per slice, and 3-D
+per slice and stored everywhere (the default path of a developed 3-D flow, with the row data parked in LDS)."""
 import ctypes as C
 import os
 import sys
@@ -64,10 +65,10 @@ def _update(lib, off, U_start, dirichlet, storage, dim):
     return out
 
 
-@pytest.mark.parametrize("case", ["2d:tile", "2d:everywhere", "2d:per_slice", "3d:per_slice", "3d:tile"])
+@pytest.mark.parametrize("case", ["2d:tile", "2d:everywhere", "2d:per_slice", "3d:per_slice", "3d:everywhere"])
 def test_compacted_tail_reads_what_other_lanes_stored(case):
     kind, storage_name = case.split(":")
-    storage = {"tile": 3, "everywhere": -1, "per_slice": 1}[storage_name]
+    storage = {"tile": 0, "everywhere": -1, "per_slice": 1}[storage_name]
     rng = np.random.default_rng(5)
     lib = capi.load_hip()
     if kind == "2d":
