@@ -567,6 +567,44 @@ int ryujin_hip_debug_rk_outcome(int restart_accum, int tau_invalid_accum, int id
 const char *ryujin_hip_last_error(void);
 const char *ryujin_hip_version(void);
 
+/* ---- Postprocessor: schlieren and vorticity fields, device resident ------ */
+/* Postprocessor::compute() of the reference (source/postprocessor.template.h:108-271, steps 1 - 3) on the state
+ * vector behind a handle. For every owned row i with more than one stencil entry and every configured quantity q
+ * -- a component of the conserved state U_j, or of to_primitive_state(U_j) of the context's Description
+ * (Euler (rho, v, p); EulerAEOS (rho, v, e), e the specific internal energy; shallow water (h, v) with the sharp
+ * inverse water depth; scalar conservation u), computed from U itself, whether or not prepare_state_vector has
+ * run on that vector:
+ *   schlieren  s_i = | sum_j c_ij q_j | / m_i
+ *   vorticity  of the dim consecutive components starting at `component`:
+ *              dim = 2: w_i = sum_j (c_ij,x q_j,y - c_ij,y q_j,x) / m_i, SIGNED (a counter-clockwise rigid rotation
+ *              of angular speed omega gives +2 omega); dim = 3: w_i = | sum_j c_ij x q_j | / m_i; refused in 1-D.
+ * Rows of length 1 (constrained DoFs) get 0. ryujin_hip_offline carries no affine constraints, so step 4 of the
+ * reference (AffineConstraints::distribute) has no counterpart here.
+ * Bounds per quantity over the owned rows of ALL ranks: q_max = max |.| starting from 0, q_min = min |.|; with
+ * recompute_bounds = 0 the bounds of the first compute() after configure() are kept for the later ones
+ * ("schlieren recompute bounds" of the reference). Normalised value, with eps = DBL_EPSILON, floor = 1e-10:
+ *   r = max(0, |v| - q_min - floor) / max(q_max - q_min, eps),   copysign(1 - exp(-beta r), v).
+ * compute() is collective over the ranks of the context's communicator (it exchanges the ghost range of the state
+ * vector and reduces the bounds); on one rank and over RCCL it is asynchronous on the context's stream.
+ * RYUJIN_ERR_ARG: n_quantities outside [1, RYUJIN_PP_MAX_QUANTITIES], an unknown kind, a component outside the
+ * state, a vorticity in 1-D or one whose dim components do not fit the state, compute() before configure(),
+ * download() / bounds() before compute() or for a quantity that was not configured. */
+#define RYUJIN_PP_MAX_QUANTITIES 8
+enum { RYUJIN_PP_SCHLIEREN = 0, RYUJIN_PP_VORTICITY = 1 };
+typedef struct ryujin_hip_postprocess_quantity {
+  int kind;         /* RYUJIN_PP_SCHLIEREN, RYUJIN_PP_VORTICITY */
+  int is_primitive; /* 0: component of U, 1: of to_primitive_state(U) */
+  int component;    /* index; vorticity: the first of dim consecutive components */
+} ryujin_hip_postprocess_quantity;
+/* reference defaults: beta = 10, recompute_bounds = 1 */
+int ryujin_hip_postprocess_configure(ryujin_hip_ctx *ctx, int n_quantities,
+                                     const ryujin_hip_postprocess_quantity *quantities, double beta,
+                                     int recompute_bounds);
+int ryujin_hip_postprocess_compute(ryujin_hip_ctx *ctx, int state_handle);
+/* out [n_owned]: quantity q of the latest compute(); raw != 0: the values before the normalisation */
+int ryujin_hip_postprocess_download(ryujin_hip_ctx *ctx, int q, double *out, int raw);
+int ryujin_hip_postprocess_bounds(ryujin_hip_ctx *ctx, int q, double *q_max, double *q_min);
+
 #ifdef __cplusplus
 }
 #endif

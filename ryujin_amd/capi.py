@@ -97,6 +97,39 @@ class SynthSpec(C.Structure):
     ]
 
 
+PP_SCHLIEREN, PP_VORTICITY = 0, 1
+PP_MAX_QUANTITIES = 8
+
+
+class PostprocessQuantity(C.Structure):
+    _fields_ = [("kind", C.c_int), ("is_primitive", C.c_int), ("component", C.c_int)]
+
+
+def component_names(equation: int, dim: int) -> tuple[tuple[str, ...], tuple[str, ...]]:
+    """(View::component_names, View::primitive_component_names) of a Description
+    (source/<eq>/hyperbolic_system.h)."""
+    def vec(name: str) -> tuple[str, ...]:
+        return (name,) if dim == 1 else tuple(f"{name}_{d + 1}" for d in range(dim))
+    if equation == EQ_EULER:
+        return ("rho", *vec("m"), "E"), ("rho", *vec("v"), "p")
+    if equation == EQ_EULER_AEOS:
+        return ("rho", *vec("m"), "E"), ("rho", *vec("v"), "e")
+    if equation == EQ_SHALLOW_WATER:
+        return ("h", *vec("m")), ("h", *vec("v"))
+    if equation == EQ_SCALAR_CONSERVATION:
+        return ("u",), ("u",)
+    raise ValueError(f"unknown equation {equation}")
+
+
+def resolve_component(equation: int, dim: int, name: str) -> tuple[int, int]:
+    """(is_primitive, index) of a component name: the conserved names first, the primitive names second, as
+    Postprocessor::prepare() (source/postprocessor.template.h:73-93); ValueError for an unknown name."""
+    for is_primitive, names in enumerate(component_names(equation, dim)):
+        if name in names:
+            return is_primitive, names.index(name)
+    raise ValueError(f"Invalid component name »{name}«")
+
+
 def as_ptr(a: np.ndarray, typ):
     return a.ctypes.data_as(typ)
 
@@ -180,6 +213,8 @@ HIP_SYMBOLS = [
     "ryujin_hip_set_timers", "ryujin_hip_get_timers", "ryujin_hip_synchronize",
     "ryujin_hip_event_record", "ryujin_hip_event_elapsed_ms", "ryujin_hip_last_error",
     "ryujin_hip_version", "ryujin_hip_debug_layout", "ryujin_hip_debug_pow", "ryujin_hip_debug_function", "ryujin_hip_debug_rk_outcome",
+    "ryujin_hip_postprocess_configure", "ryujin_hip_postprocess_compute", "ryujin_hip_postprocess_download",
+    "ryujin_hip_postprocess_bounds",
 ]
 
 
@@ -265,5 +300,10 @@ def load_hip():
         lib.ryujin_hip_debug_rk_outcome.argtypes = [C.c_int, C.c_int, C.c_int]
         lib.ryujin_hip_debug_function.argtypes = [C.c_int, C.POINTER(Params), C.c_int, c_double_p, c_double_p,
                                                   C.c_size_t]
+        lib.ryujin_hip_postprocess_configure.argtypes = [vp, C.c_int, C.POINTER(PostprocessQuantity), C.c_double,
+                                                         C.c_int]
+        lib.ryujin_hip_postprocess_compute.argtypes = [vp, C.c_int]
+        lib.ryujin_hip_postprocess_download.argtypes = [vp, C.c_int, c_double_p, C.c_int]
+        lib.ryujin_hip_postprocess_bounds.argtypes = [vp, C.c_int, c_double_p, c_double_p]
         _hip = lib
     return _hip

@@ -45,6 +45,7 @@
 #include "kernels_euler_aeos.hpp"
 #include "kernels_shallow_water.hpp"
 #include "scalar_conservation_device.hpp"
+#include "kernels_postprocessor.hpp"
 
 using namespace ryujin_hip;
 
@@ -447,6 +448,14 @@ struct ryujin_hip_ctx {
   DeviceBuffer<DeviceScalars> d_scalars;
   DeviceBuffer<double> d_integrals; /* ryujin_hip_state_integrals: block partials + result */
   DeviceScalars *h_scalars = nullptr; /* pinned */
+  /* Postprocessor (ryujin_hip_postprocess_*, kernels_postprocessor.hpp): allocated by the first compute */
+  PostprocessDesc pp_desc{};
+  double pp_beta = 10.;
+  bool pp_recompute_bounds = true, pp_configured = false, pp_have_bounds = false, pp_computed = false;
+  DeviceBuffer<double> d_pp_raw, d_pp_normalised;  /* SoA [n_quantities][n_owned] */
+  DeviceBuffer<unsigned long long> d_pp_bounds;    /* [2][kPostprocessMaxQuantities]: q_max, q_min (bit patterns) */
+  template <typename E>
+  void postprocess_compute(int h);
   /* time-dependent Dirichlet data inside a device-resident RK step (ryujin_hip_time_step_fn): the tau of the
    * first stage is copied to the host as soon as it exists (behind step 3 of the first stage), the later stages'
    * boundary data is evaluated at t + c_s tau while the rest of the first stage runs */
@@ -2115,6 +2124,79 @@ int ryujin_hip_ctx::time_step(int scheme, int h_state, int n_tmp, const int *h_t
   return status;
 }
 
+/* Postprocessor::compute() (source/postprocessor.template.h:108-271) on the device: ghost exchange of the state
+ * vector (the sweep gathers ghost U_j), one sweep for all quantities, the bounds reduced over the ranks, the
+ * normalisation. One rank / RCCL: nothing here waits for the device. */
+template <typename E>
+void ryujin_hip_ctx::postprocess_compute(int h)
+{
+  State &s = state(h);
+  const uint32_t n_owned = L.n_owned;
+  const int n = pp_desc.n;
+  constexpr int MAXQ = kPostprocessMaxQuantities;
+  if (d_pp_raw.n != (size_t)n * n_owned) {
+    d_pp_raw.alloc((size_t)n * n_owned);
+    d_pp_normalised.alloc((size_t)n * n_owned);
+  }
+  if (d_pp_bounds.n == 0)
+    d_pp_bounds.alloc(2 * MAXQ);
+  wait_comm();
+  exchange_vector(s.U.ptr, KP, false);
+  wait_comm();
+
+  const bool fold_bounds = pp_recompute_bounds || !pp_have_bounds;
+  if (fold_bounds)
+    hipLaunchKernelGGL(k_postprocess_reset_bounds, dim3(1), dim3(64), 0, stream, d_pp_bounds.ptr);
+  DeviceMesh mm = mesh;
+  mm.begin = StepBegin{};
+  mm.slice_begin = 0;
+  mm.slice_end = L.n_slices;
+  const dim3 grid((L.n_slices + kWavesPerBlock - 1) / kWavesPerBlock);
+  hipLaunchKernelGGL((k_postprocess_sweep<E, tile_map_pays<E::DIMENSION>()>), grid, dim3(kBlock), 0, stream,
+                     eq_params<E>(), mm, pp_desc, fold_bounds ? 1 : 0, s.U.ptr, d_pp_raw.ptr, d_pp_bounds.ptr);
+  HIP_CHECK(hipGetLastError());
+
+  if (fold_bounds && comm && comm->n_ranks > 1) {
+    /* over the ranks, as ryujin_hip_state_integrals reduces its sums (the bit patterns are those of non-negative
+     * doubles: reduced as doubles) */
+    double *b = reinterpret_cast<double *>(d_pp_bounds.ptr);
+    if (!comm->local) {
+      ++n_allreduces;
+      NCCL_CHECK(ncclAllReduce(b, b, MAXQ, ncclDouble, ncclMax, comm->comm, stream));
+      NCCL_CHECK(ncclAllReduce(b + MAXQ, b + MAXQ, MAXQ, ncclDouble, ncclMin, comm->comm, stream));
+    } else if (!comm->local->loopback) {
+      static_assert(MAXQ <= 8, "LocalGroup::scratch_vec holds 8 doubles per rank");
+      LocalGroup &g = *comm->local;
+      double host[2 * MAXQ];
+      HIP_CHECK(hipMemcpyAsync(host, b, sizeof(host), hipMemcpyDeviceToHost, stream));
+      HIP_CHECK(hipStreamSynchronize(stream));
+      for (int part = 0; part < 2; ++part) { /* q_max, then q_min */
+        for (int q = 0; q < MAXQ; ++q)
+          g.scratch_vec[(size_t)comm->rank * 8 + q] = host[part * MAXQ + q];
+        g.barrier();
+        for (int q = 0; q < MAXQ; ++q) {
+          double v = g.scratch_vec[q];
+          for (int r = 1; r < g.n_ranks; ++r) {
+            const double w = g.scratch_vec[(size_t)r * 8 + q];
+            v = part == 0 ? std::max(v, w) : std::min(v, w);
+          }
+          host[part * MAXQ + q] = v;
+        }
+        g.barrier();
+      }
+      HIP_CHECK(hipMemcpyAsync(b, host, sizeof(host), hipMemcpyHostToDevice, stream));
+      HIP_CHECK(hipStreamSynchronize(stream)); /* host[] goes out of scope */
+    }
+  }
+  pp_have_bounds = true;
+
+  const size_t total = (size_t)n * n_owned;
+  hipLaunchKernelGGL(k_postprocess_normalise, dim3(std::min<size_t>(grid_for(total), 4096)), dim3(kBlock), 0, stream,
+                     n_owned, n, pp_beta, d_pp_bounds.ptr, d_pp_raw.ptr, d_pp_normalised.ptr);
+  HIP_CHECK(hipGetLastError());
+  pp_computed = true;
+}
+
 /* ============================================================================ C ABI */
 
 namespace
@@ -3263,6 +3345,97 @@ int ryujin_hip_event_elapsed_ms(ryujin_hip_ctx *ctx, double *ms)
     float f = 0.f;
     HIP_CHECK(hipEventElapsedTime(&f, ctx->ev_user[0], ctx->ev_user[1]));
     *ms = f;
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_postprocess_configure(ryujin_hip_ctx *ctx, int n_quantities,
+                                     const ryujin_hip_postprocess_quantity *quantities, double beta,
+                                     int recompute_bounds)
+{
+  return guarded_ctx(ctx, [&]() {
+    if (n_quantities < 1 || n_quantities > RYUJIN_PP_MAX_QUANTITIES || !quantities)
+      throw HipError(RYUJIN_ERR_ARG, "postprocess_configure: n_quantities must be in [1, " +
+                                         std::to_string(RYUJIN_PP_MAX_QUANTITIES) + "]");
+    if (std::isnan(beta))
+      throw HipError(RYUJIN_ERR_ARG, "postprocess_configure: beta is NaN");
+    static_assert(RYUJIN_PP_MAX_QUANTITIES == kPostprocessMaxQuantities, "header and kernels agree");
+    static_assert(RYUJIN_PP_SCHLIEREN == kPostprocessSchlieren && RYUJIN_PP_VORTICITY == kPostprocessVorticity,
+                  "header and kernels agree");
+    PostprocessDesc d{};
+    d.n = n_quantities;
+    for (int q = 0; q < n_quantities; ++q) {
+      const auto &in = quantities[q];
+      if (in.kind != RYUJIN_PP_SCHLIEREN && in.kind != RYUJIN_PP_VORTICITY)
+        throw HipError(RYUJIN_ERR_ARG, "postprocess_configure: unknown kind " + std::to_string(in.kind));
+      if (in.component < 0 || in.component >= ctx->K)
+        throw HipError(RYUJIN_ERR_ARG, "postprocess_configure: component " + std::to_string(in.component) +
+                                           " out of range [0, " + std::to_string(ctx->K) + ")");
+      if (in.kind == RYUJIN_PP_VORTICITY) {
+        if (ctx->dim == 1)
+          throw HipError(RYUJIN_ERR_ARG, "postprocess_configure: vorticity is not defined in 1-D");
+        if (in.component + ctx->dim > ctx->K)
+          throw HipError(RYUJIN_ERR_ARG, "postprocess_configure: the dim components of a vorticity starting at " +
+                                             std::to_string(in.component) + " do not fit the state");
+      }
+      d.kind[q] = in.kind;
+      d.select[q] = (in.is_primitive ? ctx->K : 0) + in.component;
+      d.any_primitive = d.any_primitive || in.is_primitive;
+      const int n_components = in.kind == RYUJIN_PP_VORTICITY ? ctx->dim : 1;
+      for (int c = in.component; c < in.component + n_components; ++c)
+        d.load_mask |= 1 << (c / 2);
+    }
+    if (d.any_primitive) /* a primitive state needs all of U_j */
+      d.load_mask = (1 << (ctx->KP / 2)) - 1;
+    ctx->pp_desc = d;
+    ctx->pp_beta = beta;
+    ctx->pp_recompute_bounds = recompute_bounds != 0;
+    ctx->pp_configured = true;
+    ctx->pp_have_bounds = false;
+    ctx->pp_computed = false;
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_postprocess_compute(ryujin_hip_ctx *ctx, int handle)
+{
+  return guarded_ctx(ctx, [&]() {
+    if (!ctx->pp_configured)
+      throw HipError(RYUJIN_ERR_ARG, "postprocess_compute before postprocess_configure");
+    dispatch_equation(ctx->params.equation, ctx->dim, [&](auto tag) {
+      ctx->template postprocess_compute<typename decltype(tag)::type>(handle);
+      return 0;
+    });
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_postprocess_download(ryujin_hip_ctx *ctx, int q, double *out, int raw)
+{
+  return guarded_ctx(ctx, [&]() {
+    if (!ctx->pp_computed)
+      throw HipError(RYUJIN_ERR_ARG, "postprocess_download before postprocess_compute");
+    if (q < 0 || q >= ctx->pp_desc.n || !out)
+      throw HipError(RYUJIN_ERR_ARG, "postprocess_download: quantity " + std::to_string(q) + " out of range");
+    ctx->finish();
+    const size_t n = ctx->L.n_owned;
+    const double *src = (raw ? ctx->d_pp_raw.ptr : ctx->d_pp_normalised.ptr) + (size_t)q * n;
+    HIP_CHECK(hipMemcpy(out, src, n * sizeof(double), hipMemcpyDeviceToHost));
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_postprocess_bounds(ryujin_hip_ctx *ctx, int q, double *q_max, double *q_min)
+{
+  return guarded_ctx(ctx, [&]() {
+    if (!ctx->pp_computed)
+      throw HipError(RYUJIN_ERR_ARG, "postprocess_bounds before postprocess_compute");
+    if (q < 0 || q >= ctx->pp_desc.n || !q_max || !q_min)
+      throw HipError(RYUJIN_ERR_ARG, "postprocess_bounds: quantity " + std::to_string(q) + " out of range");
+    ctx->finish();
+    const double *b = reinterpret_cast<const double *>(ctx->d_pp_bounds.ptr);
+    HIP_CHECK(hipMemcpy(q_max, b + q, sizeof(double), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(q_min, b + kPostprocessMaxQuantities + q, sizeof(double), hipMemcpyDeviceToHost));
     return RYUJIN_OK;
   });
 }

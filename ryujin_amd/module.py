@@ -231,6 +231,66 @@ class HyperbolicModule:
         self._check(self._f("state_integrals")(self._ctx, state.handle, capi.as_ptr(out, capi.c_double_p)))
         return out
 
+    # ------------------------------------------------------------------ Postprocessor (device backend only)
+    def postprocess_configure(self, schlieren=("rho",), vorticity=(), beta: float = 10.0,
+                              recompute_bounds: bool = True) -> list[str]:
+        """Select the quantities of postprocess_compute(); returns their names in output order (schlieren first, as
+        Postprocessor::prepare()). A name is looked up among the Description's conserved component names first and
+        its primitive names second; an unknown one raises ValueError. A call that changes nothing keeps the
+        configuration, and with it the bounds that recompute_bounds=False holds on to."""
+        entries, names = [], []
+        for kind, prefix, wanted in ((capi.PP_SCHLIEREN, "schlieren_", schlieren),
+                                     (capi.PP_VORTICITY, "vorticity_", vorticity)):
+            for name in wanted:
+                is_primitive, index = capi.resolve_component(self.equation, self.dim, name)
+                entries.append((kind, is_primitive, index))
+                names.append(prefix + name)
+        config = (tuple(entries), float(beta), bool(recompute_bounds))
+        if getattr(self, "_pp_config", None) != config:
+            q = (capi.PostprocessQuantity * max(1, len(entries)))(*[capi.PostprocessQuantity(*e) for e in entries])
+            self._pp_config = None
+            self._check(self._f("postprocess_configure")(self._ctx, len(entries), q, float(beta),
+                                                         int(bool(recompute_bounds))))
+            self._pp_config, self._pp_names = config, names
+        return list(names)
+
+    def postprocess_reset_bounds(self) -> None:
+        """Postprocessor::reset_bounds(): with recompute_bounds=False the next compute takes its bounds afresh."""
+        if getattr(self, "_pp_config", None) is not None:
+            entries, beta, recompute_bounds = self._pp_config
+            q = (capi.PostprocessQuantity * len(entries))(*[capi.PostprocessQuantity(*e) for e in entries])
+            self._check(self._f("postprocess_configure")(self._ctx, len(entries), q, beta, int(recompute_bounds)))
+
+    def postprocess_compute(self, state: StateVector) -> None:
+        """Postprocessor::compute() on the device (asynchronous; collective over the ranks)."""
+        self._check(self._f("postprocess_compute")(self._ctx, state.handle))
+
+    def postprocess_download(self, raw: bool = False) -> dict:
+        out = {}
+        for q, name in enumerate(self._pp_names):
+            a = np.zeros(self.n_owned, dtype=np.float64)
+            self._check(self._f("postprocess_download")(self._ctx, q, capi.as_ptr(a, capi.c_double_p), int(bool(raw))))
+            out[name] = a
+        return out
+
+    def postprocess_bounds(self) -> dict:
+        """name -> (q_max, q_min) of the latest postprocess_compute(), over the owned rows of all ranks."""
+        out = {}
+        for q, name in enumerate(self._pp_names):
+            hi, lo = C.c_double(), C.c_double()
+            self._check(self._f("postprocess_bounds")(self._ctx, q, C.byref(hi), C.byref(lo)))
+            out[name] = (hi.value, lo.value)
+        return out
+
+    def postprocess(self, state: StateVector, schlieren=("rho",), vorticity=(), beta: float = 10.0,
+                    recompute_bounds: bool = True, raw: bool = False) -> dict:
+        """Schlieren and vorticity fields of a state vector (ryujin_hip_postprocess_*): name -> [n_owned] array,
+        keys as the reference names them ("schlieren_rho", "vorticity_v_1"); normalised to (-1, 1) on the
+        reference's exponential scale, or the values before the normalisation with raw=True."""
+        self.postprocess_configure(schlieren, vorticity, beta, recompute_bounds)
+        self.postprocess_compute(state)
+        return self.postprocess_download(raw)
+
     def sadd(self, dst: StateVector, s: float, b: float, src: StateVector):
         self._check(self._f("sadd")(self._ctx, dst.handle, float(s), float(b), src.handle))
 
