@@ -605,6 +605,52 @@ int ryujin_hip_postprocess_compute(ryujin_hip_ctx *ctx, int state_handle);
 int ryujin_hip_postprocess_download(ryujin_hip_ctx *ctx, int q, double *out, int raw);
 int ryujin_hip_postprocess_bounds(ryujin_hip_ctx *ctx, int q, double *q_max, double *q_min);
 
+/* ---- Quantities: point maps, space and time averages, device resident ---- */
+/* Quantities::prepare / accumulate / write_out / clear_statistics of the reference (source/quantities.template.h)
+ * on the state vector behind a handle. A MANIFOLD is a list of points of this rank: owned local indices and a
+ * positive weight per point. The library evaluates no level sets: the caller selects the points (prepare(),
+ * :111-226) and hands over the interior mass m_i (interior maps) or the boundary mass (boundary maps) as weights.
+ * Indices need not be sorted and may repeat (boundary_map() is a multimap). Manifold ids count from 0 in the order
+ * of the add_manifold calls.
+ * The value of a point is (V, V o V), V = to_primitive_state(U_i) of the context's Description (see the
+ * Postprocessor block), 2k doubles; `out` arrays are [n_points][2k] in manifold order.
+ *   accumulate      acts on every manifold with TIME_AVERAGED or SPACE_AVERAGED (:511-514). The first call after a
+ *                   clear (the reference's test: t_old == 0 && t_new == 0) only sets t_old = t - 1, t_new = t; later
+ *                   calls add, in this order per point, sum += 0.5 tau old; sum += 0.5 tau new with
+ *                   tau = t - t_old, and t_sum += tau. Every call appends one row (t, mean V, mean V o V) to the
+ *                   manifold's time series, mean x = sum_p w_p x_p / sum_p w_p over the points of ALL ranks; a
+ *                   manifold without a point on any rank gives the reference's 0/0 (NaN). Collective over the
+ *                   context's communicator. On one rank and over RCCL it is an enqueue on the context's stream: no
+ *                   host synchronisation, no copy to the host (the in-process test transport meets on the host). The
+ *                   sums are formed in a fixed order (no floating-point atomics): for a given partition the series
+ *                   is reproducible bit for bit.
+ *   instantaneous   needs INSTANTANEOUS. Without TIME_/SPACE_AVERAGED it evaluates the given state; with, it returns
+ *                   the values of the latest accumulate and fails unless t equals that call's t (:615-619).
+ *   time_averaged   out = sum * (1 / t_sum), t_begin = t_new - t_sum, t_end = t_new (:628-645); returns
+ *                   RYUJIN_Q_NONE_YET and leaves out, t_begin, t_end untouched while t_sum == 0.
+ *   time_series     rows [n_rows][1 + 2k] since the last clear; clear != 0 empties it (:663-665). The series lives on
+ *                   the device between calls; reading it is the only call that waits for the stream. rows = NULL
+ *                   with capacity_rows = 0 only reports the number of rows.
+ *   clear_statistics  t_old = t_new = t_sum = 0, sums zeroed, series emptied (:341-364).
+ *   reset           drops all manifolds (prepare()).
+ * RYUJIN_ERR_ARG: an index >= n_owned, a non-finite or non-positive weight, options zero or with unknown bits, more
+ * than RYUJIN_Q_MAX_MANIFOLDS manifolds, an unknown manifold id, NULL pointers with n_points > 0, instantaneous /
+ * time_averaged on a manifold without that option, instantaneous with a stale t, capacity_rows smaller than the
+ * number of rows (which *n_rows then reports). */
+enum { RYUJIN_Q_INSTANTANEOUS = 1, RYUJIN_Q_TIME_AVERAGED = 2, RYUJIN_Q_SPACE_AVERAGED = 4 };
+#define RYUJIN_Q_MAX_MANIFOLDS 16
+#define RYUJIN_Q_NONE_YET 3 /* time_averaged: nothing accumulated yet (distinct from RYUJIN_WARN, RYUJIN_RESTART) */
+int ryujin_hip_quantities_add_manifold(ryujin_hip_ctx *ctx, uint32_t n_points, const uint32_t *index,
+                                       const double *weight, int options, int *manifold_out);
+int ryujin_hip_quantities_reset(ryujin_hip_ctx *ctx);
+int ryujin_hip_quantities_clear_statistics(ryujin_hip_ctx *ctx);
+int ryujin_hip_quantities_accumulate(ryujin_hip_ctx *ctx, int state_handle, double t);
+int ryujin_hip_quantities_instantaneous(ryujin_hip_ctx *ctx, int manifold, int state_handle, double t, double *out);
+int ryujin_hip_quantities_time_averaged(ryujin_hip_ctx *ctx, int manifold, double *out, double *t_begin,
+                                        double *t_end);
+int ryujin_hip_quantities_time_series(ryujin_hip_ctx *ctx, int manifold, double *rows, size_t capacity_rows,
+                                      size_t *n_rows, int clear);
+
 #ifdef __cplusplus
 }
 #endif

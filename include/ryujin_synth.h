@@ -50,6 +50,9 @@ uint64_t ryujin_synth_n_global(const ryujin_synth *s);      /* sum of n_owned ov
 const double *ryujin_synth_positions(const ryujin_synth *s);   /* [n_relevant*dim] */
 const uint64_t *ryujin_synth_global_ids(const ryujin_synth *s); /* [n_relevant] lexicographic id of the node in the full grid */
 const double *ryujin_synth_bdry_positions(const ryujin_synth *s); /* [n_bdry*dim] */
+/* [n_bdry] boundary mass of every boundary_map entry (offline_data.template.h:1246-1361: the face integrals of phi_i,
+ * summed over the faces merged into the entry): the weights of the boundary maps of Quantities */
+const double *ryujin_synth_bdry_mass(const ryujin_synth *s);
 
 /* exported instance of ryujin_ghost_row_send_entries() (include/ryujin_exchange_lists.h): the ghost-row
  * send-list rule of sparse_matrix_simd.template.h:196-264, the function the generator itself calls; bound by

@@ -99,6 +99,9 @@ class SynthSpec(C.Structure):
 
 PP_SCHLIEREN, PP_VORTICITY = 0, 1
 PP_MAX_QUANTITIES = 8
+Q_INSTANTANEOUS, Q_TIME_AVERAGED, Q_SPACE_AVERAGED = 1, 2, 4
+Q_MAX_MANIFOLDS = 16
+Q_NONE_YET = 3
 
 
 class PostprocessQuantity(C.Structure):
@@ -169,6 +172,8 @@ def load_synth():
         lib.ryujin_synth_global_ids.argtypes = [C.c_void_p]
         lib.ryujin_synth_bdry_positions.restype = c_double_p
         lib.ryujin_synth_bdry_positions.argtypes = [C.c_void_p]
+        lib.ryujin_synth_bdry_mass.restype = c_double_p
+        lib.ryujin_synth_bdry_mass.argtypes = [C.c_void_p]
         lib.ryujin_synth_ghost_row_send_entries.restype = C.c_size_t
         lib.ryujin_synth_ghost_row_send_entries.argtypes = [c_u64_p, c_u32_p, c_u32_p, C.c_size_t, C.c_uint32,
                                                             C.c_uint32, c_u32_p, c_u32_p]
@@ -215,6 +220,9 @@ HIP_SYMBOLS = [
     "ryujin_hip_version", "ryujin_hip_debug_layout", "ryujin_hip_debug_pow", "ryujin_hip_debug_function", "ryujin_hip_debug_rk_outcome",
     "ryujin_hip_postprocess_configure", "ryujin_hip_postprocess_compute", "ryujin_hip_postprocess_download",
     "ryujin_hip_postprocess_bounds",
+    "ryujin_hip_quantities_add_manifold", "ryujin_hip_quantities_reset", "ryujin_hip_quantities_clear_statistics",
+    "ryujin_hip_quantities_accumulate", "ryujin_hip_quantities_instantaneous", "ryujin_hip_quantities_time_averaged",
+    "ryujin_hip_quantities_time_series",
 ]
 
 
@@ -305,5 +313,13 @@ def load_hip():
         lib.ryujin_hip_postprocess_compute.argtypes = [vp, C.c_int]
         lib.ryujin_hip_postprocess_download.argtypes = [vp, C.c_int, c_double_p, C.c_int]
         lib.ryujin_hip_postprocess_bounds.argtypes = [vp, C.c_int, c_double_p, c_double_p]
+        lib.ryujin_hip_quantities_add_manifold.argtypes = [vp, C.c_uint32, c_u32_p, c_double_p, C.c_int, c_int_p]
+        lib.ryujin_hip_quantities_reset.argtypes = [vp]
+        lib.ryujin_hip_quantities_clear_statistics.argtypes = [vp]
+        lib.ryujin_hip_quantities_accumulate.argtypes = [vp, C.c_int, C.c_double]
+        lib.ryujin_hip_quantities_instantaneous.argtypes = [vp, C.c_int, C.c_int, C.c_double, c_double_p]
+        lib.ryujin_hip_quantities_time_averaged.argtypes = [vp, C.c_int, c_double_p, c_double_p, c_double_p]
+        lib.ryujin_hip_quantities_time_series.argtypes = [vp, C.c_int, c_double_p, C.c_size_t,
+                                                          C.POINTER(C.c_size_t), C.c_int]
         _hip = lib
     return _hip

@@ -59,7 +59,7 @@ struct ryujin_synth {
   std::vector<uint32_t> columns;
   std::vector<double> cij, mij, mi, mi_inv;
   std::vector<uint32_t> b_i;
-  std::vector<double> b_normal, b_pos;
+  std::vector<double> b_normal, b_pos, b_mass;
   std::vector<uint8_t> b_id;
   std::vector<uint32_t> p_i, p_col, p_j;
   std::vector<int> nbr_rank;
@@ -577,6 +577,7 @@ bool ryujin_synth::build()
   b_normal.clear();
   b_id.clear();
   b_pos.clear();
+  b_mass.clear();
   for (const auto &it : filtered) {
     double norm = 0.;
     for (int d = 0; d < dim; ++d)
@@ -588,6 +589,7 @@ bool ryujin_synth::build()
       b_pos.push_back(positions[(size_t)it.first * dim + d]);
     }
     b_id.push_back((uint8_t)it.second.id);
+    b_mass.push_back(it.second.boundary_mass);
   }
 
   /* ---- coupling boundary pairs ------------------------------------------ */
@@ -743,6 +745,11 @@ const uint64_t *ryujin_synth_global_ids(const ryujin_synth *s)
 const double *ryujin_synth_bdry_positions(const ryujin_synth *s)
 {
   return s->b_pos.data();
+}
+
+const double *ryujin_synth_bdry_mass(const ryujin_synth *s)
+{
+  return s->b_mass.data();
 }
 
 size_t ryujin_synth_ghost_row_send_entries(const uint64_t *row_starts, const uint32_t *columns,

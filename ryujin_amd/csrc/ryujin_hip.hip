@@ -46,6 +46,7 @@
 #include "kernels_shallow_water.hpp"
 #include "scalar_conservation_device.hpp"
 #include "kernels_postprocessor.hpp"
+#include "kernels_quantities.hpp"
 
 using namespace ryujin_hip;
 
@@ -278,6 +279,8 @@ struct LocalGroup {
   std::vector<std::vector<const double *>> mail;           /* [src][dst] -> segment in src's send buffer */
   unsigned long long *slots = nullptr;                      /* device: [2][n_ranks][2] 8-byte slots */
   std::vector<double> scratch_vec;                          /* [n_ranks][8] vector sums (host) */
+  static constexpr int kQuantitiesRow = 12;                 /* >= 1 + 2 K, K <= 5 */
+  std::vector<double> scratch_quantities;                   /* [n_ranks][kQuantitiesRow] sums of a manifold (host) */
   int refs = 0;
   int device = 0;
   bool aborted = false; /* a rank failed: the others must not wait for it (guarded_ctx sets it) */
@@ -297,6 +300,7 @@ struct LocalGroup {
       , ev_reduced((size_t)n * kRing, nullptr)
       , mail(n, std::vector<const double *>(n, nullptr))
       , scratch_vec((size_t)n * 8, 0.)
+      , scratch_quantities((size_t)n * kQuantitiesRow, 0.)
       , device(dev)
   {
     HIP_CHECK(hipSetDevice(dev));
@@ -456,6 +460,34 @@ struct ryujin_hip_ctx {
   DeviceBuffer<unsigned long long> d_pp_bounds;    /* [2][kPostprocessMaxQuantities]: q_max, q_min (bit patterns) */
   template <typename E>
   void postprocess_compute(int h);
+  /* Quantities (ryujin_hip_quantities_*, kernels_quantities.hpp) */
+  struct Manifold {
+    uint32_t n_points = 0, first = 0;
+    bool contiguous = false; /* index[p] = first + p: addressed without the index stream */
+    int options = 0;
+    DeviceBuffer<uint32_t> d_index;
+    DeviceBuffer<double> d_weight;
+    DeviceBuffer<double> d_values;  /* [n_points][2 K]: (V, V o V) of the latest evaluation (val_new) */
+    DeviceBuffer<double> d_sum;     /* [n_points][2 K]: val_sum, time-averaged manifolds only */
+    DeviceBuffer<double> d_partial; /* [n_blocks + 1][1 + 2 K]: block partials, then the sums */
+    uint32_t n_blocks = 0;
+    double t_old = 0., t_new = 0., t_sum = 0.;
+    bool have_values = false; /* an accumulate since the last clear */
+    /* space_averaged_time_series: rows (t, mean V, mean V o V) in device chunks of kSeriesChunkRows rows; the host
+     * knows the row number, so appending a row is an enqueue (and, every kSeriesChunkRows calls, an allocation) */
+    std::vector<std::unique_ptr<DeviceBuffer<double>>> series;
+    size_t n_rows = 0;
+  };
+  static constexpr size_t kSeriesChunkRows = 1024;
+  std::vector<std::unique_ptr<Manifold>> manifolds;
+  Manifold &manifold(int id)
+  {
+    if (id < 0 || id >= (int)manifolds.size())
+      throw HipError(RYUJIN_ERR_ARG, "quantities: unknown manifold " + std::to_string(id));
+    return *manifolds[id];
+  }
+  template <typename E>
+  void quantities_evaluate(Manifold &m, int h, bool accumulate, double t);
   /* time-dependent Dirichlet data inside a device-resident RK step (ryujin_hip_time_step_fn): the tau of the
    * first stage is copied to the host as soon as it exists (behind step 3 of the first stage), the later stages'
    * boundary data is evaluated at t + c_s tau while the rest of the first stage runs */
@@ -2197,6 +2229,97 @@ void ryujin_hip_ctx::postprocess_compute(int h)
   pp_computed = true;
 }
 
+/* internal_accumulate() of one manifold on state h. accumulate: the trapezoid update, the weighted sums over all
+ * ranks and one row of the time series as well (Quantities::accumulate, :516-549); otherwise only the values
+ * (write_out of an "instantaneous" manifold that is not averaged, :615-617). */
+template <typename E>
+void ryujin_hip_ctx::quantities_evaluate(Manifold &m, int h, bool accumulate, double t)
+{
+  constexpr int NQ = 1 + 2 * E::K;
+  static_assert(NQ <= LocalGroup::kQuantitiesRow, "LocalGroup::scratch_quantities holds a row per rank");
+  State &s = state(h);
+  const bool time_averaged = (m.options & RYUJIN_Q_TIME_AVERAGED) != 0;
+
+  QuantitiesSweep S{};
+  S.n_points = m.n_points;
+  S.first = m.first;
+  S.index = m.d_index.ptr;
+  S.weight = m.d_weight.ptr;
+  S.store = m.d_values.n != 0;
+  S.values = m.d_values.ptr;
+  S.sum = m.d_sum.ptr;
+  S.partial = m.d_partial.ptr;
+  S.reduce = accumulate;
+
+  if (accumulate) {
+    std::swap(m.t_old, m.t_new); /* (:519; the values are not swapped: one array, updated behind the sum) */
+    if (m.t_old == 0. && m.t_new == 0.) {
+      /* We have not accumulated any statistics yet (:529-532) */
+      m.t_old = t - 1.;
+      m.t_new = t;
+    } else {
+      m.t_new = t;
+      const double tau = m.t_new - m.t_old;
+      S.add = time_averaged;
+      S.half_tau = 0.5 * tau;
+      m.t_sum += tau;
+    }
+  }
+
+  if (m.n_points > 0) { /* (no zero-sized grid) */
+    if (m.contiguous)
+      hipLaunchKernelGGL((k_quantities_sweep<E, false>), dim3(m.n_blocks), dim3(kBlock), 0, stream, eq_params<E>(), S,
+                         s.U.ptr);
+    else
+      hipLaunchKernelGGL((k_quantities_sweep<E, true>), dim3(m.n_blocks), dim3(kBlock), 0, stream, eq_params<E>(), S,
+                         s.U.ptr);
+    HIP_CHECK(hipGetLastError());
+  }
+  m.have_values = true;
+  if (!accumulate)
+    return;
+
+  /* one row of the time series (:549) */
+  const size_t chunk = m.n_rows / kSeriesChunkRows;
+  if (chunk >= m.series.size()) {
+    m.series.emplace_back(new DeviceBuffer<double>());
+    m.series.back()->alloc(kSeriesChunkRows * NQ, false);
+  }
+  double *row = m.series[chunk]->ptr + (m.n_rows % kSeriesChunkRows) * NQ;
+  double *sums = m.d_partial.ptr + (size_t)m.n_blocks * NQ;
+  const bool several_ranks = comm && comm->n_ranks > 1 && !(comm->local && comm->local->loopback);
+  hipLaunchKernelGGL(k_quantities_final<NQ>, dim3(1), dim3(64), 0, stream, m.n_points > 0 ? m.n_blocks : 0u,
+                     m.d_partial.ptr, t, sums, several_ranks ? nullptr : row);
+  HIP_CHECK(hipGetLastError());
+  if (several_ranks) {
+    if (!comm->local) {
+      ++n_allreduces;
+      NCCL_CHECK(ncclAllReduce(sums, sums, NQ, ncclDouble, ncclSum, comm->comm, stream));
+    } else {
+      /* in-process transport: host rendezvous, as ryujin_hip_state_integrals; the ranks in order on every rank */
+      LocalGroup &g = *comm->local;
+      double host[NQ];
+      HIP_CHECK(hipMemcpyAsync(host, sums, sizeof(host), hipMemcpyDeviceToHost, stream));
+      HIP_CHECK(hipStreamSynchronize(stream));
+      for (int q = 0; q < NQ; ++q)
+        g.scratch_quantities[(size_t)comm->rank * LocalGroup::kQuantitiesRow + q] = host[q];
+      g.barrier();
+      for (int q = 0; q < NQ; ++q) {
+        double v = 0.;
+        for (int r = 0; r < g.n_ranks; ++r)
+          v += g.scratch_quantities[(size_t)r * LocalGroup::kQuantitiesRow + q];
+        host[q] = v;
+      }
+      g.barrier();
+      HIP_CHECK(hipMemcpyAsync(sums, host, sizeof(host), hipMemcpyHostToDevice, stream));
+      HIP_CHECK(hipStreamSynchronize(stream)); /* host[] goes out of scope */
+    }
+    hipLaunchKernelGGL(k_quantities_row<NQ>, dim3(1), dim3(64), 0, stream, sums, t, row);
+    HIP_CHECK(hipGetLastError());
+  }
+  ++m.n_rows;
+}
+
 /* ============================================================================ C ABI */
 
 namespace
@@ -3436,6 +3559,181 @@ int ryujin_hip_postprocess_bounds(ryujin_hip_ctx *ctx, int q, double *q_max, dou
     const double *b = reinterpret_cast<const double *>(ctx->d_pp_bounds.ptr);
     HIP_CHECK(hipMemcpy(q_max, b + q, sizeof(double), hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(q_min, b + kPostprocessMaxQuantities + q, sizeof(double), hipMemcpyDeviceToHost));
+    return RYUJIN_OK;
+  });
+}
+
+/* ---- Quantities ---------------------------------------------------------- */
+
+int ryujin_hip_quantities_add_manifold(ryujin_hip_ctx *ctx, uint32_t n_points, const uint32_t *index,
+                                       const double *weight, int options, int *manifold_out)
+{
+  return guarded_ctx(ctx, [&]() {
+    constexpr int known = RYUJIN_Q_INSTANTANEOUS | RYUJIN_Q_TIME_AVERAGED | RYUJIN_Q_SPACE_AVERAGED;
+    if (!manifold_out)
+      throw HipError(RYUJIN_ERR_ARG, "quantities_add_manifold: null argument");
+    if (options == 0 || (options & ~known) != 0)
+      throw HipError(RYUJIN_ERR_ARG, "quantities_add_manifold: options " + std::to_string(options) +
+                                         " are not a combination of RYUJIN_Q_INSTANTANEOUS, _TIME_AVERAGED, "
+                                         "_SPACE_AVERAGED");
+    if (ctx->manifolds.size() >= RYUJIN_Q_MAX_MANIFOLDS)
+      throw HipError(RYUJIN_ERR_ARG, "quantities_add_manifold: more than RYUJIN_Q_MAX_MANIFOLDS = " +
+                                         std::to_string(RYUJIN_Q_MAX_MANIFOLDS) + " manifolds");
+    if (n_points > 0 && (!index || !weight))
+      throw HipError(RYUJIN_ERR_ARG, "quantities_add_manifold: null index or weight with n_points > 0");
+    bool contiguous = n_points > 0;
+    for (uint32_t p = 0; p < n_points; ++p) {
+      if (index[p] >= ctx->L.n_owned)
+        throw HipError(RYUJIN_ERR_ARG, "quantities_add_manifold: index " + std::to_string(index[p]) + " of point " +
+                                           std::to_string(p) + " is not an owned row (n_owned = " +
+                                           std::to_string(ctx->L.n_owned) + ")");
+      if (!std::isfinite(weight[p]) || !(weight[p] > 0.))
+        throw HipError(RYUJIN_ERR_ARG, "quantities_add_manifold: weight of point " + std::to_string(p) +
+                                           " is not a positive finite number");
+      contiguous = contiguous && index[p] == index[0] + p;
+    }
+    auto m = std::make_unique<ryujin_hip_ctx::Manifold>();
+    m->n_points = n_points;
+    m->options = options;
+    m->contiguous = contiguous;
+    m->first = contiguous ? index[0] : 0u;
+    const size_t width = 2 * (size_t)ctx->K;
+    m->n_blocks = (uint32_t)std::min<size_t>(kQuantitiesMaxBlocks, ((size_t)n_points + kBlock - 1) / kBlock);
+    if (n_points > 0) {
+      if (!contiguous)
+        m->d_index.upload(index, n_points);
+      m->d_weight.upload(weight, n_points);
+      /* the values are kept where something reads them later: the trapezoid rule and "instantaneous" */
+      if (options & (RYUJIN_Q_TIME_AVERAGED | RYUJIN_Q_INSTANTANEOUS))
+        m->d_values.alloc(n_points * width);
+      if (options & RYUJIN_Q_TIME_AVERAGED)
+        m->d_sum.alloc(n_points * width);
+    }
+    m->d_partial.alloc(((size_t)m->n_blocks + 1) * (1 + width));
+    *manifold_out = (int)ctx->manifolds.size();
+    ctx->manifolds.push_back(std::move(m));
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_quantities_reset(ryujin_hip_ctx *ctx)
+{
+  return guarded_ctx(ctx, [&]() {
+    ctx->finish(); /* the buffers may be in use */
+    ctx->manifolds.clear();
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_quantities_clear_statistics(ryujin_hip_ctx *ctx)
+{
+  return guarded_ctx(ctx, [&]() {
+    for (auto &m : ctx->manifolds) {
+      m->t_old = m->t_new = m->t_sum = 0.;
+      m->have_values = false;
+      m->n_rows = 0;
+      if (m->d_sum.n)
+        HIP_CHECK(hipMemsetAsync(m->d_sum.ptr, 0, m->d_sum.n * sizeof(double), ctx->stream));
+    }
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_quantities_accumulate(ryujin_hip_ctx *ctx, int state_handle, double t)
+{
+  return guarded_ctx(ctx, [&]() {
+    (void)ctx->state(state_handle);
+    /* RCCL orders the operations of a communicator in issue order whatever stream they are on (allreduce_scalar) */
+    ctx->wait_comm();
+    for (auto &m : ctx->manifolds) {
+      if (!(m->options & (RYUJIN_Q_TIME_AVERAGED | RYUJIN_Q_SPACE_AVERAGED)))
+        continue; /* (:511-514) */
+      dispatch_equation(ctx->params.equation, ctx->dim, [&](auto tag) {
+        ctx->template quantities_evaluate<typename decltype(tag)::type>(*m, state_handle, true, t);
+        return 0;
+      });
+    }
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_quantities_instantaneous(ryujin_hip_ctx *ctx, int manifold, int state_handle, double t, double *out)
+{
+  return guarded_ctx(ctx, [&]() {
+    auto &m = ctx->manifold(manifold);
+    if (!(m.options & RYUJIN_Q_INSTANTANEOUS))
+      throw HipError(RYUJIN_ERR_ARG, "quantities_instantaneous: manifold " + std::to_string(manifold) +
+                                         " was added without RYUJIN_Q_INSTANTANEOUS");
+    if (m.n_points > 0 && !out)
+      throw HipError(RYUJIN_ERR_ARG, "quantities_instantaneous: null argument");
+    if (m.options & (RYUJIN_Q_TIME_AVERAGED | RYUJIN_Q_SPACE_AVERAGED)) {
+      /* AssertThrow(t_new == t) (:619) */
+      if (!m.have_values || m.t_new != t)
+        throw HipError(RYUJIN_ERR_ARG, "quantities_instantaneous: the latest accumulate of manifold " +
+                                           std::to_string(manifold) + " is not one at t = " + std::to_string(t));
+    } else {
+      (void)ctx->state(state_handle);
+      ctx->wait_comm();
+      dispatch_equation(ctx->params.equation, ctx->dim, [&](auto tag) {
+        ctx->template quantities_evaluate<typename decltype(tag)::type>(m, state_handle, false, t);
+        return 0;
+      });
+    }
+    if (m.n_points > 0) {
+      HIP_CHECK(hipStreamSynchronize(ctx->stream));
+      HIP_CHECK(hipMemcpy(out, m.d_values.ptr, m.d_values.n * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_quantities_time_averaged(ryujin_hip_ctx *ctx, int manifold, double *out, double *t_begin,
+                                        double *t_end)
+{
+  return guarded_ctx(ctx, [&]() {
+    auto &m = ctx->manifold(manifold);
+    if (!(m.options & RYUJIN_Q_TIME_AVERAGED))
+      throw HipError(RYUJIN_ERR_ARG, "quantities_time_averaged: manifold " + std::to_string(manifold) +
+                                         " was added without RYUJIN_Q_TIME_AVERAGED");
+    if ((m.n_points > 0 && !out) || !t_begin || !t_end)
+      throw HipError(RYUJIN_ERR_ARG, "quantities_time_averaged: null argument");
+    if (m.t_sum == 0.)
+      return (int)RYUJIN_Q_NONE_YET; /* (:636) */
+    *t_begin = m.t_new - m.t_sum;
+    *t_end = m.t_new;
+    if (m.n_points > 0) {
+      HIP_CHECK(hipStreamSynchronize(ctx->stream));
+      HIP_CHECK(hipMemcpy(out, m.d_sum.ptr, m.d_sum.n * sizeof(double), hipMemcpyDeviceToHost));
+      const double scale = 1. / m.t_sum; /* (:643): the reference multiplies by the reciprocal */
+      for (size_t e = 0; e < m.d_sum.n; ++e)
+        out[e] = scale * out[e];
+    }
+    return (int)RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_quantities_time_series(ryujin_hip_ctx *ctx, int manifold, double *rows, size_t capacity_rows,
+                                      size_t *n_rows, int clear)
+{
+  return guarded_ctx(ctx, [&]() {
+    auto &m = ctx->manifold(manifold);
+    if (!n_rows)
+      throw HipError(RYUJIN_ERR_ARG, "quantities_time_series: null argument");
+    *n_rows = m.n_rows;
+    if (!rows && capacity_rows == 0)
+      return RYUJIN_OK; /* a query for the number of rows */
+    if (capacity_rows < m.n_rows || (m.n_rows > 0 && !rows))
+      throw HipError(RYUJIN_ERR_ARG, "quantities_time_series: " + std::to_string(m.n_rows) +
+                                         " rows do not fit a capacity of " + std::to_string(capacity_rows));
+    const size_t width = 1 + 2 * (size_t)ctx->K;
+    if (m.n_rows > 0)
+      HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (size_t r = 0, c = 0; r < m.n_rows; r += ryujin_hip_ctx::kSeriesChunkRows, ++c) {
+      const size_t n = std::min(ryujin_hip_ctx::kSeriesChunkRows, m.n_rows - r);
+      HIP_CHECK(hipMemcpy(rows + r * width, m.series[c]->ptr, n * width * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    if (clear)
+      m.n_rows = 0; /* series.clear() (:665) */
     return RYUJIN_OK;
   });
 }

@@ -291,6 +291,56 @@ class HyperbolicModule:
         self.postprocess_compute(state)
         return self.postprocess_download(raw)
 
+    # ------------------------------------------------------------------ Quantities (device backend only)
+    def quantities_add_manifold(self, index, weight, options: int) -> int:
+        """A point map of this rank (ryujin_hip_quantities_add_manifold): owned local indices, a positive weight per
+        point (interior mass or boundary mass), options a combination of capi.Q_*; returns the manifold id."""
+        index = np.ascontiguousarray(index, dtype=np.uint32).reshape(-1)
+        weight = np.ascontiguousarray(weight, dtype=np.float64).reshape(-1)
+        assert index.size == weight.size
+        out = C.c_int(-1)
+        self._check(self._f("quantities_add_manifold")(
+            self._ctx, index.size, capi.as_ptr(index, capi.c_u32_p) if index.size else None,
+            capi.as_ptr(weight, capi.c_double_p) if index.size else None, int(options), C.byref(out)))
+        self._q_points = getattr(self, "_q_points", {})
+        self._q_points[out.value] = index.size
+        return out.value
+
+    def quantities_reset(self) -> None:
+        self._check(self._f("quantities_reset")(self._ctx))
+        self._q_points = {}
+
+    def quantities_clear_statistics(self) -> None:
+        self._check(self._f("quantities_clear_statistics")(self._ctx))
+
+    def quantities_accumulate(self, state: StateVector, t: float) -> None:
+        """Quantities::accumulate() on the device: an enqueue (collective over the ranks)."""
+        self._check(self._f("quantities_accumulate")(self._ctx, state.handle, float(t)))
+
+    def quantities_instantaneous(self, manifold: int, state: StateVector, t: float) -> np.ndarray:
+        """[n_points, 2k]: (V, V o V) per point, V the primitive state"""
+        out = np.zeros((self._q_points[manifold], 2 * self.k), dtype=np.float64)
+        self._check(self._f("quantities_instantaneous")(self._ctx, manifold, state.handle, float(t),
+                                                        capi.as_ptr(out, capi.c_double_p)))
+        return out
+
+    def quantities_time_averaged(self, manifold: int):
+        """(values [n_points, 2k], t_begin, t_end), or None while nothing has been accumulated"""
+        out = np.zeros((self._q_points[manifold], 2 * self.k), dtype=np.float64)
+        t0, t1 = C.c_double(), C.c_double()
+        rc = self._check(self._f("quantities_time_averaged")(self._ctx, manifold, capi.as_ptr(out, capi.c_double_p),
+                                                             C.byref(t0), C.byref(t1)))
+        return None if rc == capi.Q_NONE_YET else (out, t0.value, t1.value)
+
+    def quantities_time_series(self, manifold: int, clear: bool = False) -> np.ndarray:
+        """[n_rows, 1 + 2k]: (t, mean V, mean V o V) of every accumulate since the last clear"""
+        n = C.c_size_t(0)
+        fn = self._f("quantities_time_series")
+        self._check(fn(self._ctx, manifold, None, 0, C.byref(n), 0))  # rows = NULL, capacity 0: the number of rows
+        rows = np.zeros((n.value, 1 + 2 * self.k), dtype=np.float64)
+        self._check(fn(self._ctx, manifold, capi.as_ptr(rows, capi.c_double_p), n.value, C.byref(n), int(bool(clear))))
+        return rows
+
     def sadd(self, dst: StateVector, s: float, b: float, src: StateVector):
         self._check(self._f("sadd")(self._ctx, dst.handle, float(s), float(b), src.handle))
 

@@ -164,6 +164,11 @@ class SyntheticOffline(_OfflineArrays):
         return self._arr(self._lib.ryujin_synth_bdry_positions(self._h), self.n_bdry * self.dim,
                          np.float64).reshape(-1, self.dim)
 
+    @property
+    def b_mass(self):
+        """boundary mass of every boundary_map entry [n_bdry]: the weights of the boundary maps of Quantities"""
+        return self._arr(self._lib.ryujin_synth_bdry_mass(self._h), self.n_bdry, np.float64)
+
 
 class ImportedOffline(_OfflineArrays):
     """An OfflineData dump read from disk: the same object as SyntheticOffline as far
