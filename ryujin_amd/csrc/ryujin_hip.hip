@@ -39,6 +39,7 @@
 #endif
 
 #include "host_layout.hpp"
+#include "step_plan.hpp"
 #include "kernels_euler.hpp"
 #include "kernels_limiter.hpp"
 #include "kernels_limiter_stage0.hpp"
@@ -251,6 +252,23 @@ namespace
     else
       launch(std::integral_constant<int, 1>{});
   }
+
+  /* a run-time bool as a template argument: launch(std::true_type{}) or launch(std::false_type{}) */
+  template <typename F>
+  void with_bool(const bool value, F &&launch)
+  {
+    if (value)
+      launch(std::true_type{});
+    else
+      launch(std::false_type{});
+  }
+
+  template <typename E> constexpr bool is_euler_v = std::is_same<typename E::Params, EulerParams>::value;
+  template <typename E> constexpr bool is_aeos_v = std::is_same<typename E::Params, EulerAeosParams>::value;
+  template <typename E> constexpr bool is_scalar_v = std::is_same<typename E::Params, ScalarParams>::value;
+  template <typename E> constexpr bool is_sw_v = std::is_same<typename E::Params, ShallowWaterParams>::value;
+
+  static_assert(kPlanWavesPerBlock == (uint32_t)kWavesPerBlock, "step_plan.hpp counts the waves of a block");
 } // namespace
 
 /* In-process transport (test facility): several contexts of ONE process, each driven by its own host
@@ -515,13 +533,11 @@ struct ryujin_hip_ctx {
   DeviceBuffer<uint32_t> d_send_idx, d_row_send_pos;
   DeviceBuffer<double> d_send_buf;
 
-  /* step 5 of the running step left V_i = U_i^low + sum_j lambda P_ij (k_lij_stage0, k_pij_lij): step 6 may take it */
+  /* V_i = U_i^low + sum_j lambda P_ij, where step 5 leaves it (StepPlan::has_V): step 6 may take it */
   DeviceBuffer<double> d_V;
-  bool stage0_V = false;
-  /* the last step stored P_ij per slice (per_slice below): ryujin_hip_debug_fetch forms it from these operands for
-   * the slices the sweeps left out */
-  bool last_per_slice = false;
-  bool last_tile_store = false; /* the last step stored P_ij per tile (plain kernels): debug_fetch forms the rest */
+  /* what the latest update ran (step_plan.hpp). Where it stored P_ij per slice or per tile, ryujin_hip_debug_fetch
+   * forms the rest from the operands in last_s0 */
+  StepPlan last_plan{};
   Stage0Src last_s0{};
   /* SliceFlags (kernels_limiter.hpp), [n_slices] each; `unlimited` starts at 0 = "limited": the first update of a
    * context stores P_ij everywhere */
@@ -549,13 +565,13 @@ struct ryujin_hip_ctx {
     seen_sampled_stored = h_scalars->n_sampled_stored;
     if (d_slices != 0) {
       limited_fraction = (double)d_limited / (double)d_slices;
-      stored_fraction = last_per_slice ? (double)d_stored / (double)d_slices : 1.;
+      stored_fraction = last_plan.per_slice() ? (double)d_stored / (double)d_slices : 1.;
     }
     const unsigned int d_needed = h_scalars->n_sampled_tiles_needed - seen_sampled_tiles_needed;
     const unsigned int d_formed = h_scalars->n_sampled_tiles_formed - seen_sampled_tiles_formed;
     seen_sampled_tiles_needed = h_scalars->n_sampled_tiles_needed;
     seen_sampled_tiles_formed = h_scalars->n_sampled_tiles_formed;
-    if (last_tile_store && d_tiles != 0) { /* (of the tiles, by step 5; step 6 adds the few it has to form itself) */
+    if (last_plan.per_tile() && d_tiles != 0) { /* (of the tiles, by step 5; step 6 adds the few it has to form itself) */
       stored_fraction = (double)d_tiles_stored / (double)d_tiles;
       tiles_needed_fraction = (double)d_needed / (double)d_tiles;
       tiles_formed_fraction = (double)d_formed / (double)d_tiles;
@@ -574,7 +590,6 @@ struct ryujin_hip_ctx {
 
   /* profiling */
   bool timers_enabled = false;
-  bool step2_split = false; /* step 2 ran as indicator kernel + Riemann kernel (event 8 recorded in between) */
   /* device-resident RK driver: per-step host synchronisation is deferred to the end of the RK step */
   bool deferred = false;
   int rk_stage = 0; /* selects the event set while deferred */
@@ -653,6 +668,32 @@ struct ryujin_hip_ctx {
   template <typename E>
   int step(int h_old, int stages, const int *h_stage, const double *w, int h_new, double tau_in,
            double tau_max_in, double *tau_out);
+  /* ... and its stages: each launches what the plan names */
+  template <int DIM>
+  struct StepArgs {
+    State &old, &nw;
+    StageArgs<DIM> S{};
+    double weight = 1.;
+    SliceFlags slice_flags{}, tile_flags{};
+    FusedSadd fused_sadd{0., 0., nullptr}; /* applied by the last sweep */
+    FusedPrecompute fused_prec{nullptr, nullptr};
+  };
+  template <typename E>
+  StepPlanInput plan_input(int stages) const;
+  template <typename E>
+  void step2_dij_alpha(const StepPlan &plan, const State &old);
+  template <typename E>
+  void step3_diagonal_tau(const StepPlan &plan, const State &old);
+  void ensure_limiter_buffers(const StepPlan &plan);
+  template <typename E>
+  void step4_low_order(const StepPlan &plan, const StepArgs<E::DIMENSION> &a);
+  template <typename E>
+  void step5_limiter(const StepPlan &plan, const StepArgs<E::DIMENSION> &a);
+  template <typename E>
+  void step6_high_order_next(const StepPlan &plan, const StepArgs<E::DIMENSION> &a);
+  template <typename E>
+  void step7_high_order_last(const StepPlan &plan, const StepArgs<E::DIMENSION> &a);
+  int finish_step(double *tau_out);
   template <typename E>
   int time_step(int scheme, int h_state, int n_tmp, const int *h_tmp, const double *dirichlet,
                 double tau_max, int cfl_recovery, double cfl_min, double cfl_max, double *tau_out,
@@ -1243,7 +1284,7 @@ void ryujin_hip_ctx::store_pij_for_debug()
   mm.slice_end = L.n_slices;
   const dim3 grid((L.n_slices + kWavesPerBlock - 1) / kWavesPerBlock), block(kBlock);
   hipLaunchKernelGGL(k_pij_stage0_store<E>, grid, block, 0, stream, mm, last_s0, d_pij.ptr,
-                     last_per_slice ? (const uint8_t *)d_slice_first_stored.ptr : (const uint8_t *)nullptr);
+                     last_plan.per_slice() ? (const uint8_t *)d_slice_first_stored.ptr : (const uint8_t *)nullptr);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(stream));
 }
@@ -1387,94 +1428,79 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet)
   HIP_CHECK(hipGetLastError());
 }
 
+/* what step_plan.hpp decides from (plan_step): everything of the context that selects a kernel */
 template <typename E>
-int ryujin_hip_ctx::step(int h_old, int stages, const int *h_stage, const double *w, int h_new,
-                         double tau_in, double tau_max_in, double *tau_out)
+StepPlanInput ryujin_hip_ctx::plan_input(const int stages) const
+{
+  StepPlanInput in;
+  in.equation = is_euler_v<E> ? PlanEquation::euler
+                              : (is_aeos_v<E> ? PlanEquation::euler_aeos
+                                              : (is_scalar_v<E> ? PlanEquation::scalar : PlanEquation::shallow_water));
+  in.dim = E::DIMENSION;
+  in.fusable_precompute = E::kFusablePrecompute;
+  in.stages = stages;
+  in.limiter_iterations = params.limiter_iterations;
+  in.dg = dg;
+  in.max_row_len = L.max_row_len;
+  in.n_slices = L.n_slices;
+  in.debug_pij_storage = params.debug_pij_storage;
+  in.checked = params.debug_expensive_bounds_check != 0;
+  in.limited_fraction = limited_fraction;
+  in.per_slice_max_limited = (double)RYUJIN_PER_SLICE_MAX_LIMITED;
+  in.resident_waves_step5 = resident_waves_step5;
+  in.resident_waves_step6 = resident_waves_step6;
+  in.bc_fold_max_slices = bc_fold_max_slices;
+  in.pending_precompute = pending_precompute;
+  in.riemann_newton_max_iterations = eparams.riemann_newton_max_iterations;
+  in.rarefaction_power = eparams.rarefaction_power;
+  in.friction = swparams.manning != 0.;
+  return in;
+}
+
+/* Step 2: d_ij (upper triangle), alpha_i; ghost alpha (:341-424) */
+template <typename E>
+void ryujin_hip_ctx::step2_dij_alpha(const StepPlan &plan, const State &old)
 {
   constexpr int DIM = E::DIMENSION;
-  constexpr bool is_euler = std::is_same<typename E::Params, EulerParams>::value;
-  constexpr bool is_aeos = std::is_same<typename E::Params, EulerAeosParams>::value;
-  constexpr bool is_scalar = std::is_same<typename E::Params, ScalarParams>::value;
-  constexpr bool is_sw = std::is_same<typename E::Params, ShallowWaterParams>::value;
   const auto &eparams = eq_params<E>(); /* shadows the member: the equation's parameter block */
-  State &old = state(h_old);
-  State &nw = state(h_new);
-  if (h_old == h_new)
-    throw HipError(RYUJIN_ERR_ARG, "old and new state vector must differ");
-  nw.precomputed = false; /* rewritten below */
-
   const dim3 block(kBlock);
-
-  /* scalars: tau_max := tau_max_in, flags := 0 -- carried by the first sweep of step 2 (step_begin) */
-  const bool use_device_tau = deferred && rk_stage > 0;
-  struct ClearBegin { /* a step that throws before its first sweep must not leave it armed */
-    StepBegin &b;
-    ~ClearBegin() { b = StepBegin{}; }
-  } clear_begin{pending_begin};
-  pending_begin = StepBegin{d_scalars.ptr,
-                            tau_max_in,
-                            tau_in,
-                            (!deferred || rk_stage == 0) ? 1 : 0,
-                            (deferred && rk_stage > 0) ? rk_stage - 1 : -1,
-                            use_device_tau ? 1 : 0,
-                            deferred ? rk_stage : 0};
-
-  bool euler_fast_riemann = false;
-  if constexpr (is_euler)
-    euler_fast_riemann = eparams.riemann_newton_max_iterations == 0 && eparams.rarefaction_power > 0;
-  mark(0);
-  step2_split = false;
-  /* Step 2: d_ij (upper triangle), alpha_i; ghost alpha (:341-424) */
-  if constexpr (is_aeos) {
-    if (L.max_row_len > 32)
-      throw HipError(RYUJIN_ERR_UNSUPPORTED, "euler aeos: stencils of more than 32 entries");
+  if constexpr (is_aeos_v<E>) {
     sweep([&](const DeviceMesh &mm, dim3 grid) {
       hipLaunchKernelGGL(k_alpha_aeos<DIM>, grid, block, 0, launch_stream, eparams, mm, old.U.ptr, old.prec.ptr,
                          d_alpha.ptr);
     });
     mark(8);
-    step2_split = true;
     exchange_vector(d_alpha.ptr, 1, true);
     sweep([&](const DeviceMesh &mm, dim3 grid) {
       hipLaunchKernelGGL(k_dij_aeos<DIM>, grid, block, 0, launch_stream, eparams, mm, d_lower_mask.ptr,
                          old.rrec.ptr, d_dij.ptr);
     });
-  } else if constexpr (is_scalar) {
+  } else if constexpr (is_scalar_v<E>) {
     sweep([&](const DeviceMesh &mm, dim3 grid) {
       hipLaunchKernelGGL(k_dij_alpha_sc<DIM>, grid, block, 0, launch_stream, eparams, mm, old.U.ptr,
                          old.prec.ptr, d_dij.ptr, d_alpha.ptr);
     });
     mark(8);
-    step2_split = true;
     exchange_vector(d_alpha.ptr, 1, true);
-  } else if (((is_euler && euler_fast_riemann) || is_sw) && L.max_row_len <= 32) {
-    /* (Euler's general Riemann path -- Newton iterations or a non-integral exponent -- holds twice the
-     * registers and keeps the two-kernel form below) */
-    if constexpr (is_euler || is_sw) {
-      sweep([&](const DeviceMesh &mm, dim3 grid) {
-        hipLaunchKernelGGL((k_dij_alpha_records<E, false>), grid, block, 0, launch_stream, eparams, mm,
-                           old.U.ptr, old.prec.ptr, old.rrec.ptr, d_dij.ptr, d_alpha.ptr);
-      });
-      exchange_vector(d_alpha.ptr, 1, true);
-    }
-  } else if (is_euler && L.max_row_len <= 32) {
-    /* Euler with the general Riemann path: the indicator sweep and the Riemann sweep as two kernels */
+  } else if (plan.step2 == StepPlan::Step2::records) {
+    sweep([&](const DeviceMesh &mm, dim3 grid) {
+      hipLaunchKernelGGL((k_dij_alpha_records<E, false>), grid, block, 0, launch_stream, eparams, mm,
+                         old.U.ptr, old.prec.ptr, old.rrec.ptr, d_dij.ptr, d_alpha.ptr);
+    });
+    exchange_vector(d_alpha.ptr, 1, true);
+  } else if (plan.step2 == StepPlan::Step2::alpha_then_dij) {
     sweep([&](const DeviceMesh &mm, dim3 grid) {
       hipLaunchKernelGGL(k_alpha<E>, grid, block, 0, launch_stream, eparams, mm, old.U.ptr, old.prec.ptr,
                          d_alpha.ptr);
     });
     mark(8); /* end of the indicator kernel: sweep_ms[0] = k_alpha alone */
-    step2_split = true;
     exchange_vector(d_alpha.ptr, 1, true); /* overlaps with the Riemann sweep as well */
     sweep([&](const DeviceMesh &mm, dim3 grid) {
-      if constexpr (is_euler) {
-        if (eparams.riemann_newton_max_iterations == 0 && eparams.rarefaction_power > 0)
-          hipLaunchKernelGGL((k_dij_records<E, false>), grid, block, 0, launch_stream, eparams, mm,
+      if constexpr (is_euler_v<E>)
+        with_bool(!plan.fast_riemann, [&](auto newton) {
+          hipLaunchKernelGGL((k_dij_records<E, decltype(newton)::value>), grid, block, 0, launch_stream, eparams, mm,
                              d_lower_mask.ptr, old.rrec.ptr, d_dij.ptr);
-        else
-          hipLaunchKernelGGL((k_dij_records<E, true>), grid, block, 0, launch_stream, eparams, mm,
-                             d_lower_mask.ptr, old.rrec.ptr, d_dij.ptr);
-      }
+        });
     });
   } else {
     sweep([&](const DeviceMesh &mm, dim3 grid) {
@@ -1483,16 +1509,22 @@ int ryujin_hip_ctx::step(int h_old, int stages, const int *h_stage, const double
     });
     exchange_vector(d_alpha.ptr, 1, true);
   }
-  mark(1);
+}
 
-  /* Step 3: boundary d_ij, symmetrise, diagonal, tau_max (:432-578) */
+/* Step 3: boundary d_ij, symmetrise, diagonal, tau_max (:432-578) */
+template <typename E>
+void ryujin_hip_ctx::step3_diagonal_tau(const StepPlan &plan, const State &old)
+{
+  constexpr int DIM = E::DIMENSION;
+  const auto &eparams = eq_params<E>();
+  const dim3 block(kBlock);
   if (n_pairs) {
     join_export(); /* boundary pairs may sit in export rows, whose d_ij the export part wrote on comm_stream
                     * (and may point to ghost columns: the U exchange precedes that export part in stream order) */
-    if constexpr (is_aeos)
+    if constexpr (is_aeos_v<E>)
       hipLaunchKernelGGL(k_dij_boundary_aeos<DIM>, dim3(grid_for(n_pairs)), block, 0, stream, eparams,
                          n_pairs, d_p_i.ptr, d_p_j.ptr, d_p_pos.ptr, d_p_cji.ptr, old.rrec.ptr, d_dij.ptr);
-    else if constexpr (is_scalar)
+    else if constexpr (is_scalar_v<E>)
       hipLaunchKernelGGL(k_dij_boundary_sc<DIM>, dim3(grid_for(n_pairs)), block, 0, stream, eparams,
                          n_pairs, d_p_i.ptr, d_p_j.ptr, d_p_pos.ptr, d_p_cji.ptr, old.U.ptr,
                          old.prec.ptr, d_dij.ptr);
@@ -1501,15 +1533,16 @@ int ryujin_hip_ctx::step(int h_old, int stages, const int *h_stage, const double
                          n_pairs, d_p_i.ptr, d_p_j.ptr, d_p_pos.ptr, d_p_cji.ptr, old.U.ptr, d_dij.ptr);
   }
   sweep([&](const DeviceMesh &mm, dim3 grid) {
-    if (L.max_row_len <= 3)
-      hipLaunchKernelGGL(k_dij_diag_unrolled<3>, grid, block, 0, launch_stream, mm, d_lower_mask.ptr,
-                         params.cfl, d_dij.ptr, d_scalars.ptr);
-    else if (L.max_row_len <= 9)
-      hipLaunchKernelGGL(k_dij_diag_unrolled<9>, grid, block, 0, launch_stream, mm, d_lower_mask.ptr,
-                         params.cfl, d_dij.ptr, d_scalars.ptr);
-    else if (L.max_row_len <= 27)
-      hipLaunchKernelGGL(k_dij_diag_unrolled<27>, grid, block, 0, launch_stream, mm, d_lower_mask.ptr,
-                         params.cfl, d_dij.ptr, d_scalars.ptr);
+    auto unrolled = [&](auto width) {
+      hipLaunchKernelGGL(k_dij_diag_unrolled<decltype(width)::value>, grid, block, 0, launch_stream, mm,
+                         d_lower_mask.ptr, params.cfl, d_dij.ptr, d_scalars.ptr);
+    };
+    if (plan.diag_width == 3)
+      unrolled(std::integral_constant<int, 3>{});
+    else if (plan.diag_width == 9)
+      unrolled(std::integral_constant<int, 9>{});
+    else if (plan.diag_width == 27)
+      unrolled(std::integral_constant<int, 27>{});
     else
       hipLaunchKernelGGL(k_dij_diag, grid, block, 0, launch_stream, mm, params.cfl, d_dij.ptr,
                          d_scalars.ptr);
@@ -1528,168 +1561,109 @@ int ryujin_hip_ctx::step(int h_old, int stages, const int *h_stage, const double
     HIP_CHECK(hipEventRecord(ev_tau, stream));
   }
   /* tau itself is resolved inside the step-4 kernel (finalize_tau) */
-  mark(2);
+}
 
-  /* Step 4: low-order update, bounds, r_i, p_ij; ghost r (:597-884) */
-  double weight;
-  {
-    double acc = -1.;
-    for (int s = 0; s < stages; ++s)
-      acc += w[s];
-    weight = -acc;
-  }
-  StageArgs<DIM> S{};
-  S.stages = stages;
-  for (int s = 0; s < stages; ++s) {
-    S.U[s] = state(h_stage[s]).U.ptr;
-    S.prec[s] = state(h_stage[s]).prec.ptr;
-    S.w[s] = w[s];
-  }
-  /* Euler, stages == 0, limiter on: P_ij (part 1) is recomputed in step 5 instead of stored here.
-   * A/B on MI355X: -7 % per update in 2-D (k=4, 9 columns). In 3-D (k=5, 27 columns) step 4 drops from 2.01
-   * to 1.34 ms on 4.2 M gridpoints but step 5 grows from 2.16 to 2.77-2.94 ms (27 flux evaluations per row at
-   * 240 registers): -0.7 % ... +1.5 % per update, inside the run-to-run spread -- so only for dim <= 2. */
-  const bool recompute_p = is_euler && DIM <= 2 && stages == 0 && params.limiter_iterations != 0 && !dg;
-  /* Euler and EulerAEOS, stages == 0, Q1 stencil widths: step 4 does not touch P_ij; step 5 forms it once from
-   * d_ij, m_ij and the per-node vectors, limits it and stores it for steps 6 and 7 (kernels_limiter_stage0.hpp)
-   * -- any dimension */
-  constexpr int kStage0Width = DIM == 1 ? 3 : (DIM == 2 ? 9 : 27);
-  const bool stage0_pij = (is_euler || is_aeos) && stages == 0 && params.limiter_iterations != 0 && !dg &&
-                          L.max_row_len <= (uint32_t)kStage0Width;
-  stage0_V = false;
+/* the buffers the planned kernels of steps 4 - 7 need beyond those create() made; allocated by the first update that
+ * takes the path */
+void ryujin_hip_ctx::ensure_limiter_buffers(const StepPlan &plan)
+{
   if (params.limiter_iterations == 2 && d_V.n == 0) {
     d_V.alloc((size_t)L.n_relevant * KP);
     d_slice_unlimited.alloc(L.n_slices);
   }
-  /* step 5 on small meshes: up to four waves per slice, each taking a share of the columns (decided for the whole
-   * mesh, not per launch: the export and the interior part of a split sweep must agree on whether V_i exists) */
-  const uint32_t step5_groups = std::min<uint32_t>(
-      4u, resident_waves_step5 /
-              std::max<uint32_t>(1u, (L.n_slices + kWavesPerBlock - 1) / kWavesPerBlock * kWavesPerBlock));
-  /* WHERE STEP 5 STORES P_ij, only where steps 6 and 7 will read it (kernels_limiter_stage0.hpp): where the update has
-   * two limiter passes and one wave per slice, and not in the checked build (its kernels read all of P_ij). Same bits
-   * in every case. debug_pij_storage (create() refuses other values): 0 the default; 1 per slice, nothing predicted;
-   * 2 per tile with nothing predicted (tests: every tile the neighbour's l_ji limits goes through step 6's repair), per
-   * slice as 1 in 3-D; < 0 everywhere, as rounds 1 - 4.
-   *   PER TILE, up to two dimensions: step 5 stores a (slice, column) tile iff one of its own l_ij comes out limited
-   *   or step 6 read the tile in one of the last updates (SliceFlags::needed_tiles); step 6 -- one launch, the plain
-   *   kernel -- forms the few tiles that are limited through the neighbour's l_ji alone and were not predicted
-   *   (kernels_limiter_stage0.hpp, next_cached_slice). On the Mach-3 step a third to 45 % of the tiles are stored
-   *   where 71 - 93 % of the slices would be, and the update is faster than with either alternative at every stage of
-   *   the flow (profiles/r05t_ab_tile_*). (In 3-D per tile was measured as a loss and retired: DESIGN_HISTORY.md.)
-   *   PER SLICE (3-D; debug_pij_storage = 1 in any dimension): WHILE that pays. Its bookkeeping (the prediction and
-   *   the trigger in step 5, step 6 as three launches) costs a few per cent of the three sweeps, the savings are
-   *   proportional to the share of unlimited slices. Above RYUJIN_PER_SLICE_MAX_LIMITED (the measured break-even,
-   *   profiles/r04*_ab_limited_fraction*) the plain kernels run: P_ij stored EVERYWHERE, step 6 in one launch. The
-   *   fraction is the one step 6 counted between the two latest host synchronisations (1 until the first: the first
-   *   update of a context runs the plain kernels). */
-  const int storage = params.debug_pij_storage;
-  const bool selective = stage0_pij && params.limiter_iterations == 2 && step5_groups < 2 && storage >= 0 &&
-                         !params.debug_expensive_bounds_check;
-  const bool tile_store = DIM <= 2 && selective && storage != 1;
-  const bool per_slice =
-      selective && !tile_store && (storage != 0 || limited_fraction <= (double)RYUJIN_PER_SLICE_MAX_LIMITED);
-  const bool tiles_predicted_from_history = tile_store && storage == 0;
   ensure_pij();
-  if (per_slice && d_slice_first_stored.n == 0) {
+  if (plan.per_slice() && d_slice_first_stored.n == 0) {
     d_slice_first_stored.alloc(L.n_slices);
     d_slice_todo.alloc(L.n_slices);
   }
-  if (tiles_predicted_from_history && d_slice_needed.n == 0) { /* all ones: the first update stores every tile */
+  if (plan.tiles_predicted_from_history && d_slice_needed.n == 0) { /* all ones: the first update stores every tile */
     d_slice_needed.alloc(L.n_slices);
     HIP_CHECK(hipMemsetAsync(d_slice_needed.ptr, 0xff, (size_t)L.n_slices * sizeof(uint32_t), launch_stream));
   }
-  last_per_slice = per_slice;
-  last_tile_store = tile_store;
-  const SliceFlags slice_flags{d_slice_unlimited.ptr, d_slice_first_stored.ptr, d_slice_todo.ptr};
-  const SliceFlags tile_flags{nullptr, nullptr, nullptr, tiles_predicted_from_history ? d_slice_needed.ptr : nullptr};
-  last_s0 = Stage0Src{d_scalars.ptr, old.U.ptr, d_alpha.ptr, d_dij.ptr, d_r.ptr, tile_store ? 1 : 0};
-  /* step 4 stores the first part of P_ij unless step 5 forms it (recompute_p, stage0_pij: Euler and EulerAEOS) */
-  const bool store_p = !(recompute_p || stage0_pij);
+}
+
+/* Step 4: low-order update, bounds, r_i, p_ij; ghost r (:597-884) */
+template <typename E>
+void ryujin_hip_ctx::step4_low_order(const StepPlan &plan, const StepArgs<E::DIMENSION> &a)
+{
+  constexpr int DIM = E::DIMENSION;
+  const auto &eparams = eq_params<E>();
+  const dim3 block(kBlock);
+  const State &old = a.old, &nw = a.nw;
   sweep([&](const DeviceMesh &mm, dim3 grid) {
-    if constexpr (is_sw) {
-      /* rows of at most 3 / 9 columns (1-D, 2-D Q1): one walk over the stencil, the shift-free part of the
-       * limiter's U_ij_bar parked in LDS (kernels_shallow_water.hpp); wider rows: the two walks of the reference */
-      constexpr int kSwWidth = DIM == 1 ? 3 : 9;
-      auto launch_single_walk = [&](auto has_stages, auto friction) {
-        hipLaunchKernelGGL((k_low_order_sw_single_walk<DIM, decltype(has_stages)::value, kSwWidth,
-                                                       decltype(friction)::value>),
-                           grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr, weight, S, old.U.ptr,
-                           old.prec.ptr, d_Z.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr);
-      };
-      if (!dg && L.max_row_len <= (uint32_t)kSwWidth) {
-        const bool friction = eparams.manning != 0.;
-        if (stages == 0 && friction)
-          launch_single_walk(std::false_type{}, std::true_type{});
-        else if (stages == 0)
-          launch_single_walk(std::false_type{}, std::false_type{});
-        else if (friction)
-          launch_single_walk(std::true_type{}, std::true_type{});
-        else
-          launch_single_walk(std::true_type{}, std::false_type{});
-        return;
+    /* every step-4 kernel takes the same arguments; shallow water adds the bathymetry */
+    auto launch = [&](auto kernel, auto... bathymetry) {
+      hipLaunchKernelGGL(kernel, grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr, a.weight, a.S, old.U.ptr,
+                         old.prec.ptr, bathymetry..., d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr,
+                         d_pij.ptr);
+    };
+    if constexpr (is_sw_v<E>) {
+      if (plan.step4_single_walk) {
+        constexpr int kSwWidth = DIM == 1 ? 3 : 9;
+        return with_bool(plan.step4_has_stages, [&](auto has_stages) {
+          with_bool(plan.step4_friction, [&](auto friction) {
+            launch(k_low_order_sw_single_walk<DIM, decltype(has_stages)::value, kSwWidth, decltype(friction)::value>,
+                   d_Z.ptr);
+          });
+        });
       }
     }
-    /* the kernel of the Description with stage vectors, the first part of P_ij stored (Euler, EulerAEOS), dG */
+    /* <has_stages, stores_p, dg>; not storing P_ij goes with no stage vectors and a continuous ansatz (plan_step) */
     auto launch4 = [&](auto has_stages, auto stores_p, auto dg_) {
       constexpr bool HS = decltype(has_stages)::value, SP = decltype(stores_p)::value, DG = decltype(dg_)::value;
-      if constexpr (is_euler)
-        hipLaunchKernelGGL((k_low_order<DIM, HS, SP, DG>), grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr,
-                           weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr,
-                           d_bounds.ptr, d_pij.ptr);
-      else if constexpr (is_aeos)
-        hipLaunchKernelGGL((k_low_order_aeos<DIM, HS, SP, DG>), grid, block, 0, launch_stream, eparams, mm,
-                           d_scalars.ptr, weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr,
-                           d_r.ptr, d_bounds.ptr, d_pij.ptr);
-      else if constexpr (is_scalar)
-        hipLaunchKernelGGL((k_low_order_sc<DIM, HS, DG>), grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr,
-                           weight, S, old.U.ptr, old.prec.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr,
-                           d_bounds.ptr, d_pij.ptr);
+      if constexpr (is_euler_v<E>)
+        launch(k_low_order<DIM, HS, SP, DG>);
+      else if constexpr (is_aeos_v<E>)
+        launch(k_low_order_aeos<DIM, HS, SP, DG>);
+      else if constexpr (is_scalar_v<E>)
+        launch(k_low_order_sc<DIM, HS, DG>);
       else
-        hipLaunchKernelGGL((k_low_order_sw<DIM, HS, DG>), grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr,
-                           weight, S, old.U.ptr, old.prec.ptr, d_Z.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr,
-                           d_bounds.ptr, d_pij.ptr);
+        launch(k_low_order_sw<DIM, HS, DG>, d_Z.ptr);
     };
-    if (dg && stages == 0)
-      launch4(std::false_type{}, std::true_type{}, std::true_type{});
-    else if (dg)
-      launch4(std::true_type{}, std::true_type{}, std::true_type{});
-    else if (!store_p)
+    if (!plan.step4_stores_p)
       launch4(std::false_type{}, std::false_type{}, std::false_type{});
-    else if (stages == 0)
-      launch4(std::false_type{}, std::true_type{}, std::false_type{});
     else
-      launch4(std::true_type{}, std::true_type{}, std::false_type{});
+      with_bool(plan.step4_has_stages, [&](auto has_stages) {
+        with_bool(plan.dg, [&](auto dg_) { launch4(has_stages, std::true_type{}, dg_); });
+      });
   });
   /* EXPENSIVE_BOUNDS_CHECK as a run-time option (Euler): is_admissible() of the low-order update (:851-855) */
-  const bool checked = params.debug_expensive_bounds_check != 0;
-  if (checked)
+  if (plan.checked)
     sweep([&](const DeviceMesh &mm, dim3 grid) {
       hipLaunchKernelGGL(k_check_admissible<E>, grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr,
                          (const double *)nw.U.ptr);
     });
   exchange_vector(d_r.ptr, KP, true);
-  if (dg && params.limiter_iterations != 0) {
+  if (plan.dg && plan.step5 != StepPlan::Step5::none) {
     /* the bounds are extended over the stencil in step 5: their ghost range has to be current
      * (hyperbolic_module.template.h:601-613); SoA, one scalar vector per bound */
     for (int b = 0; b < NB; ++b)
       exchange_vector(d_bounds.ptr + (size_t)b * bounds_stride, 1, true);
   }
-  mark(3);
+}
 
-  /* Step 5: second part of p_ij, first l_ij; ghost rows of l_ij (:892-1041) */
-  const int n_iterations = params.limiter_iterations;
-  if (dg && n_iterations != 0) {
+/* Step 5: second part of p_ij, first l_ij; ghost rows of l_ij (:892-1041) */
+template <typename E>
+void ryujin_hip_ctx::step5_limiter(const StepPlan &plan, const StepArgs<E::DIMENSION> &a)
+{
+  using Step5 = StepPlan::Step5;
+  constexpr int DIM = E::DIMENSION;
+  const auto &eparams = eq_params<E>();
+  const dim3 block(kBlock);
+  const State &old = a.old, &nw = a.nw;
+  if (plan.step5 == Step5::none)
+    return;
+  if (plan.dg) {
     /* bounds over the stencil (:938-948) with the Description's Limiter::combine_bounds; steps 5-7 read the
      * extended bounds */
     sweep([&](const DeviceMesh &mm, dim3 grid) {
-      if constexpr (is_euler)
+      if constexpr (is_euler_v<E>)
         hipLaunchKernelGGL(k_bounds_combine_euler, grid, block, 0, launch_stream, mm, d_bounds.ptr,
                            d_bounds_combined.ptr);
-      else if constexpr (is_sw)
+      else if constexpr (is_sw_v<E>)
         hipLaunchKernelGGL(k_bounds_combine_sw, grid, block, 0, launch_stream, mm, d_bounds.ptr,
                            d_bounds_combined.ptr);
-      else if constexpr (is_aeos)
+      else if constexpr (is_aeos_v<E>)
         hipLaunchKernelGGL((k_bounds_combine_minmax<4, 0x2u>), grid, block, 0, launch_stream, mm, d_bounds.ptr,
                            d_bounds_combined.ptr);
       else
@@ -1698,197 +1672,146 @@ int ryujin_hip_ctx::step(int h_old, int stages, const int *h_stage, const double
     });
     std::swap(d_bounds.ptr, d_bounds_combined.ptr);
   }
-  if (n_iterations != 0) {
-    sweep([&](const DeviceMesh &mm, dim3 grid) {
-      if constexpr (is_euler || is_aeos) {
-        if (stage0_pij) {
-          /* small meshes: up to four waves per slice, each taking a share of the columns (decided for the whole
-           * mesh, not per launch: the export and the interior part of a split sweep must agree on whether V_i exists) */
-          if constexpr (DIM <= 2) {
-            if (tile_store) { /* (tile_store implies one wave per slice) */
-              hipLaunchKernelGGL((k_lij_stage0<E, 1, false, true>), grid, block, 0, launch_stream, eparams, mm,
-                                 d_scalars.ptr, old.U.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr,
-                                 d_pij.ptr, d_lij.ptr, d_V.ptr, tile_flags, 0);
-              stage0_V = d_V.ptr != nullptr;
-              return;
-            }
-          }
-          if (per_slice) {
-            hipLaunchKernelGGL((k_lij_stage0<E, 1, true>), grid, block, 0, launch_stream, eparams, mm,
-                               d_scalars.ptr, old.U.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr,
-                               d_pij.ptr, d_lij.ptr, d_V.ptr, slice_flags, params.debug_pij_storage);
-            stage0_V = true;
-            return;
-          }
-          with_groups(step5_groups, [&](auto ny) {
-            constexpr int NY = decltype(ny)::value;
-            hipLaunchKernelGGL((k_lij_stage0<E, NY>), dim3(grid.x, NY), block, 0, launch_stream, eparams, mm,
-                               d_scalars.ptr, old.U.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr,
-                               d_pij.ptr, d_lij.ptr, NY == 1 ? d_V.ptr : nullptr, tile_flags, 0);
-            stage0_V = NY == 1 && d_V.ptr != nullptr;
-          });
-          return;
-        }
+  sweep([&](const DeviceMesh &mm, dim3 grid) {
+    if constexpr (is_euler_v<E> || is_aeos_v<E>) {
+      /* <waves per slice, P_ij per slice, P_ij per tile>; several waves per slice leave no V_i */
+      auto stage0 = [&](auto ny, auto per_slice, auto per_tile, const SliceFlags &flags, const int storage) {
+        constexpr int NY = decltype(ny)::value;
+        hipLaunchKernelGGL((k_lij_stage0<E, NY, decltype(per_slice)::value, decltype(per_tile)::value>),
+                           dim3(grid.x, NY), block, 0, launch_stream, eparams, mm, d_scalars.ptr, old.U.ptr,
+                           d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr,
+                           NY == 1 ? d_V.ptr : nullptr, flags, storage);
+      };
+      constexpr std::integral_constant<int, 1> one{};
+      if (plan.step5 == Step5::stage0_per_tile) {
+        if constexpr (DIM <= 2)
+          stage0(one, std::false_type{}, std::true_type{}, a.tile_flags, 0);
+        return;
       }
-      if constexpr (is_euler) {
-        if (recompute_p) {
-          /* small meshes: up to four waves per slice, each taking a share of the columns (see the kernel), as
-           * long as all of them are resident at once (256 CUs x 4 SIMDs x 2 waves of this kernel) */
-          const uint32_t groups = resident_waves_step5 / std::max<uint32_t>(1u, grid.x * kWavesPerBlock);
-          with_groups(groups, [&](auto ny) {
-            constexpr int NY = decltype(ny)::value;
-            hipLaunchKernelGGL((k_pij_lij_recompute<DIM, NY>), dim3(grid.x, NY), block, 0, launch_stream, eparams,
-                               mm, d_scalars.ptr, weight, old.U.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr,
-                               d_bounds.ptr, d_pij.ptr, d_lij.ptr);
-          });
-          return;
-        }
-      }
-      {
-        if (dg) {
-          if (L.max_row_len > 64)
-            hipLaunchKernelGGL((k_pij_lij<E, true, true>), grid, block, tail_queue_bytes(mm), launch_stream, eparams, mm,
-                               d_scalars.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_V.ptr);
-          else
-            hipLaunchKernelGGL((k_pij_lij<E, true>), grid, block, tail_queue_bytes(mm), launch_stream, eparams, mm, d_scalars.ptr,
-                               nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_V.ptr);
-          stage0_V = d_V.ptr != nullptr;
-          return;
-        }
-      }
-      if (L.max_row_len > 64)
-        hipLaunchKernelGGL((k_pij_lij<E, false, true>), grid, block, tail_queue_bytes(mm), launch_stream, eparams, mm, d_scalars.ptr,
-                           nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_V.ptr);
-      else
-        hipLaunchKernelGGL(k_pij_lij<E>, grid, block, tail_queue_bytes(mm), launch_stream, eparams, mm, d_scalars.ptr, nw.U.ptr,
-                           d_r.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_V.ptr);
-      stage0_V = d_V.ptr != nullptr;
-    });
-    if (checked) /* the first limiter pass in the checked control flow (limiter.template.h:110-134,244-322) */
-      sweep([&](const DeviceMesh &mm, dim3 grid) {
-        hipLaunchKernelGGL(k_check_limiter<E>, grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr,
-                           (const double *)nw.U.ptr, (const double *)d_bounds.ptr, (const double *)d_pij.ptr,
-                           (const double *)nullptr);
-      });
-    exchange_matrix(d_lij.ptr, true);
-  }
-  mark(4);
-
-  /* Steps 6, 7: symmetrise l_ij, high-order update, next l_ij (:1053-1182) */
-  /* a pending sadd of the device-resident RK driver is applied by the last sweep */
-  const FusedSadd fused_sadd = pending_sadd;
-  pending_sadd = FusedSadd{0., 0., nullptr};
-  /* ... and so are the precomputed values and Riemann records of the new vector, where the next pre-pass would be a
-   * sweep of its own (large meshes: below bc_fold_max_slices the boundary conditions ride on that sweep) */
-  bool fuse_precompute = false;
-  if constexpr (E::kFusablePrecompute)
-    fuse_precompute = pending_precompute && n_iterations != 0 &&
-                      L.n_slices > bc_fold_max_slices &&
-                      L.max_row_len <= (uint32_t)(DIM == 1 ? 3 : (DIM == 2 ? 9 : 27));
-  pending_precompute = false;
-  nw.precomputed = false;
-  const FusedPrecompute fused_prec{fuse_precompute ? nw.prec.ptr : nullptr, fuse_precompute ? nw.rrec.ptr : nullptr};
-  if (fused_sadd.src && n_iterations == 0)
-    throw HipError(RYUJIN_ERR_ARG, "internal: fused sadd without a limiter pass");
-  bool step6_flags = false; /* step 6 left SliceFlags::unlimited for every slice: the last sweep may use it */
-  for (int pass = 0; pass < n_iterations; ++pass) {
-    const bool last_round = (pass + 1 == n_iterations);
-    if (n_iterations == 2 && last_round)
-      std::swap(d_lij.ptr, d_lij_next.ptr);
-    constexpr int kCachedWidth = DIM == 1 ? 3 : (DIM == 2 ? 9 : 27);
-    if (last_round) {
-      sweep([&](const DeviceMesh &mm, dim3 grid) {
-        constexpr int kLastChunk = DIM == 3 ? RYUJIN_LAST_CHUNK_3D : (DIM == 2 ? RYUJIN_LAST_CHUNK_2D : kCachedWidth);
-        if (L.max_row_len <= (uint32_t)kCachedWidth)
-          hipLaunchKernelGGL((k_high_order_last_cached<E, kCachedWidth, kLastChunk>), grid,
-                             block, 0, launch_stream, eparams, mm, nw.U.ptr, d_pij.ptr, d_lij.ptr, fused_sadd,
-                             fused_prec, step6_flags ? d_slice_unlimited.ptr : nullptr);
-        else
-          hipLaunchKernelGGL((k_high_order<E, true>), grid, block, 0, launch_stream, eparams, mm, nw.U.ptr,
-                             d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_lij_next.ptr, fused_sadd);
-      });
-    } else {
-      /* 3-D: cache all l_ij and the P_ij of the first RYUJIN_HO_CP_3D columns */
-      constexpr int kCachedP = DIM == 3 ? RYUJIN_HO_CP_3D
-                                        : (DIM == 2 ? (RYUJIN_HO_CP_2D < kCachedWidth ? RYUJIN_HO_CP_2D : kCachedWidth) : kCachedWidth);
-      sweep([&](const DeviceMesh &mm, dim3 grid) {
-        if constexpr (is_euler || is_aeos) {
-          if (per_slice) {
-            /* three launches over all slices: the light one finishes the slices without a stored P_ij in which
-             * nothing was limited (V_i), the repair launch completes the P_ij of the slices that turned out limited
-             * without (all of) it, the heavy one runs the limited slices (kernels_limiter.hpp) */
-            hipLaunchKernelGGL((k_high_order_next_cached<E, kCachedWidth, kCachedP, false, kHoLight>), grid, block, 0,
-                               launch_stream, eparams, mm, nw.U.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr,
-                               d_lij_next.ptr, d_V.ptr, last_s0, slice_flags);
-            hipLaunchKernelGGL(k_pij_repair<E>, grid, block, 0, launch_stream, mm, last_s0, d_pij.ptr, slice_flags);
-            hipLaunchKernelGGL((k_high_order_next_cached<E, kCachedWidth, kCachedP, false, kHoHeavy>), grid, block, 0,
-                               launch_stream, eparams, mm, nw.U.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr,
-                               d_lij_next.ptr, d_V.ptr, last_s0, slice_flags);
-            step6_flags = true;
-            return;
-          }
-        }
-        if constexpr (DIM <= 2) {
-          /* small meshes: the four waves of a block share one slice (see the kernel) while all of them fit */
-          const uint32_t n_launch = mm.slice_end - mm.slice_begin;
-          if (!tile_store && L.max_row_len <= (uint32_t)kCachedWidth && n_launch * kWavesPerBlock <= resident_waves_step6) {
-            /* (not with P_ij stored per tile: the export part of a large mesh may be this small, and the split
-             * variant does not form the tiles step 5 left out) */
-            hipLaunchKernelGGL((k_high_order_next_cached<E, kCachedWidth, kCachedWidth, true>), dim3(n_launch),
-                               block, 0, launch_stream, eparams, mm, nw.U.ptr, d_bounds.ptr, d_pij.ptr,
-                               d_lij.ptr, d_lij_next.ptr, stage0_V ? d_V.ptr : nullptr, last_s0,
-                               SliceFlags{stage0_V ? d_slice_unlimited.ptr : nullptr, nullptr, nullptr});
-            step6_flags = stage0_V;
-            return;
-          }
-        }
-        if (L.max_row_len <= (uint32_t)kCachedWidth) {
-          /* (with P_ij stored per tile the plain kernel forms the tiles step 5 left out: forms_missing_tiles) */
-          SliceFlags flags6 = tile_flags;
-          flags6.unlimited = stage0_V ? d_slice_unlimited.ptr : nullptr;
-          hipLaunchKernelGGL((k_high_order_next_cached<E, kCachedWidth, kCachedP>), grid, block, 0, launch_stream,
-                             eparams, mm, nw.U.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_lij_next.ptr,
-                             stage0_V ? d_V.ptr : nullptr, last_s0, flags6);
-          step6_flags = stage0_V;
-        } else if (L.max_row_len > 64)
-          hipLaunchKernelGGL((k_high_order<E, false, true>), grid, block, 0, launch_stream, eparams, mm, nw.U.ptr,
-                             d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_lij_next.ptr, FusedSadd{0., 0., nullptr});
-        else
-          hipLaunchKernelGGL((k_high_order<E, false>), grid, block, 0, launch_stream, eparams, mm, nw.U.ptr,
-                             d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_lij_next.ptr, FusedSadd{0., 0., nullptr});
-      });
-      if (checked) /* the update after the first pass (:1121-1126) and the second pass's success (:1155-1161) */
-        sweep([&](const DeviceMesh &mm, dim3 grid) {
-          hipLaunchKernelGGL(k_check_admissible<E>, grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr,
-                             (const double *)nw.U.ptr);
-          hipLaunchKernelGGL(k_check_limiter<E>, grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr,
-                             (const double *)nw.U.ptr, (const double *)d_bounds.ptr, (const double *)d_pij.ptr,
-                             (const double *)d_lij.ptr);
-        });
-      exchange_matrix(d_lij_next.ptr, true);
+      if (plan.step5 == Step5::stage0_per_slice)
+        return stage0(one, std::true_type{}, std::false_type{}, a.slice_flags, params.debug_pij_storage);
+      if (plan.step5 == Step5::stage0_groups)
+        return with_groups(plan.step5_groups,
+                           [&](auto ny) { stage0(ny, std::false_type{}, std::false_type{}, a.tile_flags, 0); });
     }
-    if (checked && last_round) /* the final update (:1121-1126) */
-      sweep([&](const DeviceMesh &mm, dim3 grid) {
-        hipLaunchKernelGGL(k_check_admissible<E>, grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr,
-                           (const double *)nw.U.ptr);
+    if constexpr (is_euler_v<E>) {
+      if (plan.step5 == Step5::recompute) {
+        with_groups(plan.recompute_groups(grid.x), [&](auto ny) {
+          constexpr int NY = decltype(ny)::value;
+          hipLaunchKernelGGL((k_pij_lij_recompute<DIM, NY>), dim3(grid.x, NY), block, 0, launch_stream, eparams,
+                             mm, d_scalars.ptr, a.weight, old.U.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr,
+                             d_bounds.ptr, d_pij.ptr, d_lij.ptr);
+        });
+        return;
+      }
+    }
+    with_bool(plan.dg, [&](auto dg_) {
+      with_bool(plan.wide, [&](auto wide) {
+        hipLaunchKernelGGL((k_pij_lij<E, decltype(dg_)::value, decltype(wide)::value>), grid, block,
+                           tail_queue_bytes(mm), launch_stream, eparams, mm, d_scalars.ptr, nw.U.ptr, d_r.ptr,
+                           d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_V.ptr);
       });
-    mark(5 + pass);
-  }
-  for (int k = 5 + n_iterations; k <= 7; ++k)
-    mark(k);
-  nw.precomputed = fuse_precompute;
+    });
+  });
+  if (plan.checked) /* the first limiter pass in the checked control flow (limiter.template.h:110-134,244-322) */
+    sweep([&](const DeviceMesh &mm, dim3 grid) {
+      hipLaunchKernelGGL(k_check_limiter<E>, grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr,
+                         (const double *)nw.U.ptr, (const double *)d_bounds.ptr, (const double *)d_pij.ptr,
+                         (const double *)nullptr);
+    });
+  exchange_matrix(d_lij.ptr, true);
+}
 
-  join_export(); /* (the exchange of U_new stays in flight: whoever reads its ghost range joins it) */
-  if (!deferred)
-    allreduce_scalar(&d_scalars.ptr->restart_needed, 1); /* MPI::logical_or(restart_needed), :1194 */
-  /* (deferred: the restart flag is folded into its accumulator by the next stage's step_begin(), or by
-   * time_step() behind the last stage) */
+/* Step 6, the first of two limiter passes: symmetrise l_ij, high-order update, next l_ij (:1053-1182) */
+template <typename E>
+void ryujin_hip_ctx::step6_high_order_next(const StepPlan &plan, const StepArgs<E::DIMENSION> &a)
+{
+  using Step6 = StepPlan::Step6;
+  constexpr int DIM = E::DIMENSION;
+  constexpr int kWidth = q1_stencil_width(DIM);
+  /* 3-D: cache all l_ij and the P_ij of the first RYUJIN_HO_CP_3D columns */
+  constexpr int kCachedP =
+      DIM == 3 ? RYUJIN_HO_CP_3D : (DIM == 2 ? (RYUJIN_HO_CP_2D < kWidth ? RYUJIN_HO_CP_2D : kWidth) : kWidth);
+  const auto &eparams = eq_params<E>();
+  const dim3 block(kBlock);
+  const State &nw = a.nw;
+  double *const V = plan.has_V ? d_V.ptr : nullptr;
+  uint8_t *const unlimited = plan.has_V ? d_slice_unlimited.ptr : nullptr;
+  sweep([&](const DeviceMesh &mm, dim3 grid) {
+    if constexpr (is_euler_v<E> || is_aeos_v<E>) {
+      if (plan.step6 == Step6::per_slice) { /* light, repair, heavy (plan_step) */
+        auto launch_mode = [&](auto mode) {
+          hipLaunchKernelGGL((k_high_order_next_cached<E, kWidth, kCachedP, false, decltype(mode)::value>), grid,
+                             block, 0, launch_stream, eparams, mm, nw.U.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr,
+                             d_lij_next.ptr, d_V.ptr, last_s0, a.slice_flags);
+        };
+        launch_mode(std::integral_constant<int, kHoLight>{});
+        hipLaunchKernelGGL(k_pij_repair<E>, grid, block, 0, launch_stream, mm, last_s0, d_pij.ptr, a.slice_flags);
+        launch_mode(std::integral_constant<int, kHoHeavy>{});
+        return;
+      }
+    }
+    if constexpr (DIM <= 2) {
+      const uint32_t n_launch = mm.slice_end - mm.slice_begin;
+      if (plan.step6_shares_slices(n_launch)) {
+        hipLaunchKernelGGL((k_high_order_next_cached<E, kWidth, kWidth, true>), dim3(n_launch), block, 0,
+                           launch_stream, eparams, mm, nw.U.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_lij_next.ptr,
+                           V, last_s0, SliceFlags{unlimited, nullptr, nullptr});
+        return;
+      }
+    }
+    if (plan.step6 == Step6::cached) {
+      SliceFlags flags6 = a.tile_flags;
+      flags6.unlimited = unlimited;
+      hipLaunchKernelGGL((k_high_order_next_cached<E, kWidth, kCachedP>), grid, block, 0, launch_stream, eparams, mm,
+                         nw.U.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_lij_next.ptr, V, last_s0, flags6);
+    } else
+      with_bool(plan.wide, [&](auto wide) {
+        hipLaunchKernelGGL((k_high_order<E, false, decltype(wide)::value>), grid, block, 0, launch_stream, eparams,
+                           mm, nw.U.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_lij_next.ptr,
+                           FusedSadd{0., 0., nullptr});
+      });
+  });
+  if (plan.checked) /* the update after the first pass (:1121-1126) and the second pass's success (:1155-1161) */
+    sweep([&](const DeviceMesh &mm, dim3 grid) {
+      hipLaunchKernelGGL(k_check_admissible<E>, grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr,
+                         (const double *)nw.U.ptr);
+      hipLaunchKernelGGL(k_check_limiter<E>, grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr,
+                         (const double *)nw.U.ptr, (const double *)d_bounds.ptr, (const double *)d_pij.ptr,
+                         (const double *)d_lij.ptr);
+    });
+  exchange_matrix(d_lij_next.ptr, true);
+}
 
-  HIP_CHECK(hipGetLastError());
-  if (deferred) {
-    *tau_out = std::numeric_limits<double>::quiet_NaN(); /* known at the end of the RK step */
-    return RYUJIN_OK;
-  }
+/* Step 7, the last limiter pass: symmetrise l_ij, high-order update; carries a pending sadd and the next pre-pass */
+template <typename E>
+void ryujin_hip_ctx::step7_high_order_last(const StepPlan &plan, const StepArgs<E::DIMENSION> &a)
+{
+  constexpr int DIM = E::DIMENSION;
+  constexpr int kWidth = q1_stencil_width(DIM);
+  constexpr int kLastChunk = DIM == 3 ? RYUJIN_LAST_CHUNK_3D : (DIM == 2 ? RYUJIN_LAST_CHUNK_2D : kWidth);
+  const auto &eparams = eq_params<E>();
+  const dim3 block(kBlock);
+  const State &nw = a.nw;
+  sweep([&](const DeviceMesh &mm, dim3 grid) {
+    if (plan.step7 == StepPlan::Step7::last_cached)
+      hipLaunchKernelGGL((k_high_order_last_cached<E, kWidth, kLastChunk>), grid, block, 0, launch_stream, eparams,
+                         mm, nw.U.ptr, d_pij.ptr, d_lij.ptr, a.fused_sadd, a.fused_prec,
+                         plan.step6_flags ? d_slice_unlimited.ptr : nullptr);
+    else
+      hipLaunchKernelGGL((k_high_order<E, true>), grid, block, 0, launch_stream, eparams, mm, nw.U.ptr,
+                         d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_lij_next.ptr, a.fused_sadd);
+  });
+  if (plan.checked) /* the final update (:1121-1126) */
+    sweep([&](const DeviceMesh &mm, dim3 grid) {
+      hipLaunchKernelGGL(k_check_admissible<E>, grid, block, 0, launch_stream, eparams, mm, d_scalars.ptr,
+                         (const double *)nw.U.ptr);
+    });
+}
+
+/* the end of an update outside a device-resident RK step: scalars read back, timers, status */
+int ryujin_hip_ctx::finish_step(double *tau_out)
+{
   HIP_CHECK(hipMemcpyAsync(h_scalars, d_scalars.ptr, sizeof(DeviceScalars), hipMemcpyDeviceToHost,
                            stream));
   HIP_CHECK(hipStreamSynchronize(stream));
@@ -1901,7 +1824,7 @@ int ryujin_hip_ctx::step(int h_old, int stages, const int *h_stage, const double
       sweep_ms[k + 1] = ms;
     }
     sweep_ms[0] = 0.;
-    if (step2_split) {
+    if (last_plan.step2_split) {
       float ms = 0.f;
       HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[8]));
       sweep_ms[0] = ms;
@@ -1924,6 +1847,103 @@ int ryujin_hip_ctx::step(int h_old, int stages, const int *h_stage, const double
     return RYUJIN_RESTART;
   }
   return RYUJIN_OK;
+}
+
+template <typename E>
+int ryujin_hip_ctx::step(int h_old, int stages, const int *h_stage, const double *w, int h_new,
+                         double tau_in, double tau_max_in, double *tau_out)
+{
+  constexpr int DIM = E::DIMENSION;
+  State &old = state(h_old);
+  State &nw = state(h_new);
+  if (h_old == h_new)
+    throw HipError(RYUJIN_ERR_ARG, "old and new state vector must differ");
+  nw.precomputed = false; /* rewritten below */
+
+  /* which kernels this update runs: decided here, once (step_plan.hpp) */
+  const StepPlan plan = plan_step(plan_input<E>(stages));
+  if (plan.unsupported)
+    throw HipError(RYUJIN_ERR_UNSUPPORTED, plan.unsupported);
+  if (plan.violated)
+    throw HipError(RYUJIN_ERR_ARG, std::string("internal: ") + plan.violated);
+  last_plan = plan;
+  pending_precompute = false;
+
+  /* scalars: tau_max := tau_max_in, flags := 0 -- carried by the first sweep of step 2 (step_begin) */
+  const bool use_device_tau = deferred && rk_stage > 0;
+  struct ClearBegin { /* a step that throws before its first sweep must not leave it armed */
+    StepBegin &b;
+    ~ClearBegin() { b = StepBegin{}; }
+  } clear_begin{pending_begin};
+  pending_begin = StepBegin{d_scalars.ptr,
+                            tau_max_in,
+                            tau_in,
+                            (!deferred || rk_stage == 0) ? 1 : 0,
+                            (deferred && rk_stage > 0) ? rk_stage - 1 : -1,
+                            use_device_tau ? 1 : 0,
+                            deferred ? rk_stage : 0};
+  mark(0);
+  step2_dij_alpha<E>(plan, old);
+  mark(1);
+  step3_diagonal_tau<E>(plan, old);
+  mark(2);
+
+  StepArgs<DIM> a{old, nw};
+  {
+    double acc = -1.;
+    for (int s = 0; s < stages; ++s)
+      acc += w[s];
+    a.weight = -acc;
+  }
+  a.S.stages = stages;
+  for (int s = 0; s < stages; ++s) {
+    a.S.U[s] = state(h_stage[s]).U.ptr;
+    a.S.prec[s] = state(h_stage[s]).prec.ptr;
+    a.S.w[s] = w[s];
+  }
+  ensure_limiter_buffers(plan);
+  a.slice_flags = SliceFlags{d_slice_unlimited.ptr, d_slice_first_stored.ptr, d_slice_todo.ptr};
+  a.tile_flags = SliceFlags{nullptr, nullptr, nullptr, plan.tiles_predicted_from_history ? d_slice_needed.ptr : nullptr};
+  last_s0 = Stage0Src{d_scalars.ptr, old.U.ptr, d_alpha.ptr, d_dij.ptr, d_r.ptr, plan.per_tile() ? 1 : 0};
+  step4_low_order<E>(plan, a);
+  mark(3);
+  step5_limiter<E>(plan, a);
+  mark(4);
+
+  /* a pending sadd of the device-resident RK driver is applied by the last sweep, and so are the precomputed values
+   * and Riemann records of the new vector where the plan says so (fuse_precompute) */
+  a.fused_sadd = pending_sadd;
+  pending_sadd = FusedSadd{0., 0., nullptr};
+  if (plan.fuse_precompute)
+    a.fused_prec = FusedPrecompute{nw.prec.ptr, nw.rrec.ptr};
+  const int n_iterations = params.limiter_iterations;
+  if (a.fused_sadd.src && n_iterations == 0)
+    throw HipError(RYUJIN_ERR_ARG, "internal: fused sadd without a limiter pass");
+  if (n_iterations == 2) {
+    step6_high_order_next<E>(plan, a);
+    mark(5);
+    std::swap(d_lij.ptr, d_lij_next.ptr);
+  }
+  if (n_iterations != 0) {
+    step7_high_order_last<E>(plan, a);
+    mark(4 + n_iterations);
+  }
+  for (int k = 5 + n_iterations; k <= 7; ++k)
+    mark(k);
+  nw.precomputed = plan.fuse_precompute;
+
+  join_export(); /* (the exchange of U_new stays in flight: whoever reads its ghost range joins it) */
+  if (!deferred)
+    allreduce_scalar(&d_scalars.ptr->restart_needed, 1); /* MPI::logical_or(restart_needed), :1194 */
+  /* (deferred: the restart flag is folded into its accumulator by the next stage's step_begin(), or by
+   * time_step() behind the last stage) */
+
+  HIP_CHECK(hipGetLastError());
+  if (deferred) {
+    *tau_out = std::numeric_limits<double>::quiet_NaN(); /* known at the end of the RK step */
+    return RYUJIN_OK;
+  }
+  return finish_step(tau_out);
 }
 
 /* Device-resident Runge-Kutta driver: ryujin::TimeIntegrator::step for the
@@ -2105,7 +2125,7 @@ int ryujin_hip_ctx::time_step(int scheme, int h_state, int n_tmp, const int *h_t
           HIP_CHECK(hipEventElapsedTime(&ms, ev_rk[st][k], ev_rk[st][k + 1]));
           sweep_ms_accum[k + 1] += ms;
         }
-        if (step2_split) {
+        if (last_plan.step2_split) {
           float ms = 0.f;
           HIP_CHECK(hipEventElapsedTime(&ms, ev_rk[st][0], ev_rk[st][8]));
           sweep_ms_accum[0] += ms;
@@ -3028,7 +3048,7 @@ int ryujin_hip_limiter_statistics(ryujin_hip_ctx *ctx, double *limited_slice_fra
     if (limited_slice_fraction)
       *limited_slice_fraction = ctx->limited_fraction;
     if (pij_stored)
-      *pij_stored = ctx->last_per_slice ? 2 : (ctx->last_tile_store ? 3 : 1);
+      *pij_stored = ctx->last_plan.pij_stored;
     if (stored_slice_fraction)
       *stored_slice_fraction = ctx->stored_fraction;
     return RYUJIN_OK;
@@ -3041,7 +3061,7 @@ int ryujin_hip_tile_statistics(ryujin_hip_ctx *ctx, double *stored_fraction, dou
   return guarded([&]() {
     if (!ctx)
       throw HipError(RYUJIN_ERR_ARG, "null context");
-    const bool tiles = ctx->last_tile_store;
+    const bool tiles = ctx->last_plan.per_tile();
     if (stored_fraction)
       *stored_fraction = tiles ? ctx->stored_fraction : 1.;
     if (read_fraction)
@@ -3099,7 +3119,7 @@ int ryujin_hip_debug_fetch(ryujin_hip_ctx *ctx, int what, double *out, size_t n_
     case 1: fetch_matrix(ctx->d_lij.ptr, 1); break;
     case 2:
       ctx->ensure_pij();
-      if (ctx->last_per_slice || ctx->last_tile_store)
+      if (ctx->last_plan.pij_stored != 1)
         dispatch_equation(ctx->params.equation, ctx->dim, [&](auto tag) {
           using E = typename decltype(tag)::type;
           if constexpr (std::is_same<typename E::Params, EulerParams>::value ||

@@ -1,0 +1,119 @@
+"""The step plan on the CPU (ryujin_amd/csrc/step_plan.hpp): which kernels an update runs. The stored-P_ij variants give
+the same bits by design, so a change that silently moves a configuration to another variant passes every parity test;
+here the invariants the kernels rely on are checked over the whole input lattice, and the kernel paths of the benchmark
+configurations are pinned to what the kernel traces of record show (profiles/r07_kernel_trace*.md; C1:
+profiles/r04p_kernel_trace_c1.md with the template arguments of today's k_lij_stage0). Host logic only: no GPU, no HIP
+runtime."""
+import json
+import os
+import subprocess
+
+import pytest
+
+from ryujin_amd.workloads import benchmark_workload
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "tests", "cpp", "step_plan_cases")
+
+
+@pytest.fixture(scope="module")
+def checker():
+    src = os.path.join(ROOT, "tests", "cpp", "step_plan_cases.cc")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "ryujin_amd", "csrc"), src,
+                    "-o", BIN], check=True)
+    return BIN
+
+
+def _run(checker, *args):
+    out = subprocess.run([checker, *map(str, args)], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    return json.loads(out.stdout)
+
+
+def test_invariants_over_the_input_lattice(checker):
+    """Per tile implies V_i, one wave per slice and dim <= 2; per slice implies V_i; the checked build stores P_ij
+    everywhere; the two selective modes exclude each other and imply the stage-0 kernel; step 4 stores its part of P_ij
+    exactly when step 5 neither recomputes nor forms it; step 6 gets V_i only where it exists and never shares slices
+    with per-tile storage; EulerAEOS with rows of more than 32 entries is refused. And the lattice reaches every
+    variant: all three storage modes, one to four waves per slice, both sides of the fold limit."""
+    r = _run(checker, "lattice")
+    assert r["violations"] == 0, r
+    # 11 (equation, dim) x 3 stages x 3 iterations x 2 dG x 5 widths x 11 meshes x 4 storages x 2 checked x 4 fractions
+    # x 2 pending x 2 Riemann paths / friction
+    assert r["plans"] == 11 * 3 * 3 * 2 * 5 * 11 * 4 * 2 * 4 * 2 * 2
+    assert r["refused"] == r["plans"] // 11 * 3 * 2 // 5  # EulerAEOS (3 of 11) with 33 or 65 entries (2 of 5)
+    for key in ("pij_stored_1", "pij_stored_2", "pij_stored_3", "stage0_groups_1", "stage0_groups_2", "stage0_groups_3",
+                "stage0_groups_4", "step6_shares_slices", "fuse_precompute", "has_V", "step5_0", "step5_1", "step5_2",
+                "step5_3", "step5_4", "step5_5", "step6_0", "step6_1", "step6_2", "step6_3"):
+        assert r.get(key, 0) > 0, (key, r)
+
+
+def _step_points(cells_per_unit):
+    """Gridpoints of the Mach-3 step mesh, [0,3]x[0,1] minus the step [0.6,3]x[0,0.2] (the nodes strictly inside it and
+    on its lower and right edge do not exist)."""
+    n = cells_per_unit
+    nx0, ny0 = round(0.6 * n), round(0.2 * n)
+    return (3 * n + 1) * (n + 1) - (3 * n - nx0) * ny0
+
+
+def _slices(points):
+    return (points + 63) // 64
+
+
+E2, E3, A2, S2 = "Euler<2>", "Euler<3>", "EulerAeos<2>", "ShallowWater<2>"
+
+# (equation, dim, widest row, gridpoints) and the kernels of steps 2 - 7, first update of a context (limited fraction 1)
+# and developed flow (the fraction the bench line of record reports; C3 44 %, the others do not depend on it)
+PINS = {
+    "step2d": (("euler", 2, 9, _step_points(benchmark_workload("step2d").resolution)), 0.9, [
+        f"k_dij_alpha_records<{E2}, false>", "k_dij_diag_unrolled<9>", "k_low_order<2, false, false, false>",
+        f"k_lij_stage0<{E2}, 1, false, true>", f"k_high_order_next_cached<{E2}, 9, 9, false, 0>",
+        f"k_high_order_last_cached<{E2}, 9, 3>"], None),
+    "step2d_aeos": (("euler_aeos", 2, 9, _step_points(benchmark_workload("step2d_aeos").resolution)), 0.9, [
+        "k_alpha_aeos<2>", "k_dij_aeos<2>", "k_dij_diag_unrolled<9>", "k_low_order_aeos<2, false, false, false>",
+        f"k_lij_stage0<{A2}, 1, false, true>", f"k_high_order_next_cached<{A2}, 9, 9, false, 0>",
+        f"k_high_order_last_cached<{A2}, 9, 3>"], None),
+    "sw2d": (("shallow_water", 2, 9, (benchmark_workload("sw2d").resolution + 1) ** 2), 0.67, [
+        f"k_dij_alpha_records<{S2}, false>", "k_dij_diag_unrolled<9>", "k_low_order_sw_single_walk<2, false, 9, false>",
+        f"k_pij_lij<{S2}, false, false>", f"k_high_order_next_cached<{S2}, 9, 9, false, 0>",
+        f"k_high_order_last_cached<{S2}, 9, 3>"], None),
+    "cylinder3d": (("euler", 3, 27, 4176134), 1.0, [  # h = 1/96: the gridpoints of record (DESIGN_HISTORY.md)
+        f"k_dij_alpha_records<{E3}, false>", "k_dij_diag_unrolled<27>", "k_low_order<3, false, false, false>",
+        f"k_lij_stage0<{E3}, 1, false, false>", f"k_high_order_next_cached<{E3}, 27, 2, false, 0>",
+        f"k_high_order_last_cached<{E3}, 27, 3>"], None),
+    # first update: P_ij everywhere, the plain kernels; developed: per slice, step 6 as light, repair, heavy
+    "sedov3d": (("euler", 3, 27, (benchmark_workload("sedov3d").resolution + 1) ** 3), 0.44, [
+        f"k_dij_alpha_records<{E3}, false>", "k_dij_diag_unrolled<27>", "k_low_order<3, false, false, false>",
+        f"k_lij_stage0<{E3}, 1, true, false>", f"k_high_order_next_cached<{E3}, 27, 2, false, 1>",
+        f"k_pij_repair<{E3} >", f"k_high_order_next_cached<{E3}, 27, 2, false, 2>",
+        f"k_high_order_last_cached<{E3}, 27, 3>"], [
+        f"k_dij_alpha_records<{E3}, false>", "k_dij_diag_unrolled<27>", "k_low_order<3, false, false, false>",
+        f"k_lij_stage0<{E3}, 1, false, false>", f"k_high_order_next_cached<{E3}, 27, 2, false, 0>",
+        f"k_high_order_last_cached<{E3}, 27, 3>"]),
+    # C1, bench.py --cells-per-unit 130: 43 109 gridpoints, 674 slices: three waves per slice in step 5 (no V_i), the
+    # four waves of a block share a slice in step 6
+    "c1": (("euler", 2, 9, _step_points(130)), 1.0, [
+        f"k_dij_alpha_records<{E2}, false>", "k_dij_diag_unrolled<9>", "k_low_order<2, false, false, false>",
+        f"k_lij_stage0<{E2}, 3, false, false>", f"k_high_order_next_cached<{E2}, 9, 9, true, 0>",
+        f"k_high_order_last_cached<{E2}, 9, 3>"], None),
+}
+STORED = {"step2d": 3, "step2d_aeos": 3, "sw2d": 1, "cylinder3d": 1, "sedov3d": 2, "c1": 1}
+
+
+def test_gridpoints_of_record():
+    assert _step_points(995) == 2498844 and _step_points(130) == 43109  # DESIGN_HISTORY.md
+
+
+@pytest.mark.parametrize("key", sorted(PINS))
+def test_kernel_path_of_the_benchmark_configurations(checker, key):
+    """The full kernel path, by the names rocprofv3 prints (bench.py's KERNEL_OF_SWEEP matches their prefixes), for the
+    first update of a context and for the developed flow."""
+    (equation, dim, width, points), fraction, developed, first = PINS[key]
+    r = _run(checker, "path", equation, dim, width, _slices(points), fraction)
+    assert r["kernels"] == developed, r
+    assert r["pij_stored"] == STORED[key]
+    r = _run(checker, "path", equation, dim, width, _slices(points), 1.0)
+    assert r["kernels"] == (developed if first is None else first), r
+    assert r["pij_stored"] == (STORED[key] if first is None else 1)
+    # the last sweep carries the next pre-pass on the large Euler and shallow-water meshes, never on C1 or EulerAEOS
+    assert r["fuse_precompute"] == (key in ("step2d", "sw2d", "cylinder3d", "sedov3d"))
