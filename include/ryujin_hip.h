@@ -651,6 +651,88 @@ int ryujin_hip_quantities_time_averaged(ryujin_hip_ctx *ctx, int manifold, doubl
 int ryujin_hip_quantities_time_series(ryujin_hip_ctx *ctx, int manifold, double *rows, size_t capacity_rows,
                                       size_t *n_rows, int clear);
 
+/* ---- InitialValues: analytic initial and Dirichlet states, device resident -- */
+/* InitialValues::initial_state(position, t) of the reference (source/initial_values.template.h:154-196) for its
+ * analytic InitialState classes, evaluated by ONE device function (ryujin_amd/csrc/initial_states_device.hpp) for
+ * every use: at arbitrary points, at the mesh nodes (interpolate_hyperbolic_vector, :222-262) and at the
+ * boundary_map entries at the stage times of a Runge-Kutta step (hyperbolic_module.template.h:137-139 called from
+ * time_integrator.template.h:279-510). The point is translated by `position`, `direction` is rolled onto the x-axis
+ * (z first, then y), the state's momentum is rotated back (affine_transform / affine_transform_vector, :66-148);
+ * `direction` is normalised at configure time. A 1-D profile in 2-D / 3-D is evaluated on the first coordinate
+ * behind the transform, momentum along `direction`. In 1-D `direction` only has to be non-zero, as in the reference.
+ *
+ * States and their `params` (the reference's parameter names; its defaults in brackets -- the library applies
+ * none, the caller passes every value). Euler and EulerAEOS (the conserved state through the context's equation of
+ * state, from_initial_state, euler_aeos/hyperbolic_system.h:1470-1512):
+ *   RYUJIN_IV_UNIFORM            euler/initial_state_uniform.h:36-50            0-2 "primitive state" (rho, u, p)
+ *   RYUJIN_IV_RADIAL_CONTRAST    euler/initial_state_radial_contrast.h:29-62    0-2 "primitive state inner",
+ *                                                                               3-5 "primitive state outer", 6 "radius"
+ *   RYUJIN_IV_ISENTROPIC_VORTEX  euler/initial_state_isentropic_vortex.h:54-92  0 "mach number" [2], 1 "beta" [5],
+ *                                (dim = 2)                                      2 "gamma" [1.4] (EulerAEOS only)
+ *   RYUJIN_IV_LEBLANC            euler/initial_state_leblanc.h:63-120           none (gamma = 5/3 is part of the state)
+ *   RYUJIN_IV_RAREFACTION        euler/initial_state_rarefaction.h:40-160       0 "gamma" [1.4] (EulerAEOS only)
+ * Euler takes gamma from ryujin_hip_params. Shallow water (gravity and the Manning coefficient from ryujin_hip_params;
+ * the bathymetry stays what ryujin_hip_create was given as initial_precomputed):
+ *   RYUJIN_IV_CIRCULAR_DAM_BREAK shallow_water/initial_state_circular_dam_break.h:48-54   0 "still water depth",
+ *                                                                               1 "radius", 2 "dam amplitude"
+ *   RYUJIN_IV_PARABOLOID         shallow_water/initial_state_paraboloid.h:66-101 (dim = 1)  0 "free surface radius",
+ *                                                                               1 "water height", 2 "paraboloid length",
+ *                                                                               3 "speed"
+ *   RYUJIN_IV_RITTER_DAM_BREAK   shallow_water/initial_state_ritter_dam_break.h:58-80    0 "time initial",
+ *                                                                               1 "left water depth"
+ *   RYUJIN_IV_SMOOTH_VORTEX      shallow_water/initial_state_smooth_vortex.h:55-85 (dim = 2, without bathymetry)
+ *                                                                               0 "reference depth", 1 "mach number",
+ *                                                                               2 "beta"
+ *   RYUJIN_IV_SLOPING_FRICTION   shallow_water/initial_state_sloping_friction.h:50-85    0 "ramp slope",
+ *                                                                               1 "initial discharge"
+ * The formulas, statement by statement, are those of ryujin_amd/initial_states.py.
+ *
+ *   configure     positions [n_relevant * dim]: the node positions of this rank, ghost rows included;
+ *                 b_positions [n_bdry * dim]: the positions of the boundary_map entries in boundary_map order (NULL
+ *                 if n_bdry == 0). Copied to the device once. A second configure replaces the first. Every rank of a
+ *                 partitioned run configures with its own positions.
+ *   evaluate      out [n * k] = initial_state(points [n * dim], t), AoS; n = 0 returns RYUJIN_OK and writes nothing.
+ *                 Waits for the context's stream.
+ *   interpolate   the state vector behind `handle` := initial_state(position_i, t) for ALL n_relevant rows (ghost
+ *                 rows are evaluated like owned ones: nothing to exchange). An enqueue.
+ *   prepare_state_vector_iv   prepare_state_vector with the Dirichlet data evaluated on the device at t.
+ *   time_step_iv  ryujin_hip_time_step_n with the Dirichlet data of every stage evaluated on the device at
+ *                 t + c_s tau (SSPRK22 c = 0, 1; SSPRK33 0, 1, 1/2; ERK stage s at s), tau read from the device where
+ *                 the first stage left it: unlike ryujin_hip_time_step_fn nothing on the host waits for tau, no
+ *                 host function is called and nothing crosses PCIe; one host synchronisation per RK step, at its
+ *                 end. All seven schemes, bang-bang recovery with its internal re-run included. A rank without
+ *                 boundary entries launches nothing for it.
+ * RYUJIN_ERR_ARG: an unknown state or one the context's Description does not have, a zero direction, NULL positions,
+ * any entry but configure before configure. RYUJIN_ERR_UNSUPPORTED: scalar conservation (the reference's
+ * configurations use the muparser "function" state there), perturbation != 0 (an unseeded generator in the
+ * reference), a state in a dimension it is not defined for. */
+enum {
+  RYUJIN_IV_UNIFORM = 0,
+  RYUJIN_IV_RADIAL_CONTRAST = 1,
+  RYUJIN_IV_ISENTROPIC_VORTEX = 2,
+  RYUJIN_IV_LEBLANC = 3,
+  RYUJIN_IV_RAREFACTION = 4,
+  RYUJIN_IV_CIRCULAR_DAM_BREAK = 5,
+  RYUJIN_IV_PARABOLOID = 6,
+  RYUJIN_IV_RITTER_DAM_BREAK = 7,
+  RYUJIN_IV_SMOOTH_VORTEX = 8,
+  RYUJIN_IV_SLOPING_FRICTION = 9
+};
+typedef struct ryujin_hip_initial_values {
+  int state;           /* RYUJIN_IV_*: "configuration" of subsection "E - InitialValues" */
+  double params[16];   /* see above; unused entries 0 */
+  double direction[3]; /* "initial - direction"; the first dim entries are read */
+  double position[3];  /* "initial - position" */
+  double perturbation; /* "perturbation": must be 0 */
+} ryujin_hip_initial_values;
+int ryujin_hip_initial_values_configure(ryujin_hip_ctx *ctx, const ryujin_hip_initial_values *initial_values,
+                                        const double *positions, const double *b_positions);
+int ryujin_hip_initial_values_evaluate(ryujin_hip_ctx *ctx, const double *points, size_t n, double t, double *out);
+int ryujin_hip_initial_values_interpolate(ryujin_hip_ctx *ctx, int handle, double t);
+int ryujin_hip_prepare_state_vector_iv(ryujin_hip_ctx *ctx, int handle, double t);
+int ryujin_hip_time_step_iv(ryujin_hip_ctx *ctx, int scheme, int h_state, int n_tmp, const int *h_tmp, double t,
+                            double tau_max, int cfl_recovery, double cfl_min, double cfl_max, double *tau_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,6 +108,70 @@ class PostprocessQuantity(C.Structure):
     _fields_ = [("kind", C.c_int), ("is_primitive", C.c_int), ("component", C.c_int)]
 
 
+# InitialValues (RYUJIN_IV_*): the analytic states of ryujin_hip_initial_values_configure
+(IV_UNIFORM, IV_RADIAL_CONTRAST, IV_ISENTROPIC_VORTEX, IV_LEBLANC, IV_RAREFACTION, IV_CIRCULAR_DAM_BREAK,
+ IV_PARABOLOID, IV_RITTER_DAM_BREAK, IV_SMOOTH_VORTEX, IV_SLOPING_FRICTION) = range(10)
+
+
+class InitialValues(C.Structure):
+    """ryujin_hip_initial_values"""
+    _fields_ = [("state", C.c_int), ("params", C.c_double * 16), ("direction", C.c_double * 3),
+                ("position", C.c_double * 3), ("perturbation", C.c_double)]
+
+
+# configuration name (subsection "E - InitialValues") -> (RYUJIN_IV_*, shallow water?, parameters); a parameter is
+# (the reference's name, first slot of ryujin_hip_initial_values::params, default -- a tuple fills consecutive
+# slots). "gamma" is a parameter of the state for EulerAEOS only (Euler takes the system's).
+IV_STATES = {
+    "uniform": (IV_UNIFORM, False, (("primitive state", 0, (1.4, 3.0, 1.0)),)),
+    "radial contrast": (IV_RADIAL_CONTRAST, False, (("primitive state inner", 0, (1.0, 0.0, 100.0)),
+                                                    ("primitive state outer", 3, (1.0, 0.0, 0.1)),
+                                                    ("radius", 6, 0.5))),
+    "isentropic vortex": (IV_ISENTROPIC_VORTEX, False, (("mach number", 0, 2.0), ("beta", 1, 5.0),
+                                                        ("gamma", 2, 1.4))),
+    "leblanc": (IV_LEBLANC, False, ()),
+    "rarefaction": (IV_RAREFACTION, False, (("gamma", 0, 1.4),)),
+    "circular dam break": (IV_CIRCULAR_DAM_BREAK, True, (("still water depth", 0, 0.5), ("radius", 1, 2.5),
+                                                         ("dam amplitude", 2, 2.5))),
+    "paraboloid": (IV_PARABOLOID, True, (("free surface radius", 0, 1.0), ("water height", 1, 0.1),
+                                         ("paraboloid length", 2, 10000.0), ("speed", 3, 2.0))),
+    "ritter dam break": (IV_RITTER_DAM_BREAK, True, (("time initial", 0, 0.1), ("left water depth", 1, 0.005))),
+    "smooth vortex": (IV_SMOOTH_VORTEX, True, (("reference depth", 0, 1.0), ("mach number", 1, 2.0),
+                                               ("beta", 2, 0.1))),
+    "sloping friction": (IV_SLOPING_FRICTION, True, (("ramp slope", 0, 1.0), ("initial discharge", 1, 0.1))),
+}
+
+
+def initial_values_struct(name: str, dim: int, direction=None, position=None, perturbation: float = 0.0,
+                          **params) -> InitialValues:
+    """ryujin_hip_initial_values for a configuration name of the reference with its parameter names (spaces may be
+    written as underscores: mach_number=1.0); what is not given takes the reference's default. ValueError for an
+    unknown configuration or parameter."""
+    if name not in IV_STATES:
+        raise ValueError(f"Could not find an initial state description with name \"{name}\"")
+    state, _, spec = IV_STATES[name]
+    iv = InitialValues()
+    iv.state = state
+    given = {k.replace("_", " "): v for k, v in params.items()}
+    for pname, slot, default in spec:
+        value = given.pop(pname, default)
+        values = tuple(value) if isinstance(default, tuple) else (value,)
+        if len(values) != (len(default) if isinstance(default, tuple) else 1):
+            raise ValueError(f"parameter \"{pname}\" of \"{name}\" takes {len(default)} values")
+        for q, v in enumerate(values):
+            iv.params[slot + q] = float(v)
+    if given:
+        raise ValueError(f"\"{name}\" has no parameter {sorted(given)}")
+    d = (1.0,) + (0.0,) * (dim - 1) if direction is None else tuple(np.atleast_1d(direction).astype(float))
+    x = (0.0,) * dim if position is None else tuple(np.atleast_1d(position).astype(float))
+    if len(d) != dim or len(x) != dim:
+        raise ValueError(f"direction and position take {dim} components")
+    for q in range(dim):
+        iv.direction[q], iv.position[q] = d[q], x[q]
+    iv.perturbation = float(perturbation)
+    return iv
+
+
 def component_names(equation: int, dim: int) -> tuple[tuple[str, ...], tuple[str, ...]]:
     """(View::component_names, View::primitive_component_names) of a Description
     (source/<eq>/hyperbolic_system.h)."""
@@ -223,6 +287,8 @@ HIP_SYMBOLS = [
     "ryujin_hip_quantities_add_manifold", "ryujin_hip_quantities_reset", "ryujin_hip_quantities_clear_statistics",
     "ryujin_hip_quantities_accumulate", "ryujin_hip_quantities_instantaneous", "ryujin_hip_quantities_time_averaged",
     "ryujin_hip_quantities_time_series",
+    "ryujin_hip_initial_values_configure", "ryujin_hip_initial_values_evaluate",
+    "ryujin_hip_initial_values_interpolate", "ryujin_hip_prepare_state_vector_iv", "ryujin_hip_time_step_iv",
 ]
 
 
@@ -321,5 +387,11 @@ def load_hip():
         lib.ryujin_hip_quantities_time_averaged.argtypes = [vp, C.c_int, c_double_p, c_double_p, c_double_p]
         lib.ryujin_hip_quantities_time_series.argtypes = [vp, C.c_int, c_double_p, C.c_size_t,
                                                           C.POINTER(C.c_size_t), C.c_int]
+        lib.ryujin_hip_initial_values_configure.argtypes = [vp, C.POINTER(InitialValues), c_double_p, c_double_p]
+        lib.ryujin_hip_initial_values_evaluate.argtypes = [vp, c_double_p, C.c_size_t, C.c_double, c_double_p]
+        lib.ryujin_hip_initial_values_interpolate.argtypes = [vp, C.c_int, C.c_double]
+        lib.ryujin_hip_prepare_state_vector_iv.argtypes = [vp, C.c_int, C.c_double]
+        lib.ryujin_hip_time_step_iv.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int_p, C.c_double, C.c_double,
+                                                C.c_int, C.c_double, C.c_double, c_double_p]
         _hip = lib
     return _hip

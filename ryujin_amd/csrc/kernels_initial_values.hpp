@@ -1,0 +1,88 @@
+// HIP kernels for InitialValues on the device (gfx950): initial_state(position, t) of an analytic state at
+// arbitrary points, at the mesh nodes, and at the boundary_map entries at a Runge-Kutta stage time.
+//
+// Reference: source/initial_values.template.h:222-262 (interpolate_hyperbolic_vector) and
+// source/hyperbolic_module.template.h:137-139 (Dirichlet data of prepare_state_vector) called with the stage times
+// of source/time_integrator.template.h:279-510.
+//   k_initial_values_points     one thread per point: positions AoS [n][DIM] -> states AoS [n][stride]. With
+//                               stride = K it serves ryujin_hip_initial_values_evaluate, with stride = KP and the
+//                               context's node positions it writes a state vector in place
+//                               (ryujin_hip_initial_values_interpolate; ghost rows are evaluated like owned rows, the
+//                               same function of the same position on every rank: nothing to exchange).
+//   k_initial_values_dirichlet  one thread per boundary_map entry in the library's grouped order (positions permuted
+//                               once at configure time): writes the buffer k_apply_bc* reads. The stage time
+//                               t + c tau_rk is formed HERE, from the tau the first stage left on the device, so
+//                               that the host never waits for it; two rounded operations (the library is built with
+//                               -ffp-contract=off), i.e. the bits of the host's t + c * tau.
+// Both are latency-bound launches of a few thousand threads at most on the boundary (2 in 1-D); 64 threads per block
+// spread the boundary of a 2-D mesh over as many compute units as it has waves (profiles/initial_values_timing.md).
+
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "initial_states_device.hpp"
+#include "kernels_euler.hpp"
+
+namespace ryujin_hip
+{
+  constexpr int kInitialValuesBlock = 64;
+
+  template <typename E>
+  __global__ __launch_bounds__(kInitialValuesBlock) void k_initial_values_points(
+      const InitialValuesParams P, const uint32_t n, const double *__restrict__ positions, const double t,
+      const int stride, double *__restrict__ out)
+  {
+    constexpr int DIM = E::DIMENSION, K = E::K;
+    const uint32_t i = blockIdx.x * (uint32_t)kInitialValuesBlock + threadIdx.x;
+    if (i >= n)
+      return;
+    double x[DIM];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      x[d] = positions[(size_t)i * DIM + d];
+    double U[K];
+    initial_state<E>(P, x, t, U);
+#pragma unroll
+    for (int q = 0; q < K; ++q)
+      out[(size_t)i * stride + q] = U[q];
+    for (int q = K; q < stride; ++q) /* the pad lane of an odd state, as state_upload leaves it */
+      out[(size_t)i * stride + q] = 0.;
+  }
+
+  /* b_id: entries whose boundary id does not read Dirichlet data are skipped (their slot is never read) */
+  template <typename E>
+  __global__ __launch_bounds__(kInitialValuesBlock) void k_initial_values_dirichlet(
+      const InitialValuesParams P, const uint32_t n_bdry, const double *__restrict__ b_positions,
+      const uint8_t *__restrict__ b_id, const double t, const double c,
+      const DeviceScalars *__restrict__ scalars, double *__restrict__ dirichlet)
+  {
+    constexpr int DIM = E::DIMENSION, K = E::K;
+    const uint32_t e = blockIdx.x * (uint32_t)kInitialValuesBlock + threadIdx.x;
+    if (e >= n_bdry)
+      return;
+    const int id = b_id[e];
+    if (id != RYUJIN_BC_DIRICHLET && id != RYUJIN_BC_DYNAMIC && id != RYUJIN_BC_DIRICHLET_MOMENTUM)
+      return;
+    double time = t;
+    if (c != 0.) {
+      /* an invalid tau_max ends the step in RYUJIN_ERR_TAU whatever this stage sees: evaluate at t */
+      double tau = scalars->tau_rk;
+      if (!(tau > 0.) || isinf(tau))
+        tau = 0.;
+      const double increment = c * tau;
+      time = t + increment;
+    }
+    double x[DIM];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      x[d] = b_positions[(size_t)e * DIM + d];
+    double U[K];
+    initial_state<E>(P, x, time, U);
+#pragma unroll
+    for (int q = 0; q < K; ++q)
+      dirichlet[(size_t)e * K + q] = U[q];
+  }
+} // namespace ryujin_hip

@@ -48,6 +48,7 @@
 #include "scalar_conservation_device.hpp"
 #include "kernels_postprocessor.hpp"
 #include "kernels_quantities.hpp"
+#include "kernels_initial_values.hpp"
 
 using namespace ryujin_hip;
 
@@ -514,6 +515,24 @@ struct ryujin_hip_ctx {
   hipEvent_t ev_tau = nullptr;
   bool want_tau_early = false;
   double *h_dirichlet_stage[kMaxRkStages] = {}; /* pinned staging, one per RK stage */
+  /* InitialValues (ryujin_hip_initial_values_*, kernels_initial_values.hpp): the configured analytic state, the
+   * node positions and the boundary_map positions in the grouped order of d_b_i (bdry_perm applied once) */
+  bool iv_configured = false;
+  InitialValuesParams iv{};
+  DeviceBuffer<double> d_iv_positions, d_iv_b_positions;
+  DeviceBuffer<double> d_iv_points, d_iv_values; /* scratch of evaluate(), grown on demand */
+  /* Dirichlet data of a prepare_state_vector() evaluated on the device at t + c tau_rk (c = 0: at t) */
+  struct IvStage {
+    bool on;
+    double t, c;
+  };
+  void require_initial_values() const
+  {
+    if (!iv_configured)
+      throw HipError(RYUJIN_ERR_ARG, "initial values: not configured (ryujin_hip_initial_values_configure)");
+  }
+  template <typename E>
+  void initial_values_points(const double *d_points, size_t n, double t, int stride, double *d_out);
 
   struct State {
     DeviceBuffer<double> U, prec;
@@ -664,7 +683,7 @@ struct ryujin_hip_ctx {
   template <typename F>
   void sweep(F &&launch);
   template <typename E>
-  void prepare_state_vector(int h, const double *dirichlet);
+  void prepare_state_vector(int h, const double *dirichlet, IvStage iv_stage = IvStage{false, 0., 0.});
   template <typename E>
   int step(int h_old, int stages, const int *h_stage, const double *w, int h_new, double tau_in,
            double tau_max_in, double *tau_out);
@@ -697,7 +716,8 @@ struct ryujin_hip_ctx {
   template <typename E>
   int time_step(int scheme, int h_state, int n_tmp, const int *h_tmp, const double *dirichlet,
                 double tau_max, int cfl_recovery, double cfl_min, double cfl_max, double *tau_out,
-                double t = 0., ryujin_hip_dirichlet_fn dirichlet_fn = nullptr, void *dirichlet_user = nullptr);
+                double t = 0., ryujin_hip_dirichlet_fn dirichlet_fn = nullptr, void *dirichlet_user = nullptr,
+                bool dirichlet_on_device = false);
   void mark(int k)
   {
     if (timers_enabled)
@@ -1289,13 +1309,39 @@ void ryujin_hip_ctx::store_pij_for_debug()
   HIP_CHECK(hipStreamSynchronize(stream));
 }
 
+/* one thread per point (k_initial_values_points) on the compute stream */
 template <typename E>
-void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet)
+void ryujin_hip_ctx::initial_values_points(const double *d_points, size_t n, double t, int stride, double *d_out)
+{
+  if (n == 0)
+    return;
+  hipLaunchKernelGGL(k_initial_values_points<E>, dim3(grid_for(n, kInitialValuesBlock)), dim3(kInitialValuesBlock), 0,
+                     stream, iv, (uint32_t)n, d_points, t, stride, d_out);
+  HIP_CHECK(hipGetLastError());
+}
+
+template <typename E>
+void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStage iv_stage)
 {
   const auto &eparams = eq_params<E>(); /* shadows the member: the equation's parameter block */
   State &s = state(h);
   const dim3 block(kBlock);
-  if (dirichlet && n_bdry) {
+  if (iv_stage.on && n_bdry && needs_dirichlet) {
+    /* initial_state(position, t + c tau) of every boundary_map entry, evaluated where the data is read: behind
+     * every kernel of the previous stage that read the buffer (compute stream order; the export part of the previous
+     * pre-pass may have applied boundary conditions on comm_stream) and behind the step-4 kernel of the first stage,
+     * which left tau_rk. Nothing on the host waits for tau. */
+    if constexpr (is_scalar_v<E>) {
+      throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: scalar conservation is not offered");
+    } else {
+      join_export();
+      hipLaunchKernelGGL(k_initial_values_dirichlet<E>, dim3(grid_for(n_bdry, kInitialValuesBlock)),
+                         dim3(kInitialValuesBlock), 0, stream, iv, n_bdry, d_iv_b_positions.ptr, d_b_id.ptr,
+                         iv_stage.t, iv_stage.c, d_scalars.ptr, d_dirichlet.ptr);
+      HIP_CHECK(hipGetLastError());
+      have_dirichlet = true;
+    }
+  } else if (dirichlet && n_bdry) {
     /* permute into the grouped order, then upload */
     if (deferred) {
       /* inside a device-resident RK step: a pinned staging buffer per stage, no host synchronisation (a buffer
@@ -1957,7 +2003,7 @@ template <typename E>
 int ryujin_hip_ctx::time_step(int scheme, int h_state, int n_tmp, const int *h_tmp, const double *dirichlet,
                               double tau_max, int cfl_recovery, double cfl_min, double cfl_max,
                               double *tau_out, double t, ryujin_hip_dirichlet_fn dirichlet_fn,
-                              void *dirichlet_user)
+                              void *dirichlet_user, bool dirichlet_on_device)
 {
   const int U = h_state;
   int n_stages = 0;
@@ -2032,16 +2078,22 @@ int ryujin_hip_ctx::time_step(int scheme, int h_state, int n_tmp, const int *h_t
     const bool time_dependent = dirichlet_fn != nullptr && n_bdry > 0 && needs_dirichlet;
     std::vector<double> stage_data;
     double tau_first = 0.;
+    auto stage_coefficient = [&](int st) -> double {
+      if (st == 0)
+        return 0.;
+      return erk ? (double)st : (scheme == RYUJIN_SCHEME_SSPRK_33 && st == 2 ? 0.5 : 1.);
+    };
     auto dirichlet_at = [&](int st) -> const double * {
       if (!time_dependent)
         return st == 0 ? dirichlet : nullptr;
-      double c = 0.;
-      if (st > 0)
-        c = erk ? (double)st : (scheme == RYUJIN_SCHEME_SSPRK_33 && st == 2 ? 0.5 : 1.);
+      const double c = stage_coefficient(st);
       stage_data.assign((size_t)n_bdry * K, 0.);
       dirichlet_fn(dirichlet_user, t + c * tau_first, stage_data.data());
       return stage_data.data();
     };
+    /* ... or through the configured analytic state on the device (ryujin_hip_time_step_iv): the kernel forms the
+     * stage time from the tau the first stage left in DeviceScalars::tau_rk; the host waits for nothing */
+    auto device_dirichlet_at = [&](int st) { return IvStage{dirichlet_on_device, t, stage_coefficient(st)}; };
     struct EarlyTau {
       bool &flag;
       ~EarlyTau() { flag = false; }
@@ -2055,7 +2107,7 @@ int ryujin_hip_ctx::time_step(int scheme, int h_state, int n_tmp, const int *h_t
     }
 
     rk_stage = 0;
-    prepare_state_vector<E>(U, dirichlet_at(0));
+    prepare_state_vector<E>(U, dirichlet_at(0), device_dirichlet_at(0));
     pending_precompute = true; /* every stage's result goes straight into the next prepare_state_vector() */
     step<E>(U, 0, none, no_w, T[0], 0., first_tau_max, &dummy);
     result = T[0];
@@ -2068,7 +2120,7 @@ int ryujin_hip_ctx::time_step(int scheme, int h_state, int n_tmp, const int *h_t
     if (erk) {
       for (int st = 1; st < n_stages; ++st) {
         rk_stage = st;
-        prepare_state_vector<E>(T[st - 1], dirichlet_at(st));
+        prepare_state_vector<E>(T[st - 1], dirichlet_at(st), device_dirichlet_at(st));
         pending_precompute = true;
         step<E>(T[st - 1], erk_stage[st].n, erk_stage[st].h, erk_stage[st].w, T[st], 1. /*device tau*/,
                 no_limit, &dummy);
@@ -2092,7 +2144,7 @@ int ryujin_hip_ctx::time_step(int scheme, int h_state, int n_tmp, const int *h_t
           ryujin_hip_sadd(this, h_new, sa, sb, U);
       };
       rk_stage = 1;
-      prepare_state_vector<E>(T[0], dirichlet_at(1));
+      prepare_state_vector<E>(T[0], dirichlet_at(1), device_dirichlet_at(1));
       if (scheme == RYUJIN_SCHEME_SSPRK_22)
         stage_with_sadd(T[0], T[1], 1. / 2., 1. / 2.);
       else
@@ -2100,7 +2152,7 @@ int ryujin_hip_ctx::time_step(int scheme, int h_state, int n_tmp, const int *h_t
       result = T[1];
       if (n_stages >= 3) {
         rk_stage = 2;
-        prepare_state_vector<E>(T[1], dirichlet_at(2));
+        prepare_state_vector<E>(T[1], dirichlet_at(2), device_dirichlet_at(2));
         stage_with_sadd(T[1], T[0], 2. / 3., 1. / 3.);
         result = T[0];
       }
@@ -3755,6 +3807,291 @@ int ryujin_hip_quantities_time_series(ryujin_hip_ctx *ctx, int manifold, double 
     if (clear)
       m.n_rows = 0; /* series.clear() (:665) */
     return RYUJIN_OK;
+  });
+}
+
+} /* extern "C" */
+
+/* ---- InitialValues: analytic initial and Dirichlet states, device resident -------------------------------- */
+
+namespace
+{
+  /* the Descriptions that have analytic states here: everything but scalar conservation */
+  template <typename F>
+  auto dispatch_initial_values(ryujin_hip_ctx *ctx, F &&f)
+  {
+    if (ctx->params.equation == RYUJIN_EQ_SCALAR_CONSERVATION)
+      throw HipError(RYUJIN_ERR_UNSUPPORTED,
+                     "initial values: scalar conservation is not offered (the reference's configurations use "
+                     "the muparser \"function\" state there)");
+    return dispatch_equation(ctx->params.equation, ctx->dim, [&](auto tag) {
+      using E = typename decltype(tag)::type;
+      if constexpr (std::is_same<typename E::Params, ScalarParams>::value)
+        return RYUJIN_ERR_UNSUPPORTED;
+      else
+        return f(tag);
+    });
+  }
+
+  /* InitialValues::parse_parameters_callback (initial_values.template.h:154-196) and the constructors of the
+   * InitialState classes: everything that does not depend on (x, t) */
+  InitialValuesParams make_initial_values_params(const ryujin_hip_ctx &ctx, const ryujin_hip_initial_values &in)
+  {
+    const int dim = ctx.dim, eq = ctx.params.equation;
+    InitialValuesParams P{};
+    if (in.state < RYUJIN_IV_UNIFORM || in.state > RYUJIN_IV_SLOPING_FRICTION)
+      throw HipError(RYUJIN_ERR_ARG, "initial values: unknown state " + std::to_string(in.state));
+    const bool sw_state = in.state >= RYUJIN_IV_CIRCULAR_DAM_BREAK;
+    if (sw_state != (eq == RYUJIN_EQ_SHALLOW_WATER))
+      throw HipError(RYUJIN_ERR_ARG, "initial values: the Description of this context has no such state");
+    if (in.perturbation != 0.)
+      throw HipError(RYUJIN_ERR_UNSUPPORTED,
+                     "initial values: perturbation != 0 draws from an unseeded generator in the reference");
+    if ((in.state == RYUJIN_IV_ISENTROPIC_VORTEX || in.state == RYUJIN_IV_SMOOTH_VORTEX) && dim != 2)
+      throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: the vortex states are defined for dim = 2");
+    if (in.state == RYUJIN_IV_PARABOLOID && dim != 1)
+      throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: paraboloid is offered for dim = 1");
+    for (int q = 0; q < 16; ++q)
+      if (std::isnan(in.params[q]))
+        throw HipError(RYUJIN_ERR_ARG, "initial values: NaN parameter");
+
+    P.state = in.state;
+    for (int q = 0; q < 16; ++q)
+      P.p[q] = in.params[q];
+    for (int d = 0; d < dim; ++d)
+      P.position[d] = in.position[d];
+
+    /* initial_direction_ /= initial_direction_.norm(), then the rolls of affine_transform (:78-106) */
+    double n[3] = {0., 0., 0.}, norm2 = 0.;
+    for (int d = 0; d < dim; ++d)
+      norm2 += in.direction[d] * in.direction[d];
+    const double norm = std::sqrt(norm2);
+    if (!(norm > 0.) || std::isinf(norm))
+      throw HipError(RYUJIN_ERR_ARG, "initial values: direction is the zero vector (or not finite)");
+    for (int d = 0; d < dim; ++d)
+      n[d] = in.direction[d] / norm;
+    if (dim == 3) {
+      const double r = std::sqrt(n[0] * n[0] + n[2] * n[2]);
+      P.roll_z = r > 1.0e-14;
+      P.nz_x = n[0] / r;
+      P.nz_z = n[2] / r;
+    }
+    if (dim >= 2) {
+      const double r = std::sqrt(n[0] * n[0] + n[1] * n[1]);
+      P.roll_y = r > 1.0e-14;
+      P.ny_x = n[0] / r;
+      P.ny_y = n[1] / r;
+    }
+
+    const ryujin_hip_params &hp = ctx.params;
+    if (eq == RYUJIN_EQ_EULER_AEOS) {
+      P.eos = hp.eos;
+      P.eos_gamma = hp.gamma;
+      P.eos_b = hp.eos_covolume_b;
+      P.eos_q = hp.eos_q;
+      P.eos_pinf = hp.eos_pinf;
+      P.eos_a = hp.eos_vdw_a;
+      P.jwl_A = hp.jwl_A;
+      P.jwl_B = hp.jwl_B;
+      P.jwl_R1 = hp.jwl_R1;
+      P.jwl_R2 = hp.jwl_R2;
+      P.jwl_omega = hp.jwl_omega;
+      P.jwl_rho_0 = hp.jwl_rho_0;
+    }
+    /* gamma of the state itself: the system's for Euler; for EulerAEOS the states that need one take it as their
+     * own parameter "gamma" (`if constexpr (!View::have_gamma)` in the reference) */
+    double *c = P.c;
+    switch (in.state) {
+    case RYUJIN_IV_UNIFORM:
+    case RYUJIN_IV_RADIAL_CONTRAST:
+    case RYUJIN_IV_LEBLANC:
+      c[0] = hp.gamma;
+      break;
+    case RYUJIN_IV_ISENTROPIC_VORTEX: {
+      const double gamma = eq == RYUJIN_EQ_EULER ? hp.gamma : in.params[2];
+      if (!(gamma > 1.))
+        throw HipError(RYUJIN_ERR_ARG, "initial values: isentropic vortex needs gamma > 1");
+      c[0] = gamma;
+      c[1] = in.params[1] / (2.0 * M_PI);
+      c[2] = (gamma - 1.0) / (2.0 * gamma);
+      c[3] = 1.0 / (gamma - 1.0);
+      break;
+    }
+    case RYUJIN_IV_RAREFACTION: {
+      const double gamma = eq == RYUJIN_EQ_EULER ? hp.gamma : in.params[0];
+      if (!(gamma > 1.))
+        throw HipError(RYUJIN_ERR_ARG, "initial values: rarefaction needs gamma > 1");
+      const double rho_l = 3.0, p_l = 1.0;
+      const double c_l = std::sqrt(gamma * p_l / rho_l);
+      const double u_l = c_l;
+      const double rho_r = 0.5;
+      const double p_r = std::pow(rho_r / rho_l, gamma) * p_l;
+      const double c_r = std::sqrt(gamma * p_r / rho_r);
+      const double u_r = u_l + 2.0 * (c_l - c_r) / (gamma - 1.0);
+      c[0] = gamma;
+      c[1] = rho_l;
+      c[2] = u_l;
+      c[3] = p_l;
+      c[4] = c_l;
+      c[5] = rho_r;
+      c[6] = u_r;
+      c[7] = p_r;
+      c[8] = c_r;
+      c[9] = 2.0 / (gamma + 1.0);
+      c[10] = (gamma - 1.0) / ((gamma + 1.0) * c_l);
+      c[11] = c_l + ((gamma - 1.0) / 2.0) * u_l;
+      c[12] = 2.0 / (gamma - 1.0);
+      c[13] = 2.0 * gamma / (gamma - 1.0);
+      c[14] = 0.2 / (u_r - u_l);
+      break;
+    }
+    case RYUJIN_IV_CIRCULAR_DAM_BREAK:
+      break;
+    case RYUJIN_IV_PARABOLOID: {
+      const double a = in.params[0], h0 = in.params[1], B = in.params[3];
+      const double g = hp.gravity, k = hp.manning_friction_coefficient;
+      const double p = std::sqrt(8.0 * g * h0) / a;
+      const double s = std::sqrt(p * p - k * k) / 2.0;
+      c[0] = g;
+      c[1] = k;
+      c[2] = h0 / (a * a);
+      c[3] = s;
+      c[4] = (a * a * B * B) / (8.0 * g * g * h0);
+      c[5] = 1.0 / 4.0 * k * k - s * s;
+      c[6] = s * k;
+      c[7] = -(B * B / (4.0 * g));
+      c[8] = -(B / g);
+      break;
+    }
+    case RYUJIN_IV_RITTER_DAM_BREAK:
+      c[0] = hp.gravity;
+      c[1] = std::sqrt(hp.gravity * in.params[1]);
+      c[2] = 4.0 / (9.0 * hp.gravity);
+      break;
+    case RYUJIN_IV_SMOOTH_VORTEX:
+      c[0] = hp.gravity;
+      c[1] = in.params[2] / (2.0 * M_PI);
+      c[2] = 1.0 / (2.0 * hp.gravity);
+      break;
+    default: { /* RYUJIN_IV_SLOPING_FRICTION */
+      const double n_m = hp.manning_friction_coefficient, slope = in.params[0], q0 = in.params[1];
+      const double exponent = 1.0 / (2.0 + 4.0 / 3.0);
+      const double profile = n_m * n_m * q0 * q0 / slope;
+      c[0] = std::pow(profile, exponent);
+      break;
+    }
+    }
+    return P;
+  }
+} // namespace
+
+extern "C" {
+
+int ryujin_hip_initial_values_configure(ryujin_hip_ctx *ctx, const ryujin_hip_initial_values *initial_values,
+                                        const double *positions, const double *b_positions)
+{
+  return guarded_ctx(ctx, [&]() {
+    if (!initial_values)
+      throw HipError(RYUJIN_ERR_ARG, "initial values: null argument");
+    if (ctx->params.equation == RYUJIN_EQ_SCALAR_CONSERVATION)
+      throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: scalar conservation is not offered");
+    const InitialValuesParams P = make_initial_values_params(*ctx, *initial_values);
+    if ((!positions && ctx->L.n_relevant > 0) || (!b_positions && ctx->n_bdry > 0))
+      throw HipError(RYUJIN_ERR_ARG, "initial values: positions missing");
+    const size_t dim = (size_t)ctx->dim;
+    /* a second configure replaces the first: nothing enqueued may still read the old positions */
+    ctx->finish();
+    ctx->iv_configured = false;
+    ctx->d_iv_positions.upload(positions, (size_t)ctx->L.n_relevant * dim);
+    std::vector<double> grouped((size_t)ctx->n_bdry * dim);
+    for (uint32_t e = 0; e < ctx->n_bdry; ++e)
+      for (size_t d = 0; d < dim; ++d)
+        grouped[(size_t)e * dim + d] = b_positions[(size_t)ctx->bdry_perm[e] * dim + d];
+    ctx->d_iv_b_positions.upload(grouped);
+    ctx->iv = P;
+    ctx->iv_configured = true;
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_initial_values_evaluate(ryujin_hip_ctx *ctx, const double *points, size_t n, double t, double *out)
+{
+  return guarded_ctx(ctx, [&]() {
+    ctx->require_initial_values();
+    if (n == 0)
+      return RYUJIN_OK;
+    if (!points || !out || n > 0xffffffffull)
+      throw HipError(RYUJIN_ERR_ARG, "initial values: bad argument");
+    const size_t dim = (size_t)ctx->dim, K = (size_t)ctx->K;
+    if (ctx->d_iv_points.n < n * dim)
+      ctx->d_iv_points.alloc(n * dim, false);
+    if (ctx->d_iv_values.n < n * K)
+      ctx->d_iv_values.alloc(n * K, false);
+    /* on the compute stream, in order with whatever it holds; may be called from a Dirichlet callback inside a
+     * Runge-Kutta step (nothing of the exchange bookkeeping is touched) */
+    HIP_CHECK(hipMemcpyAsync(ctx->d_iv_points.ptr, points, n * dim * sizeof(double), hipMemcpyHostToDevice,
+                             ctx->stream));
+    dispatch_initial_values(ctx, [&](auto tag) {
+      ctx->template initial_values_points<typename decltype(tag)::type>(ctx->d_iv_points.ptr, n, t, (int)K,
+                                                                        ctx->d_iv_values.ptr);
+      return RYUJIN_OK;
+    });
+    HIP_CHECK(hipMemcpyAsync(out, ctx->d_iv_values.ptr, n * K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_initial_values_interpolate(ryujin_hip_ctx *ctx, int handle, double t)
+{
+  return guarded_ctx(ctx, [&]() {
+    ctx->require_initial_values();
+    auto &s = ctx->state(handle);
+    ctx->wait_comm(); /* an exchange of this vector may still be in flight */
+    s.precomputed = false;
+    return dispatch_initial_values(ctx, [&](auto tag) {
+      ctx->template initial_values_points<typename decltype(tag)::type>(ctx->d_iv_positions.ptr, ctx->L.n_relevant, t,
+                                                                        ctx->KP, s.U.ptr);
+      return RYUJIN_OK;
+    });
+  });
+}
+
+int ryujin_hip_prepare_state_vector_iv(ryujin_hip_ctx *ctx, int handle, double t)
+{
+  return guarded_ctx(ctx, [&]() {
+    ctx->require_initial_values();
+    return dispatch_initial_values(ctx, [&](auto tag) {
+      ctx->template prepare_state_vector<typename decltype(tag)::type>(handle, nullptr,
+                                                                       ryujin_hip_ctx::IvStage{true, t, 0.});
+      return RYUJIN_OK;
+    });
+  });
+}
+
+int ryujin_hip_time_step_iv(ryujin_hip_ctx *ctx, int scheme, int h_state, int n_tmp, const int *h_tmp, double t,
+                            double tau_max, int cfl_recovery, double cfl_min, double cfl_max, double *tau_out)
+{
+  return guarded_ctx(ctx, [&]() {
+    ctx->require_initial_values();
+    if (!h_tmp || !tau_out || n_tmp < 1 || n_tmp > 8)
+      throw HipError(RYUJIN_ERR_ARG, "time_step: bad argument");
+    if (std::isnan(tau_max) || !(tau_max > 0.))
+      return RYUJIN_ERR_TAU; /* as in step() */
+    ctx->state(h_state);
+    for (int q = 0; q < n_tmp; ++q) {
+      ctx->state(h_tmp[q]);
+      if (h_tmp[q] == h_state)
+        throw HipError(RYUJIN_ERR_ARG, "time_step: temporary vectors must differ from the state vector");
+      for (int r = 0; r < q; ++r)
+        if (h_tmp[r] == h_tmp[q])
+          throw HipError(RYUJIN_ERR_ARG, "time_step: temporary vectors must be distinct");
+    }
+    return dispatch_initial_values(ctx, [&](auto tag) {
+      return ctx->template time_step<typename decltype(tag)::type>(scheme, h_state, n_tmp, h_tmp, nullptr, tau_max,
+                                                                   cfl_recovery, cfl_min, cfl_max, tau_out, t,
+                                                                   nullptr, nullptr, true);
+    });
   });
 }
 

@@ -51,6 +51,22 @@ def euler_isentropic_vortex(positions, t, mach=1.0, beta=5.0, gamma=1.4, directi
     """initial_state_isentropic_vortex.h:54-92 composed with the affine transform of
     initial_values.template.h:66-148 (translate by `position`, rotate onto `direction`)."""
     n, dim = positions.shape
+    rho, u, v, p, (nx, ny) = euler_isentropic_vortex_primitive(positions, t, mach, beta, gamma, direction, position)
+    E = p / (gamma - 1.0) + 0.5 * rho * (u * u + v * v)
+    # affine_transform_vector: rotate the momentum into the lab frame
+    mx, my = rho * u, rho * v
+    U = np.zeros((n, dim + 2))
+    U[:, 0] = rho
+    U[:, 1] = nx * mx - ny * my
+    U[:, 2] = ny * mx + nx * my
+    U[:, -1] = E
+    return U
+
+
+def euler_isentropic_vortex_primitive(positions, t, mach=1.0, beta=5.0, gamma=1.4, direction=(1.0, 1.0),
+                                      position=(-1.0, -1.0)):
+    """The primitive state of euler_isentropic_vortex in the vortex frame: (rho, u, v, p, (nx, ny)) with (nx, ny) the
+    normalised direction the velocity is rotated back with."""
     d = np.asarray(direction, dtype=np.float64)
     d = d / np.linalg.norm(d)
     nx, ny = d[0], d[1]
@@ -68,15 +84,7 @@ def euler_isentropic_vortex(positions, t, mach=1.0, beta=5.0, gamma=1.4, directi
     v = factor * xb
     rho = T ** (1.0 / (gamma - 1.0))
     p = rho ** gamma
-    E = p / (gamma - 1.0) + 0.5 * rho * (u * u + v * v)
-    # affine_transform_vector: rotate the momentum into the lab frame
-    mx, my = rho * u, rho * v
-    U = np.zeros((n, dim + 2))
-    U[:, 0] = rho
-    U[:, 1] = nx * mx - ny * my
-    U[:, 2] = ny * mx + nx * my
-    U[:, -1] = E
-    return U
+    return rho, u, v, p, (nx, ny)
 
 
 def sw_circular_dam_break(positions, h_inner=2.5, h_outer=0.5, radius=2.5):
@@ -129,6 +137,16 @@ def aeos_from_primitive(params, rho, vel, p):
 def euler_leblanc(positions, t, position=0.0):
     """source/euler/initial_state_leblanc.h:63-120: the Le Blanc shock tube (gamma = 5/3), conserved
     1-D states (rho, m, E) of the exact Riemann fan at time t."""
+    rho, u, p = euler_leblanc_primitive(positions, t, position)
+    U = np.empty((rho.size, 3))
+    U[:, 0] = rho
+    U[:, 1] = rho * u
+    U[:, 2] = p / (5.0 / 3.0 - 1.0) + 0.5 * rho * u * u
+    return U
+
+
+def euler_leblanc_primitive(positions, t, position=0.0):
+    """The primitive 1-D states (rho, u, p) of euler_leblanc."""
     x = np.asarray(positions, dtype=np.float64)[:, 0] - position
     rarefaction_speed = 0.49578489518897934
     contact_velocity = 0.62183867139173454
@@ -151,16 +169,22 @@ def euler_leblanc(positions, t, position=0.0):
     p[fan] = (1.0 / 15.0) * np.power(0.75 - 0.75 * chi[fan], 5.0)
     rho[pre], u[pre], p[pre] = pre_contact_density, contact_velocity, contact_pressure
     rho[post], u[post], p[post] = post_contact_density, contact_velocity, contact_pressure
-    U = np.empty((x.size, 3))
-    U[:, 0] = rho
-    U[:, 1] = rho * u
-    U[:, 2] = p / (5.0 / 3.0 - 1.0) + 0.5 * rho * u * u
-    return U
+    return rho, u, p
 
 
 def euler_rarefaction(positions, t, gamma=1.4, position=0.0):
     """source/euler/initial_state_rarefaction.h:40-160: a single 1-rarefaction that has been running
     for t_0 = 0.2 / (u_R - u_L) already; conserved 1-D states at time t_0 + t."""
+    rho, u, p = euler_rarefaction_primitive(positions, t, gamma, position)
+    U = np.empty((rho.size, 3))
+    U[:, 0] = rho
+    U[:, 1] = rho * u
+    U[:, 2] = p / (gamma - 1.0) + 0.5 * rho * u * u
+    return U
+
+
+def euler_rarefaction_primitive(positions, t, gamma=1.4, position=0.0):
+    """The primitive 1-D states (rho, u, p) of euler_rarefaction."""
     x = np.asarray(positions, dtype=np.float64)[:, 0] - position
     rho_l, p_l = 3.0, 1.0
     c_l = np.sqrt(gamma * p_l / rho_l)
@@ -186,11 +210,7 @@ def euler_rarefaction(positions, t, gamma=1.4, position=0.0):
     rho[fan] = rho_l * np.power(base, density_exponent)
     u[fan] = k1 * (k3 + chi[fan])
     p[fan] = p_l * np.power(base, pressure_exponent)
-    U = np.empty((x.size, 3))
-    U[:, 0] = rho
-    U[:, 1] = rho * u
-    U[:, 2] = p / (gamma - 1.0) + 0.5 * rho * u * u
-    return U
+    return rho, u, p
 
 
 def sw_paraboloid_1d(positions, t, gravity=9.81, manning=0.0, free_surface_radius=3000.0,

@@ -126,7 +126,14 @@ class HyperbolicModule:
             sv.upload(U)
         return sv
 
-    def prepare_state_vector(self, state: StateVector, t: float, dirichlet: np.ndarray | None = None):
+    def prepare_state_vector(self, state: StateVector, t: float, dirichlet: np.ndarray | str | None = None):
+        """dirichlet: [n_bdry, k] values of initial_state(position, t), None, or "device": evaluated by the library
+        from the configured analytic state (initial_values_configure; ryujin_hip_prepare_state_vector_iv)."""
+        if isinstance(dirichlet, str):
+            if dirichlet != "device":
+                raise ValueError(f"dirichlet={dirichlet!r}")
+            self._check(self._f("prepare_state_vector_iv")(self._ctx, state.handle, float(t)))
+            return
         ptr = None
         if dirichlet is not None:
             dirichlet = np.ascontiguousarray(dirichlet, dtype=np.float64)
@@ -160,6 +167,10 @@ class HyperbolicModule:
         (ryujin_hip_time_step_fn)."""
         if dirichlet_fn is not None:
             return self._time_step_fn(scheme, state, temps, t, dirichlet_fn, tau_max, cfl_recovery, cfl_min, cfl_max)
+        if isinstance(dirichlet, str):
+            if dirichlet != "device":
+                raise ValueError(f"dirichlet={dirichlet!r}")
+            return self._time_step_iv(scheme, state, temps, t, tau_max, cfl_recovery, cfl_min, cfl_max)
         schemes = {"ssprk 22": capi.SCHEME_SSPRK_22, "ssprk 33": capi.SCHEME_SSPRK_33,
                    "erk 11": capi.SCHEME_ERK_11, "erk 22": capi.SCHEME_ERK_22, "erk 33": capi.SCHEME_ERK_33,
                    "erk 43": capi.SCHEME_ERK_43, "erk 54": capi.SCHEME_ERK_54}
@@ -223,6 +234,51 @@ class HyperbolicModule:
         if rc == capi.RYUJIN_RESTART:
             raise Restart()
         return tau.value
+
+    def _time_step_iv(self, scheme, state, temps, t, tau_max, cfl_recovery, cfl_min, cfl_max):
+        """ryujin_hip_time_step_iv: the Dirichlet data of every stage evaluated on the device at t + c_s tau"""
+        hs = (C.c_int * len(temps))(*[x.handle for x in temps])
+        tau = C.c_double(0.0)
+        rc = self._f("time_step_iv")(self._ctx, self.SCHEMES[scheme], state.handle, len(temps), hs, float(t),
+                                     float(np.finfo(np.float64).max if tau_max is None else tau_max),
+                                     capi.CFL_RECOVERY_BANG_BANG if cfl_recovery == "bang bang control"
+                                     else capi.CFL_RECOVERY_NONE, float(cfl_min), float(cfl_max), C.byref(tau))
+        if rc == capi.RYUJIN_ERR_TAU:
+            raise TauError("I'm sorry, Dave. I'm afraid I can't do that. We crashed.")
+        self._check(rc)
+        self.last_status = rc
+        if rc == capi.RYUJIN_RESTART:
+            raise Restart()
+        return tau.value
+
+    # ------------------------------------------------------------------ InitialValues (device backend only)
+    def initial_values_configure(self, name: str, *, direction=None, position=None, perturbation: float = 0.0,
+                                 **params) -> None:
+        """Select the analytic state of subsection "E - InitialValues" (ryujin_hip_initial_values_configure):
+        `name` and the parameter names are the reference's ("isentropic vortex", mach_number=1.0 for "mach number");
+        the node and boundary positions come from the offline data. A second call replaces the first."""
+        iv = capi.initial_values_struct(name, self.dim, direction, position, perturbation, **params)
+        pos = np.ascontiguousarray(self.offline.positions, dtype=np.float64).reshape(-1)
+        assert pos.size == self.n_relevant * self.dim
+        bpos = np.ascontiguousarray(self.offline.b_positions, dtype=np.float64).reshape(-1) \
+            if self.offline.n_bdry else np.zeros(0)
+        assert bpos.size == self.offline.n_bdry * self.dim
+        self._check(self._f("initial_values_configure")(
+            self._ctx, C.byref(iv), capi.as_ptr(pos, capi.c_double_p) if pos.size else None,
+            capi.as_ptr(bpos, capi.c_double_p) if bpos.size else None))
+
+    def initial_values_evaluate(self, points, t: float) -> np.ndarray:
+        """[n, k]: initial_state(points[n, dim], t) of the configured state, evaluated on the device"""
+        points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, self.dim)
+        out = np.zeros((points.shape[0], self.k), dtype=np.float64)
+        self._check(self._f("initial_values_evaluate")(
+            self._ctx, capi.as_ptr(points, capi.c_double_p) if points.size else None, points.shape[0], float(t),
+            capi.as_ptr(out, capi.c_double_p) if out.size else None))
+        return out
+
+    def initial_values_interpolate(self, state: StateVector, t: float) -> None:
+        """InitialValues::interpolate_hyperbolic_vector(t) into `state`, ghost rows included (an enqueue)"""
+        self._check(self._f("initial_values_interpolate")(self._ctx, state.handle, float(t)))
 
     def integrals(self, state: StateVector) -> np.ndarray:
         """sum_i m_i U_i over the owned DoFs of all ranks, computed on the device with a fixed
@@ -445,17 +501,21 @@ class DeviceResidentTimeIntegrator:
     the stage times by a callback (what contrib/hyperbolic_module_hip.h::time_step does on the ryujin side)."""
 
     def __init__(self, module: "HyperbolicModule", scheme: str = "erk 33", cfl_min=0.45, cfl_max=0.90,
-                 cfl_recovery_strategy: str = "bang bang control", dirichlet_fn=None):
+                 cfl_recovery_strategy: str = "bang bang control", dirichlet_fn=None, dirichlet=None):
+        """dirichlet="device": the Dirichlet data of every stage is evaluated on the device from the analytic state
+        of module.initial_values_configure (ryujin_hip_time_step_iv) instead of through dirichlet_fn."""
         self.m, self.scheme = module, scheme
         self.cfl_min, self.cfl_max, self.cfl_recovery_strategy = cfl_min, cfl_max, cfl_recovery_strategy
-        self.dirichlet_fn = dirichlet_fn
+        if dirichlet is not None and (dirichlet != "device" or dirichlet_fn is not None):
+            raise ValueError("dirichlet is \"device\" or None, and excludes dirichlet_fn")
+        self.dirichlet_fn, self.dirichlet = dirichlet_fn, dirichlet
         self.temp = [module.new_state_vector() for _ in range({"erk 43": 4, "erk 54": 5}.get(scheme, 3))]
         module.cfl = cfl_max
 
     def step(self, state: StateVector, t: float, t_final: float = np.finfo(np.float64).max):
         tau = self.m.time_step(self.scheme, state, self.temp, tau_max=t_final - t,
                                cfl_recovery=self.cfl_recovery_strategy, cfl_min=self.cfl_min, cfl_max=self.cfl_max,
-                               t=t, dirichlet_fn=self.dirichlet_fn)
+                               t=t, dirichlet_fn=self.dirichlet_fn, dirichlet=self.dirichlet)
         return state, tau
 
 
