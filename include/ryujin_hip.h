@@ -733,6 +733,52 @@ int ryujin_hip_prepare_state_vector_iv(ryujin_hip_ctx *ctx, int handle, double t
 int ryujin_hip_time_step_iv(ryujin_hip_ctx *ctx, int scheme, int h_state, int n_tmp, const int *h_tmp, double t,
                             double tau_max, int cfl_recovery, double cfl_min, double cfl_max, double *tau_out);
 
+/* ---- Error norms: analytic-solution error of a verification run, device resident -- */
+/* The norms of TimeLoop::compute_error() of the reference (source/time_loop.template.h:692-833) between the state
+ * vector behind h_state (U) and the analytic vector behind h_analytic (A), e = U - A per node, for a list of
+ * components of the conserved state. ryujin_hip_offline carries no cells, so the CELLS are an input of their own:
+ *   configure   n_cells cells of this rank with dofs_per_cell local indices each (< n_relevant: a cell may reach into
+ *               the ghost range), cell_dofs [n_cells][dofs_per_cell]; a quadrature of n_q points given by the TABLE
+ *               shape [n_q][dofs_per_cell] = phi_v(x_q) on the reference cell, so that one kernel serves Q1 in 1-D,
+ *               2-D and 3-D, Q2 stencils and a dG numbering with any quadrature (Q1 with QGauss(3) -- 2 x 3, 4 x 9,
+ *               8 x 27 -- runs out of registers, any other table through run-time loops); and JxW in one of two forms:
+ *                 jxw_per_cell == 0   jxw [n_cells][n_q]: |det J(x_q)| w_q, general non-affine cells; weights unused
+ *                                     (may be NULL)
+ *                 jxw_per_cell != 0   jxw [n_cells]: the cell measure, JxW_q = weights[q] * jxw[cell] with the weights
+ *                                     [n_q] of the reference cell (sum 1): affine cells
+ *               Every cell belongs to exactly ONE rank (the reference: locally owned cells); a rank with n_cells == 0
+ *               is legal and launches nothing. Everything is copied; a second configure replaces the first, a refused
+ *               one leaves the previous configuration in place.
+ *   compute     detail [n_components][6] (may be NULL) = (Linf, L1, L2 of e; Linf, L1, L2 of A) of component
+ *               components[c], over ALL ranks:
+ *                 Linf = max |x_i| over the owned rows (:740, :774)
+ *                 L1   = sum_cells sum_q |sum_v N_qv x_v| JxW_q,  L2 = sqrt(sum_cells sum_q (sum_v N_qv x_v)^2 JxW_q)
+ *               (integrate_difference against the zero function, :743-795; the root behind the sum over the ranks), and
+ *               out [3] the consolidated (Linf, L1, L2) of :797-805: with normalize != 0 the sum over the components, in
+ *               the given order, of the ratios error norm / analytic norm, without it the sum of the error norms. A
+ *               component whose analytic norm is zero gives the reference's IEEE result (x / 0 = inf, 0 / 0 = NaN), and
+ *               the consolidated sum inherits it; it is not an error.
+ *               Collective over the ranks of the context's communicator: it exchanges the ghost range of h_state as
+ *               ryujin_hip_postprocess_compute does, and reads h_analytic AS IT IS (initial_values_interpolate fills
+ *               its ghost rows, an uploaded vector carries them). Over the ranks the integrals are summed and the
+ *               maxima taken the way Quantities reduces (in-process transport, RCCL). The sums are formed in a fixed
+ *               order (no floating-point atomics): reproducible bit for bit for a given partition. The call itself
+ *               runs no prepare_state_vector (:701): the caller does, as for a step. It returns the numbers, so it
+ *               waits for the stream -- the one copy to the host is 33 doubles.
+ * ryujin_hip_offline carries no affine constraints, so AffineConstraints::distribute (:770) has no counterpart here.
+ * RYUJIN_ERR_ARG: compute before configure, an index >= n_relevant, dofs_per_cell outside
+ * [2, RYUJIN_EN_MAX_DOFS_PER_CELL], n_q outside [1, RYUJIN_EN_MAX_POINTS], a non-finite shape, weights or jxw entry,
+ * weights == NULL with jxw_per_cell != 0, NULL arrays with n_cells > 0 (shape: always), a component outside [0, k),
+ * n_components outside [1, k], an unknown handle. */
+#define RYUJIN_EN_MAX_DOFS_PER_CELL 27
+#define RYUJIN_EN_MAX_POINTS 64
+#define RYUJIN_EN_MAX_COMPONENTS 5
+int ryujin_hip_error_norms_configure(ryujin_hip_ctx *ctx, uint32_t n_cells, int dofs_per_cell,
+                                     const uint32_t *cell_dofs, int n_q, const double *shape, const double *weights,
+                                     const double *jxw, int jxw_per_cell);
+int ryujin_hip_error_norms_compute(ryujin_hip_ctx *ctx, int h_state, int h_analytic, int n_components,
+                                   const int *components, int normalize, double out[3], double *detail);
+
 #ifdef __cplusplus
 }
 #endif

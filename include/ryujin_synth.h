@@ -53,6 +53,12 @@ const double *ryujin_synth_bdry_positions(const ryujin_synth *s); /* [n_bdry*dim
 /* [n_bdry] boundary mass of every boundary_map entry (offline_data.template.h:1246-1361: the face integrals of phi_i,
  * summed over the faces merged into the entry): the weights of the boundary maps of Quantities */
 const double *ryujin_synth_bdry_mass(const ryujin_synth *s);
+/* The cells of this rank for ryujin_hip_error_norms_configure: the lattice cells that survive the cut-out,
+ * [n_cells][2^dim] local indices with the vertices in deal.II's lexicographic order v = ix + 2 iy + 4 iz. A cell
+ * belongs to the rank that owns its vertex of smallest global id; all its other vertices are stencil neighbours of
+ * that node, so every index lies in [0, n_relevant). All cells have the measure prod_d h_d. */
+uint64_t ryujin_synth_n_cells(const ryujin_synth *s);
+const uint32_t *ryujin_synth_cells(const ryujin_synth *s);
 
 /* exported instance of ryujin_ghost_row_send_entries() (include/ryujin_exchange_lists.h): the ghost-row
  * send-list rule of sparse_matrix_simd.template.h:196-264, the function the generator itself calls; bound by

@@ -102,6 +102,7 @@ PP_MAX_QUANTITIES = 8
 Q_INSTANTANEOUS, Q_TIME_AVERAGED, Q_SPACE_AVERAGED = 1, 2, 4
 Q_MAX_MANIFOLDS = 16
 Q_NONE_YET = 3
+EN_MAX_DOFS_PER_CELL, EN_MAX_POINTS, EN_MAX_COMPONENTS = 27, 64, 5
 
 
 class PostprocessQuantity(C.Structure):
@@ -238,6 +239,10 @@ def load_synth():
         lib.ryujin_synth_bdry_positions.argtypes = [C.c_void_p]
         lib.ryujin_synth_bdry_mass.restype = c_double_p
         lib.ryujin_synth_bdry_mass.argtypes = [C.c_void_p]
+        lib.ryujin_synth_n_cells.restype = C.c_uint64
+        lib.ryujin_synth_n_cells.argtypes = [C.c_void_p]
+        lib.ryujin_synth_cells.restype = c_u32_p
+        lib.ryujin_synth_cells.argtypes = [C.c_void_p]
         lib.ryujin_synth_ghost_row_send_entries.restype = C.c_size_t
         lib.ryujin_synth_ghost_row_send_entries.argtypes = [c_u64_p, c_u32_p, c_u32_p, C.c_size_t, C.c_uint32,
                                                             C.c_uint32, c_u32_p, c_u32_p]
@@ -289,6 +294,7 @@ HIP_SYMBOLS = [
     "ryujin_hip_quantities_time_series",
     "ryujin_hip_initial_values_configure", "ryujin_hip_initial_values_evaluate",
     "ryujin_hip_initial_values_interpolate", "ryujin_hip_prepare_state_vector_iv", "ryujin_hip_time_step_iv",
+    "ryujin_hip_error_norms_configure", "ryujin_hip_error_norms_compute",
 ]
 
 
@@ -393,5 +399,9 @@ def load_hip():
         lib.ryujin_hip_prepare_state_vector_iv.argtypes = [vp, C.c_int, C.c_double]
         lib.ryujin_hip_time_step_iv.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int_p, C.c_double, C.c_double,
                                                 C.c_int, C.c_double, C.c_double, c_double_p]
+        lib.ryujin_hip_error_norms_configure.argtypes = [vp, C.c_uint32, C.c_int, c_u32_p, C.c_int, c_double_p,
+                                                         c_double_p, c_double_p, C.c_int]
+        lib.ryujin_hip_error_norms_compute.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int_p, C.c_int, c_double_p,
+                                                       c_double_p]
         _hip = lib
     return _hip

@@ -67,6 +67,7 @@ struct ryujin_synth {
   std::vector<uint32_t> row_send_off, row_send_row, row_send_col;
   std::vector<double> positions;
   std::vector<uint64_t> global_ids;
+  std::vector<uint32_t> cells; /* [n_cells][2^dim] local indices, vertex v = ix + 2 iy + 4 iz */
   uint64_t n_global = 0;
 
   /* ---- geometry predicates --------------------------------------------- */
@@ -482,6 +483,20 @@ bool ryujin_synth::build()
     }
   }
 
+  /* ---- cells ---------------------------------------------------------------
+   * The active cells whose vertex of smallest global id -- the lower corner (cx, cy, cz) -- this rank owns: every
+   * cell on exactly one rank. The other vertices are stencil neighbours of that node: locally relevant. */
+
+  cells.clear();
+  for (int64_t cz = 0; cz < nc[2]; ++cz)
+    for (int64_t cy = 0; cy < nc[1]; ++cy)
+      for (int64_t cx = x0; cx < std::min<int64_t>(x1, nc[0]); ++cx) {
+        if (!cell_active(cx, cy, cz))
+          continue;
+        for (int v = 0; v < (1 << dim); ++v)
+          cells.push_back(local_id(cx + (v & 1), cy + ((v >> 1) & 1), cz + ((v >> 2) & 1)));
+      }
+
   /* ---- boundary map -------------------------------------------------------
    * Face contributions collected cell by cell (x fastest) and face by face
    * (-x,+x,-y,+y,-z,+z), then merged per node exactly as the reference's
@@ -750,6 +765,16 @@ const double *ryujin_synth_bdry_positions(const ryujin_synth *s)
 const double *ryujin_synth_bdry_mass(const ryujin_synth *s)
 {
   return s->b_mass.data();
+}
+
+uint64_t ryujin_synth_n_cells(const ryujin_synth *s)
+{
+  return s->cells.size() >> s->dim;
+}
+
+const uint32_t *ryujin_synth_cells(const ryujin_synth *s)
+{
+  return s->cells.data();
 }
 
 size_t ryujin_synth_ghost_row_send_entries(const uint64_t *row_starts, const uint32_t *columns,

@@ -49,6 +49,7 @@
 #include "kernels_postprocessor.hpp"
 #include "kernels_quantities.hpp"
 #include "kernels_initial_values.hpp"
+#include "kernels_error_norms.hpp"
 
 using namespace ryujin_hip;
 
@@ -300,6 +301,8 @@ struct LocalGroup {
   std::vector<double> scratch_vec;                          /* [n_ranks][8] vector sums (host) */
   static constexpr int kQuantitiesRow = 12;                 /* >= 1 + 2 K, K <= 5 */
   std::vector<double> scratch_quantities;                   /* [n_ranks][kQuantitiesRow] sums of a manifold (host) */
+  static constexpr int kErrorNormsRow = 32;                 /* >= kErrorNormsSums + 2 kErrorNormsMaxComponents */
+  std::vector<double> scratch_error_norms;                  /* [n_ranks][kErrorNormsRow] sums, then maxima (host) */
   int refs = 0;
   int device = 0;
   bool aborted = false; /* a rank failed: the others must not wait for it (guarded_ctx sets it) */
@@ -320,6 +323,7 @@ struct LocalGroup {
       , mail(n, std::vector<const double *>(n, nullptr))
       , scratch_vec((size_t)n * 8, 0.)
       , scratch_quantities((size_t)n * kQuantitiesRow, 0.)
+      , scratch_error_norms((size_t)n * kErrorNormsRow, 0.)
       , device(dev)
   {
     HIP_CHECK(hipSetDevice(dev));
@@ -507,6 +511,17 @@ struct ryujin_hip_ctx {
   }
   template <typename E>
   void quantities_evaluate(Manifold &m, int h, bool accumulate, double t);
+  /* Error norms (ryujin_hip_error_norms_*, kernels_error_norms.hpp): the cells of this rank, transposed */
+  struct ErrorNorms {
+    uint32_t n_cells = 0, n_blocks = 0;
+    int dofs_per_cell = 0, n_q = 0, jxw_per_cell = 0;
+    DeviceBuffer<uint32_t> d_cell_dofs; /* [dofs_per_cell][n_cells] */
+    DeviceBuffer<double> d_jxw;         /* [n_q][n_cells], or [n_cells] with jxw_per_cell */
+    DeviceBuffer<double> d_shape, d_weights;
+    DeviceBuffer<double> d_work; /* [n_blocks][kErrorNormsSums] partials, the sums, the maxima (bits), the result */
+  };
+  std::unique_ptr<ErrorNorms> error_norms;
+  void error_norms_compute(int h_state, int h_analytic, const ErrorNormsDesc &D, double *host_result);
   /* time-dependent Dirichlet data inside a device-resident RK step (ryujin_hip_time_step_fn): the tau of the
    * first stage is copied to the host as soon as it exists (behind step 3 of the first stage), the later stages'
    * boundary data is evaluated at t + c_s tau while the rest of the first stage runs */
@@ -2392,6 +2407,93 @@ void ryujin_hip_ctx::quantities_evaluate(Manifold &m, int h, bool accumulate, do
   ++m.n_rows;
 }
 
+/* TimeLoop::compute_error() (source/time_loop.template.h:692-833) behind prepare_state_vector and the analytic
+ * vector: ghost exchange of the state vector (the cells of this rank reach into the ghost range), the nodal maxima,
+ * the cell integrals, both reduced over the ranks, then roots, ratios and the consolidated sums on the device. The
+ * result row is the one copy to the host. */
+void ryujin_hip_ctx::error_norms_compute(int h_state, int h_analytic, const ErrorNormsDesc &D, double *host_result)
+{
+  constexpr int NS = kErrorNormsSums, MAXC = kErrorNormsMaxComponents;
+  static_assert(NS + 2 * MAXC <= LocalGroup::kErrorNormsRow, "LocalGroup::scratch_error_norms holds a row per rank");
+  ErrorNorms &en = *error_norms;
+  State &s = state(h_state);
+  State &a = state(h_analytic);
+  wait_comm();
+  exchange_vector(s.U.ptr, KP, false);
+  wait_comm();
+
+  double *partial = en.d_work.ptr;
+  double *sums = partial + (size_t)en.n_blocks * NS;
+  unsigned long long *max_bits = reinterpret_cast<unsigned long long *>(sums + NS);
+  double *result = sums + NS + 2 * MAXC;
+  HIP_CHECK(hipMemsetAsync(max_bits, 0, sizeof(unsigned long long) * 2 * MAXC, stream)); /* max |.| starts from 0 */
+  if (L.n_owned > 0) {
+    const uint32_t blocks = (uint32_t)std::min<size_t>(kErrorNormsMaxBlocks, ((size_t)L.n_owned + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_error_norms_nodal, dim3(blocks), dim3(kBlock), 0, stream, L.n_owned, D, s.U.ptr, a.U.ptr,
+                       max_bits);
+    HIP_CHECK(hipGetLastError());
+  }
+  if (en.n_cells > 0) { /* (no zero-sized grid) */
+    ErrorNormsCells C{};
+    C.n_cells = en.n_cells;
+    C.dofs_per_cell = en.dofs_per_cell;
+    C.n_q = en.n_q;
+    C.jxw_per_cell = en.jxw_per_cell;
+    C.cell_dofs = en.d_cell_dofs.ptr;
+    C.jxw = en.d_jxw.ptr;
+    C.shape = en.d_shape.ptr;
+    C.weights = en.d_weights.ptr;
+    C.partial = partial;
+    const dim3 grid(en.n_blocks), block(kBlock);
+    if (en.dofs_per_cell == 2 && en.n_q == 3)
+      hipLaunchKernelGGL((k_error_norms_cells<2, 3>), grid, block, 0, stream, D, C, s.U.ptr, a.U.ptr);
+    else if (en.dofs_per_cell == 4 && en.n_q == 9)
+      hipLaunchKernelGGL((k_error_norms_cells<4, 9>), grid, block, 0, stream, D, C, s.U.ptr, a.U.ptr);
+    else if (en.dofs_per_cell == 8 && en.n_q == 27)
+      hipLaunchKernelGGL((k_error_norms_cells<8, 27>), grid, block, 0, stream, D, C, s.U.ptr, a.U.ptr);
+    else
+      hipLaunchKernelGGL((k_error_norms_cells<0, 0>), grid, block, 0, stream, D, C, s.U.ptr, a.U.ptr);
+    HIP_CHECK(hipGetLastError());
+  }
+  const bool several_ranks = comm && comm->n_ranks > 1 && !(comm->local && comm->local->loopback);
+  hipLaunchKernelGGL(k_error_norms_final, dim3(1), dim3(64), 0, stream, D, en.n_blocks, partial, sums, max_bits,
+                     several_ranks ? nullptr : result);
+  HIP_CHECK(hipGetLastError());
+  if (several_ranks) {
+    double *maxima = reinterpret_cast<double *>(max_bits); /* bit patterns of non-negative doubles: reduced as doubles */
+    if (!comm->local) {
+      ++n_allreduces;
+      NCCL_CHECK(ncclAllReduce(sums, sums, NS, ncclDouble, ncclSum, comm->comm, stream));
+      NCCL_CHECK(ncclAllReduce(maxima, maxima, 2 * MAXC, ncclDouble, ncclMax, comm->comm, stream));
+    } else {
+      /* in-process transport: host rendezvous, as ryujin_hip_state_integrals; the ranks in order on every rank */
+      LocalGroup &g = *comm->local;
+      constexpr int ROW = LocalGroup::kErrorNormsRow;
+      double host[NS + 2 * MAXC];
+      HIP_CHECK(hipMemcpyAsync(host, sums, sizeof(host), hipMemcpyDeviceToHost, stream));
+      HIP_CHECK(hipStreamSynchronize(stream));
+      for (int q = 0; q < NS + 2 * MAXC; ++q)
+        g.scratch_error_norms[(size_t)comm->rank * ROW + q] = host[q];
+      g.barrier();
+      for (int q = 0; q < NS + 2 * MAXC; ++q) {
+        double v = g.scratch_error_norms[q];
+        for (int r = 1; r < g.n_ranks; ++r) {
+          const double w = g.scratch_error_norms[(size_t)r * ROW + q];
+          v = q < NS ? v + w : std::max(v, w);
+        }
+        host[q] = v;
+      }
+      g.barrier();
+      HIP_CHECK(hipMemcpyAsync(sums, host, sizeof(host), hipMemcpyHostToDevice, stream));
+      HIP_CHECK(hipStreamSynchronize(stream)); /* host[] goes out of scope */
+    }
+    hipLaunchKernelGGL(k_error_norms_result, dim3(1), dim3(64), 0, stream, D, sums, max_bits, result);
+    HIP_CHECK(hipGetLastError());
+  }
+  HIP_CHECK(hipMemcpyAsync(host_result, result, sizeof(double) * kErrorNormsResult, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+}
+
 /* ============================================================================ C ABI */
 
 namespace
@@ -4092,6 +4194,118 @@ int ryujin_hip_time_step_iv(ryujin_hip_ctx *ctx, int scheme, int h_state, int n_
                                                                    cfl_recovery, cfl_min, cfl_max, tau_out, t,
                                                                    nullptr, nullptr, true);
     });
+  });
+}
+
+} /* extern "C" */
+
+/* ---- Error norms --------------------------------------------------------- */
+
+extern "C" {
+
+int ryujin_hip_error_norms_configure(ryujin_hip_ctx *ctx, uint32_t n_cells, int dofs_per_cell,
+                                     const uint32_t *cell_dofs, int n_q, const double *shape, const double *weights,
+                                     const double *jxw, int jxw_per_cell)
+{
+  return guarded_ctx(ctx, [&]() {
+    static_assert(RYUJIN_EN_MAX_DOFS_PER_CELL == kErrorNormsMaxDofs && RYUJIN_EN_MAX_POINTS == kErrorNormsMaxPoints,
+                  "header and kernels agree");
+    if (dofs_per_cell < 2 || dofs_per_cell > kErrorNormsMaxDofs)
+      throw HipError(RYUJIN_ERR_ARG, "error_norms_configure: dofs_per_cell " + std::to_string(dofs_per_cell) +
+                                         " outside [2, " + std::to_string(kErrorNormsMaxDofs) + "]");
+    if (n_q < 1 || n_q > kErrorNormsMaxPoints)
+      throw HipError(RYUJIN_ERR_ARG, "error_norms_configure: n_q " + std::to_string(n_q) + " outside [1, " +
+                                         std::to_string(kErrorNormsMaxPoints) + "]");
+    if (!shape)
+      throw HipError(RYUJIN_ERR_ARG, "error_norms_configure: null shape table");
+    if (jxw_per_cell && !weights)
+      throw HipError(RYUJIN_ERR_ARG, "error_norms_configure: null weights with jxw_per_cell");
+    if (n_cells > 0 && (!cell_dofs || !jxw))
+      throw HipError(RYUJIN_ERR_ARG, "error_norms_configure: null cell_dofs or jxw with n_cells > 0");
+    const size_t n = n_cells, dpc = (size_t)dofs_per_cell, nq = (size_t)n_q;
+    for (size_t e = 0; e < nq * dpc; ++e)
+      if (!std::isfinite(shape[e]))
+        throw HipError(RYUJIN_ERR_ARG, "error_norms_configure: shape value " + std::to_string(e) + " is not finite");
+    if (weights)
+      for (size_t q = 0; q < nq; ++q)
+        if (!std::isfinite(weights[q]))
+          throw HipError(RYUJIN_ERR_ARG, "error_norms_configure: weights entry " + std::to_string(q) + " is not finite");
+    const size_t n_jxw = jxw_per_cell ? n : n * nq;
+    for (size_t e = 0; e < n_jxw; ++e)
+      if (!std::isfinite(jxw[e]))
+        throw HipError(RYUJIN_ERR_ARG, "error_norms_configure: jxw entry " + std::to_string(e) + " is not finite");
+    const uint32_t n_relevant = ctx->L.n_relevant;
+    for (size_t e = 0; e < n * dpc; ++e)
+      if (cell_dofs[e] >= n_relevant)
+        throw HipError(RYUJIN_ERR_ARG, "error_norms_configure: index " + std::to_string(cell_dofs[e]) + " of cell " +
+                                           std::to_string(e / dpc) + " is not below n_relevant = " +
+                                           std::to_string(n_relevant));
+    /* both cell streams transposed: lane = cell reads them coalesced */
+    std::vector<uint32_t> dofs_t(n * dpc);
+    for (size_t c = 0; c < n; ++c)
+      for (size_t v = 0; v < dpc; ++v)
+        dofs_t[v * n + c] = cell_dofs[c * dpc + v];
+    std::vector<double> jxw_t(n_jxw);
+    if (jxw_per_cell)
+      std::copy(jxw, jxw + n, jxw_t.begin());
+    else
+      for (size_t c = 0; c < n; ++c)
+        for (size_t q = 0; q < nq; ++q)
+          jxw_t[q * n + c] = jxw[c * nq + q];
+    std::vector<double> w(nq, 0.);
+    if (weights)
+      std::copy(weights, weights + nq, w.begin());
+    auto en = std::make_unique<ryujin_hip_ctx::ErrorNorms>();
+    en->n_cells = n_cells;
+    en->n_blocks = (uint32_t)std::min<size_t>(kErrorNormsMaxBlocks, (n + kBlock - 1) / kBlock);
+    en->dofs_per_cell = dofs_per_cell;
+    en->n_q = n_q;
+    en->jxw_per_cell = jxw_per_cell ? 1 : 0;
+    en->d_cell_dofs.upload(dofs_t);
+    en->d_jxw.upload(jxw_t);
+    en->d_shape.upload(shape, nq * dpc);
+    en->d_weights.upload(w);
+    en->d_work.alloc((size_t)en->n_blocks * kErrorNormsSums + kErrorNormsSums + 2 * kErrorNormsMaxComponents +
+                     kErrorNormsResult);
+    /* a second configure replaces the first: nothing enqueued may still read the old arrays */
+    ctx->finish();
+    ctx->error_norms = std::move(en);
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_error_norms_compute(ryujin_hip_ctx *ctx, int h_state, int h_analytic, int n_components,
+                                   const int *components, int normalize, double out[3], double *detail)
+{
+  return guarded_ctx(ctx, [&]() {
+    if (!ctx->error_norms)
+      throw HipError(RYUJIN_ERR_ARG, "error_norms_compute before error_norms_configure");
+    if (!components || !out)
+      throw HipError(RYUJIN_ERR_ARG, "error_norms_compute: null argument");
+    static_assert(RYUJIN_EN_MAX_COMPONENTS == kErrorNormsMaxComponents, "header and kernels agree");
+    if (n_components < 1 || n_components > ctx->K || n_components > kErrorNormsMaxComponents)
+      throw HipError(RYUJIN_ERR_ARG, "error_norms_compute: n_components " + std::to_string(n_components) +
+                                         " outside [1, " + std::to_string(ctx->K) + "]");
+    ErrorNormsDesc D{};
+    D.n = n_components;
+    D.stride = ctx->KP;
+    D.normalize = normalize ? 1 : 0;
+    for (int c = 0; c < n_components; ++c) {
+      if (components[c] < 0 || components[c] >= ctx->K)
+        throw HipError(RYUJIN_ERR_ARG, "error_norms_compute: component " + std::to_string(components[c]) +
+                                           " outside the state");
+      D.component[c] = components[c];
+    }
+    ctx->state(h_state);
+    ctx->state(h_analytic);
+    double host[kErrorNormsResult];
+    ctx->error_norms_compute(h_state, h_analytic, D, host);
+    for (int q = 0; q < 3; ++q)
+      out[q] = host[q];
+    if (detail)
+      for (int q = 0; q < 6 * n_components; ++q)
+        detail[q] = host[3 + q];
+    return RYUJIN_OK;
   });
 }
 

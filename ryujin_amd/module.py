@@ -347,6 +347,71 @@ class HyperbolicModule:
         self.postprocess_compute(state)
         return self.postprocess_download(raw)
 
+    # ------------------------------------------------------------------ error norms (device backend only)
+    def _require_device(self, what: str) -> None:
+        if self._prefix != "ryujin_hip_":
+            raise NotImplementedError(f"{what} is offered by the hip backend only")
+
+    def error_norms_configure(self, cells, shape, jxw, weights=None) -> None:
+        """The cells of this rank for compute_error() (ryujin_hip_error_norms_configure): cells [n_cells, dofs_per_cell]
+        local indices, shape [n_q, dofs_per_cell] the shape values at the quadrature points, and jxw either
+        [n_cells, n_q] (JxW per point) or [n_cells] (the cell measure; needs the weights [n_q] of the reference cell).
+        error_norms.q1_tables / q1_jxw give them for Q1 with QGauss(3). A second call replaces the first."""
+        self._require_device("error_norms_configure")
+        shape = np.ascontiguousarray(shape, dtype=np.float64)
+        if shape.ndim != 2:
+            raise ValueError("shape is [n_q, dofs_per_cell]")
+        n_q, dofs_per_cell = shape.shape
+        cells = np.ascontiguousarray(cells, dtype=np.uint32).reshape(-1, dofs_per_cell)
+        jxw = np.ascontiguousarray(jxw, dtype=np.float64)
+        per_cell = jxw.ndim == 1
+        if jxw.size != len(cells) * (1 if per_cell else n_q):
+            raise ValueError("jxw is [n_cells, n_q] or [n_cells]")
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+            if weights.size != n_q:
+                raise ValueError("weights is [n_q]")
+        self._check(self._f("error_norms_configure")(
+            self._ctx, len(cells), dofs_per_cell, capi.as_ptr(cells, capi.c_u32_p) if cells.size else None, n_q,
+            capi.as_ptr(shape, capi.c_double_p), capi.as_ptr(weights, capi.c_double_p) if weights is not None else None,
+            capi.as_ptr(jxw, capi.c_double_p) if jxw.size else None, int(per_cell)))
+
+    def error_norms_compute(self, state: StateVector, analytic: StateVector, components=None, normalize: bool = True):
+        """ryujin_hip_error_norms_compute: ((Linf, L1, L2) consolidated, detail [n_components, 6]); collective"""
+        self._require_device("error_norms_compute")
+        names = capi.component_names(self.equation, self.dim)[0]
+        if components is None:
+            components = names  # all of them (time_loop.template.h:170-173)
+        index = []
+        for name in components:
+            if name not in names:
+                raise ValueError(f"Unknown component name »{name}«")
+            index.append(names.index(name))
+        comp = (C.c_int * max(1, len(index)))(*index)
+        out = np.zeros(3, dtype=np.float64)
+        detail = np.zeros((max(1, len(index)), 6), dtype=np.float64)
+        self._check(self._f("error_norms_compute")(self._ctx, state.handle, analytic.handle, len(index), comp,
+                                                   int(bool(normalize)), capi.as_ptr(out, capi.c_double_p),
+                                                   capi.as_ptr(detail, capi.c_double_p)))
+        return (float(out[0]), float(out[1]), float(out[2])), detail[:len(index)]
+
+    def compute_error(self, state: StateVector, t: float, components=None, normalize: bool = True, analytic=None,
+                      dirichlet="device"):
+        """TimeLoop::compute_error() (source/time_loop.template.h:692-833) without leaving the device:
+        prepare_state_vector at t (dirichlet as in prepare_state_vector; "device": from the configured analytic
+        state), the analytic vector at t -- the given StateVector, or initial_values_interpolate into a scratch vector
+        the module keeps --, then the norms. Returns ((Linf, L1, L2) consolidated, detail [n_components, 6] =
+        (Linf, L1, L2 of U - A; Linf, L1, L2 of A) per component). Components by the names of the conserved state;
+        default: all of them."""
+        self._require_device("compute_error")
+        self.prepare_state_vector(state, t, dirichlet)
+        if analytic is None:
+            if getattr(self, "_en_analytic", None) is None:
+                self._en_analytic = self.new_state_vector()
+            analytic = self._en_analytic
+            self.initial_values_interpolate(analytic, t)
+        return self.error_norms_compute(state, analytic, components, normalize)
+
     # ------------------------------------------------------------------ Quantities (device backend only)
     def quantities_add_manifold(self, index, weight, options: int) -> int:
         """A point map of this rank (ryujin_hip_quantities_add_manifold): owned local indices, a positive weight per

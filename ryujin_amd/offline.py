@@ -169,6 +169,24 @@ class SyntheticOffline(_OfflineArrays):
         """boundary mass of every boundary_map entry [n_bdry]: the weights of the boundary maps of Quantities"""
         return self._arr(self._lib.ryujin_synth_bdry_mass(self._h), self.n_bdry, np.float64)
 
+    @property
+    def n_cells(self):
+        return int(self._lib.ryujin_synth_n_cells(self._h))
+
+    @property
+    def cells(self):
+        """[n_cells, 2^dim] local indices of the cells of this rank (those whose vertex of smallest global id it owns),
+        vertices in the order v = ix + 2 iy + 4 iz: the cell list of HyperbolicModule.error_norms_configure"""
+        per_cell = 1 << self.dim
+        return self._arr(self._lib.ryujin_synth_cells(self._h), self.n_cells * per_cell,
+                         np.uint32).reshape(-1, per_cell)
+
+    @property
+    def cell_measure(self):
+        """the measure of every (uniform) cell"""
+        s = self.spec
+        return float(np.prod([(s.upper[d] - s.lower[d]) / s.n_cells[d] for d in range(self.dim)]))
+
 
 class ImportedOffline(_OfflineArrays):
     """An OfflineData dump read from disk: the same object as SyntheticOffline as far
