@@ -40,6 +40,7 @@
 
 #include "host_layout.hpp"
 #include "step_plan.hpp"
+#include "rank_reduce.hpp"
 #include "kernels_euler.hpp"
 #include "kernels_limiter.hpp"
 #include "kernels_limiter_stage0.hpp"
@@ -285,27 +286,17 @@ namespace
  * ordering HIP requires; it also makes the cross-stream dependency graph acyclic). A missing
  * hipStreamWaitEvent in the shared choreography is therefore a real data race here, as it would be with
  * RCCL. All-reduces: every rank writes its value into a device slot (double buffered by parity), records
- * an event, waits for the events of all other ranks and reduces the slots with a one-thread kernel. */
-struct LocalGroup {
+ * an event, waits for the events of all other ranks and reduces the slots with a one-thread kernel. The host
+ * half -- the rendezvous and the host-valued vector reductions (reduce_over_ranks) -- is HostRendezvous. */
+struct LocalGroup : HostRendezvous {
   static constexpr int kRing = 2;
-  int n_ranks;
-  std::mutex mtx;
-  std::condition_variable cv;
-  int arrived = 0;
-  unsigned long generation = 0;
   /* exchange number g: packed[r] / pulled[r] = number of exchanges whose event rank r has recorded */
   std::vector<unsigned long> packed, pulled, reduced;
   std::vector<hipEvent_t> ev_packed, ev_pulled, ev_reduced; /* [rank * kRing + g % kRing] */
   std::vector<std::vector<const double *>> mail;           /* [src][dst] -> segment in src's send buffer */
   unsigned long long *slots = nullptr;                      /* device: [2][n_ranks][2] 8-byte slots */
-  std::vector<double> scratch_vec;                          /* [n_ranks][8] vector sums (host) */
-  static constexpr int kQuantitiesRow = 12;                 /* >= 1 + 2 K, K <= 5 */
-  std::vector<double> scratch_quantities;                   /* [n_ranks][kQuantitiesRow] sums of a manifold (host) */
-  static constexpr int kErrorNormsRow = 32;                 /* >= kErrorNormsSums + 2 kErrorNormsMaxComponents */
-  std::vector<double> scratch_error_norms;                  /* [n_ranks][kErrorNormsRow] sums, then maxima (host) */
   int refs = 0;
   int device = 0;
-  bool aborted = false; /* a rank failed: the others must not wait for it (guarded_ctx sets it) */
   /* Measurement facility: ONE rank of an n-rank slab partition run alone, every neighbour replaced by the rank
    * itself (the segment packed for the opposite neighbour is pulled into the ghost range: a periodic channel).
    * Same launches, pack kernels, copies, events and reductions as a middle rank of a real run, on an unshared
@@ -313,7 +304,7 @@ struct LocalGroup {
   bool loopback = false;
 
   LocalGroup(int n, int dev)
-      : n_ranks(n)
+      : HostRendezvous(n)
       , packed(n, 0)
       , pulled(n, 0)
       , reduced(n, 0)
@@ -321,9 +312,6 @@ struct LocalGroup {
       , ev_pulled((size_t)n * kRing, nullptr)
       , ev_reduced((size_t)n * kRing, nullptr)
       , mail(n, std::vector<const double *>(n, nullptr))
-      , scratch_vec((size_t)n * 8, 0.)
-      , scratch_quantities((size_t)n * kQuantitiesRow, 0.)
-      , scratch_error_norms((size_t)n * kErrorNormsRow, 0.)
       , device(dev)
   {
     HIP_CHECK(hipSetDevice(dev));
@@ -346,46 +334,6 @@ struct LocalGroup {
           (void)hipEventDestroy(e);
     if (slots)
       (void)hipFree(slots);
-  }
-
-  /* host-side: publish / await a generation counter (never touches the device) */
-  void publish(std::vector<unsigned long> &counter, int rank, unsigned long value)
-  {
-    {
-      std::lock_guard<std::mutex> lock(mtx);
-      counter[rank] = value;
-    }
-    cv.notify_all();
-  }
-  void await(const std::vector<unsigned long> &counter, int rank, unsigned long value)
-  {
-    std::unique_lock<std::mutex> lock(mtx);
-    cv.wait(lock, [&] { return aborted || counter[rank] >= value; });
-    if (aborted && counter[rank] < value)
-      throw HipError(RYUJIN_ERR_COMM, "in-process transport: another rank of the group failed");
-  }
-  void abort()
-  {
-    {
-      std::lock_guard<std::mutex> lock(mtx);
-      aborted = true;
-    }
-    cv.notify_all();
-  }
-
-  void barrier() /* host rendezvous for the host-valued reductions (state_integrals) */
-  {
-    std::unique_lock<std::mutex> lock(mtx);
-    const unsigned long gen = generation;
-    if (++arrived == n_ranks) {
-      arrived = 0;
-      ++generation;
-      cv.notify_all();
-    } else {
-      cv.wait(lock, [&] { return aborted || generation != gen; });
-      if (aborted && generation == gen)
-        throw HipError(RYUJIN_ERR_COMM, "in-process transport: another rank of the group failed");
-    }
   }
 };
 
@@ -690,6 +638,9 @@ struct ryujin_hip_ctx {
   void local_exchange(double *base, const std::vector<size_t> &send_offset,
                       const std::vector<size_t> &recv_offset, const std::vector<size_t> &recv_count);
   void allreduce_scalar(void *dev_ptr, int op, int count = 1);
+  /* more than one rank whose values differ: not the loopback group, which stands for all of its ranks itself */
+  bool several_ranks() const { return comm && comm->n_ranks > 1 && !(comm->local && comm->local->loopback); }
+  bool reduce_over_ranks(double *dev, std::initializer_list<RankReduceSegment> segments, bool counted = true);
   void wait_comm();
   void join_export();
   void finish();
@@ -1241,6 +1192,38 @@ void ryujin_hip_ctx::allreduce_scalar(void *dev_ptr, int op, int count)
   else
     hipLaunchKernelGGL(k_slot_reduce, dim3(1), dim3(1), 0, stream, slots, g.n_ranks, op, count, dev_ptr);
   ++local_reduces;
+}
+
+/* A few device doubles reduced over the ranks, segment by segment, the same bits on every rank; false (and nothing
+ * enqueued) where there is nothing to reduce over. RCCL: one stream-ordered all-reduce per segment, counted as one.
+ * In-process transport: through the host (HostRendezvous::reduce), the stream drained before and behind. No join
+ * with the comm stream: the callers make it where they need one. */
+bool ryujin_hip_ctx::reduce_over_ranks(double *dev, std::initializer_list<RankReduceSegment> segments, bool counted)
+{
+  if (!several_ranks())
+    return false;
+  if (!comm->local) {
+    if (counted)
+      ++n_allreduces;
+    for (const RankReduceSegment &s : segments) {
+      const ncclRedOp_t op = s.op == RankReduceOp::Sum ? ncclSum : (s.op == RankReduceOp::Max ? ncclMax : ncclMin);
+      NCCL_CHECK(ncclAllReduce(dev, dev, s.count, ncclDouble, op, comm->comm, stream));
+      dev += s.count;
+    }
+    return true;
+  }
+  int n = 0;
+  for (const RankReduceSegment &s : segments)
+    n += s.count;
+  double host[kRankReduceMaxValues];
+  if (n > kRankReduceMaxValues)
+    throw HipError(RYUJIN_ERR_ARG, "reduce_over_ranks: row too long");
+  HIP_CHECK(hipMemcpyAsync(host, dev, sizeof(double) * n, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  comm->local->reduce(comm->rank, host, n, segments);
+  HIP_CHECK(hipMemcpyAsync(dev, host, sizeof(double) * n, hipMemcpyHostToDevice, stream));
+  HIP_CHECK(hipStreamSynchronize(stream)); /* host[] goes out of scope */
+  return true;
 }
 
 void ryujin_hip_ctx::exchange_vector(double *v, int stride, bool after_split_sweep)
@@ -2275,37 +2258,11 @@ void ryujin_hip_ctx::postprocess_compute(int h)
                      eq_params<E>(), mm, pp_desc, fold_bounds ? 1 : 0, s.U.ptr, d_pp_raw.ptr, d_pp_bounds.ptr);
   HIP_CHECK(hipGetLastError());
 
-  if (fold_bounds && comm && comm->n_ranks > 1) {
-    /* over the ranks, as ryujin_hip_state_integrals reduces its sums (the bit patterns are those of non-negative
-     * doubles: reduced as doubles) */
-    double *b = reinterpret_cast<double *>(d_pp_bounds.ptr);
-    if (!comm->local) {
-      ++n_allreduces;
-      NCCL_CHECK(ncclAllReduce(b, b, MAXQ, ncclDouble, ncclMax, comm->comm, stream));
-      NCCL_CHECK(ncclAllReduce(b + MAXQ, b + MAXQ, MAXQ, ncclDouble, ncclMin, comm->comm, stream));
-    } else if (!comm->local->loopback) {
-      static_assert(MAXQ <= 8, "LocalGroup::scratch_vec holds 8 doubles per rank");
-      LocalGroup &g = *comm->local;
-      double host[2 * MAXQ];
-      HIP_CHECK(hipMemcpyAsync(host, b, sizeof(host), hipMemcpyDeviceToHost, stream));
-      HIP_CHECK(hipStreamSynchronize(stream));
-      for (int part = 0; part < 2; ++part) { /* q_max, then q_min */
-        for (int q = 0; q < MAXQ; ++q)
-          g.scratch_vec[(size_t)comm->rank * 8 + q] = host[part * MAXQ + q];
-        g.barrier();
-        for (int q = 0; q < MAXQ; ++q) {
-          double v = g.scratch_vec[q];
-          for (int r = 1; r < g.n_ranks; ++r) {
-            const double w = g.scratch_vec[(size_t)r * 8 + q];
-            v = part == 0 ? std::max(v, w) : std::min(v, w);
-          }
-          host[part * MAXQ + q] = v;
-        }
-        g.barrier();
-      }
-      HIP_CHECK(hipMemcpyAsync(b, host, sizeof(host), hipMemcpyHostToDevice, stream));
-      HIP_CHECK(hipStreamSynchronize(stream)); /* host[] goes out of scope */
-    }
+  if (fold_bounds) {
+    /* q_max, then q_min (the bit patterns are those of non-negative doubles: reduced as doubles) */
+    static_assert(2 * MAXQ <= kRankReduceMaxValues, "HostRendezvous::scratch holds a row per rank");
+    reduce_over_ranks(reinterpret_cast<double *>(d_pp_bounds.ptr),
+                      {{MAXQ, RankReduceOp::Max}, {MAXQ, RankReduceOp::Min}});
   }
   pp_have_bounds = true;
 
@@ -2323,7 +2280,7 @@ template <typename E>
 void ryujin_hip_ctx::quantities_evaluate(Manifold &m, int h, bool accumulate, double t)
 {
   constexpr int NQ = 1 + 2 * E::K;
-  static_assert(NQ <= LocalGroup::kQuantitiesRow, "LocalGroup::scratch_quantities holds a row per rank");
+  static_assert(NQ <= kRankReduceMaxValues, "HostRendezvous::scratch holds a row per rank");
   State &s = state(h);
   const bool time_averaged = (m.options & RYUJIN_Q_TIME_AVERAGED) != 0;
 
@@ -2374,33 +2331,10 @@ void ryujin_hip_ctx::quantities_evaluate(Manifold &m, int h, bool accumulate, do
   }
   double *row = m.series[chunk]->ptr + (m.n_rows % kSeriesChunkRows) * NQ;
   double *sums = m.d_partial.ptr + (size_t)m.n_blocks * NQ;
-  const bool several_ranks = comm && comm->n_ranks > 1 && !(comm->local && comm->local->loopback);
   hipLaunchKernelGGL(k_quantities_final<NQ>, dim3(1), dim3(64), 0, stream, m.n_points > 0 ? m.n_blocks : 0u,
-                     m.d_partial.ptr, t, sums, several_ranks ? nullptr : row);
+                     m.d_partial.ptr, t, sums, several_ranks() ? nullptr : row);
   HIP_CHECK(hipGetLastError());
-  if (several_ranks) {
-    if (!comm->local) {
-      ++n_allreduces;
-      NCCL_CHECK(ncclAllReduce(sums, sums, NQ, ncclDouble, ncclSum, comm->comm, stream));
-    } else {
-      /* in-process transport: host rendezvous, as ryujin_hip_state_integrals; the ranks in order on every rank */
-      LocalGroup &g = *comm->local;
-      double host[NQ];
-      HIP_CHECK(hipMemcpyAsync(host, sums, sizeof(host), hipMemcpyDeviceToHost, stream));
-      HIP_CHECK(hipStreamSynchronize(stream));
-      for (int q = 0; q < NQ; ++q)
-        g.scratch_quantities[(size_t)comm->rank * LocalGroup::kQuantitiesRow + q] = host[q];
-      g.barrier();
-      for (int q = 0; q < NQ; ++q) {
-        double v = 0.;
-        for (int r = 0; r < g.n_ranks; ++r)
-          v += g.scratch_quantities[(size_t)r * LocalGroup::kQuantitiesRow + q];
-        host[q] = v;
-      }
-      g.barrier();
-      HIP_CHECK(hipMemcpyAsync(sums, host, sizeof(host), hipMemcpyHostToDevice, stream));
-      HIP_CHECK(hipStreamSynchronize(stream)); /* host[] goes out of scope */
-    }
+  if (reduce_over_ranks(sums, {{NQ, RankReduceOp::Sum}})) {
     hipLaunchKernelGGL(k_quantities_row<NQ>, dim3(1), dim3(64), 0, stream, sums, t, row);
     HIP_CHECK(hipGetLastError());
   }
@@ -2414,7 +2348,8 @@ void ryujin_hip_ctx::quantities_evaluate(Manifold &m, int h, bool accumulate, do
 void ryujin_hip_ctx::error_norms_compute(int h_state, int h_analytic, const ErrorNormsDesc &D, double *host_result)
 {
   constexpr int NS = kErrorNormsSums, MAXC = kErrorNormsMaxComponents;
-  static_assert(NS + 2 * MAXC <= LocalGroup::kErrorNormsRow, "LocalGroup::scratch_error_norms holds a row per rank");
+  static_assert(NS + 2 * MAXC <= kRankReduceMaxValues, "HostRendezvous::scratch holds a row per rank");
+  static_assert(sizeof(unsigned long long) == sizeof(double), "sums and max_bits are reduced as one row of doubles");
   ErrorNorms &en = *error_norms;
   State &s = state(h_state);
   State &a = state(h_analytic);
@@ -2455,38 +2390,11 @@ void ryujin_hip_ctx::error_norms_compute(int h_state, int h_analytic, const Erro
       hipLaunchKernelGGL((k_error_norms_cells<0, 0>), grid, block, 0, stream, D, C, s.U.ptr, a.U.ptr);
     HIP_CHECK(hipGetLastError());
   }
-  const bool several_ranks = comm && comm->n_ranks > 1 && !(comm->local && comm->local->loopback);
   hipLaunchKernelGGL(k_error_norms_final, dim3(1), dim3(64), 0, stream, D, en.n_blocks, partial, sums, max_bits,
-                     several_ranks ? nullptr : result);
+                     several_ranks() ? nullptr : result);
   HIP_CHECK(hipGetLastError());
-  if (several_ranks) {
-    double *maxima = reinterpret_cast<double *>(max_bits); /* bit patterns of non-negative doubles: reduced as doubles */
-    if (!comm->local) {
-      ++n_allreduces;
-      NCCL_CHECK(ncclAllReduce(sums, sums, NS, ncclDouble, ncclSum, comm->comm, stream));
-      NCCL_CHECK(ncclAllReduce(maxima, maxima, 2 * MAXC, ncclDouble, ncclMax, comm->comm, stream));
-    } else {
-      /* in-process transport: host rendezvous, as ryujin_hip_state_integrals; the ranks in order on every rank */
-      LocalGroup &g = *comm->local;
-      constexpr int ROW = LocalGroup::kErrorNormsRow;
-      double host[NS + 2 * MAXC];
-      HIP_CHECK(hipMemcpyAsync(host, sums, sizeof(host), hipMemcpyDeviceToHost, stream));
-      HIP_CHECK(hipStreamSynchronize(stream));
-      for (int q = 0; q < NS + 2 * MAXC; ++q)
-        g.scratch_error_norms[(size_t)comm->rank * ROW + q] = host[q];
-      g.barrier();
-      for (int q = 0; q < NS + 2 * MAXC; ++q) {
-        double v = g.scratch_error_norms[q];
-        for (int r = 1; r < g.n_ranks; ++r) {
-          const double w = g.scratch_error_norms[(size_t)r * ROW + q];
-          v = q < NS ? v + w : std::max(v, w);
-        }
-        host[q] = v;
-      }
-      g.barrier();
-      HIP_CHECK(hipMemcpyAsync(sums, host, sizeof(host), hipMemcpyHostToDevice, stream));
-      HIP_CHECK(hipStreamSynchronize(stream)); /* host[] goes out of scope */
-    }
+  /* the sums, then the maxima behind them (bit patterns of non-negative doubles: reduced as doubles) */
+  if (reduce_over_ranks(sums, {{NS, RankReduceOp::Sum}, {2 * MAXC, RankReduceOp::Max}})) {
     hipLaunchKernelGGL(k_error_norms_result, dim3(1), dim3(64), 0, stream, D, sums, max_bits, result);
     HIP_CHECK(hipGetLastError());
   }
@@ -2506,6 +2414,9 @@ namespace
     } catch (const HipError &e) {
       g_error = e.what();
       return e.status;
+    } catch (const RankGroupAborted &e) {
+      g_error = e.what();
+      return RYUJIN_ERR_COMM;
     } catch (const std::invalid_argument &e) {
       g_error = e.what();
       return RYUJIN_ERR_ARG;
@@ -2530,6 +2441,27 @@ namespace
     if (status < 0 && status != RYUJIN_ERR_TAU && ctx && ctx->comm && ctx->comm->local)
       ctx->comm->local->abort();
     return status;
+  }
+
+  /* the arguments of a Runge-Kutta step (ryujin_hip_time_step_n, _fn, _iv): RYUJIN_OK, or RYUJIN_ERR_TAU by the
+   * tau_max rule of step(); every other error throws */
+  int check_time_step_args(ryujin_hip_ctx *ctx, int h_state, int n_tmp, const int *h_tmp, double tau_max,
+                           const double *tau_out)
+  {
+    if (!h_tmp || !tau_out || n_tmp < 1 || n_tmp > 8)
+      throw HipError(RYUJIN_ERR_ARG, "time_step: bad argument");
+    if (std::isnan(tau_max) || !(tau_max > 0.))
+      return RYUJIN_ERR_TAU; /* as in step() */
+    ctx->state(h_state);
+    for (int q = 0; q < n_tmp; ++q) {
+      ctx->state(h_tmp[q]);
+      if (h_tmp[q] == h_state)
+        throw HipError(RYUJIN_ERR_ARG, "time_step: temporary vectors must differ from the state vector");
+      for (int r = 0; r < q; ++r)
+        if (h_tmp[r] == h_tmp[q])
+          throw HipError(RYUJIN_ERR_ARG, "time_step: temporary vectors must be distinct");
+    }
+    return RYUJIN_OK;
   }
 
   template <typename E>
@@ -3008,19 +2940,8 @@ int ryujin_hip_time_step_n(ryujin_hip_ctx *ctx, int scheme, int h_state, int n_t
                            double cfl_min, double cfl_max, double *tau_out)
 {
   return guarded_ctx(ctx, [&]() {
-    if (!h_tmp || !tau_out || n_tmp < 1 || n_tmp > 8)
-      throw HipError(RYUJIN_ERR_ARG, "time_step: bad argument");
-    if (std::isnan(tau_max) || !(tau_max > 0.))
-      return RYUJIN_ERR_TAU; /* as in step() */
-    ctx->state(h_state);
-    for (int q = 0; q < n_tmp; ++q) {
-      ctx->state(h_tmp[q]);
-      if (h_tmp[q] == h_state)
-        throw HipError(RYUJIN_ERR_ARG, "time_step: temporary vectors must differ from the state vector");
-      for (int r = 0; r < q; ++r)
-        if (h_tmp[r] == h_tmp[q])
-          throw HipError(RYUJIN_ERR_ARG, "time_step: temporary vectors must be distinct");
-    }
+    if (const int status = check_time_step_args(ctx, h_state, n_tmp, h_tmp, tau_max, tau_out))
+      return status;
     return dispatch_equation(ctx->params.equation, ctx->dim, [&](auto tag) {
       return ctx->template time_step<typename decltype(tag)::type>(scheme, h_state, n_tmp, h_tmp,
                                                                    dirichlet_aos, tau_max, cfl_recovery,
@@ -3034,19 +2955,8 @@ int ryujin_hip_time_step_fn(ryujin_hip_ctx *ctx, int scheme, int h_state, int n_
                             double cfl_min, double cfl_max, double *tau_out)
 {
   return guarded_ctx(ctx, [&]() {
-    if (!h_tmp || !tau_out || n_tmp < 1 || n_tmp > 8)
-      throw HipError(RYUJIN_ERR_ARG, "time_step: bad argument");
-    if (std::isnan(tau_max) || !(tau_max > 0.))
-      return RYUJIN_ERR_TAU; /* as in step() */
-    ctx->state(h_state);
-    for (int q = 0; q < n_tmp; ++q) {
-      ctx->state(h_tmp[q]);
-      if (h_tmp[q] == h_state)
-        throw HipError(RYUJIN_ERR_ARG, "time_step: temporary vectors must differ from the state vector");
-      for (int r = 0; r < q; ++r)
-        if (h_tmp[r] == h_tmp[q])
-          throw HipError(RYUJIN_ERR_ARG, "time_step: temporary vectors must be distinct");
-    }
+    if (const int status = check_time_step_args(ctx, h_state, n_tmp, h_tmp, tau_max, tau_out))
+      return status;
     return dispatch_equation(ctx->params.equation, ctx->dim, [&](auto tag) {
       return ctx->template time_step<typename decltype(tag)::type>(scheme, h_state, n_tmp, h_tmp, nullptr, tau_max,
                                                                    cfl_recovery, cfl_min, cfl_max, tau_out, t,
@@ -3161,27 +3071,9 @@ int ryujin_hip_state_integrals(ryujin_hip_ctx *ctx, int handle, double *out)
     default: launch(std::integral_constant<int, 5>{}); break;
     }
     HIP_CHECK(hipGetLastError());
-    const ryujin_hip_comm *cm = ctx->comm;
-    if (cm && cm->n_ranks > 1 && !cm->local)
-      NCCL_CHECK(ncclAllReduce(result, result, K, ncclDouble, ncclSum, cm->comm, ctx->stream));
-    double host[8] = {0.};
-    HIP_CHECK(hipMemcpyAsync(host, result, sizeof(double) * K, hipMemcpyDeviceToHost, ctx->stream));
+    ctx->reduce_over_ranks(result, {{K, RankReduceOp::Sum}}, false);
+    HIP_CHECK(hipMemcpyAsync(out, result, sizeof(double) * K, hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (cm && cm->n_ranks > 1 && cm->local && !cm->local->loopback) {
-      LocalGroup &g = *cm->local;
-      for (int q = 0; q < K; ++q)
-        g.scratch_vec[(size_t)cm->rank * 8 + q] = host[q];
-      g.barrier();
-      for (int q = 0; q < K; ++q) {
-        double v = 0.;
-        for (int r = 0; r < g.n_ranks; ++r)
-          v += g.scratch_vec[(size_t)r * 8 + q];
-        host[q] = v;
-      }
-      g.barrier();
-    }
-    for (int q = 0; q < K; ++q)
-      out[q] = host[q];
     return RYUJIN_OK;
   });
 }
@@ -4176,19 +4068,8 @@ int ryujin_hip_time_step_iv(ryujin_hip_ctx *ctx, int scheme, int h_state, int n_
 {
   return guarded_ctx(ctx, [&]() {
     ctx->require_initial_values();
-    if (!h_tmp || !tau_out || n_tmp < 1 || n_tmp > 8)
-      throw HipError(RYUJIN_ERR_ARG, "time_step: bad argument");
-    if (std::isnan(tau_max) || !(tau_max > 0.))
-      return RYUJIN_ERR_TAU; /* as in step() */
-    ctx->state(h_state);
-    for (int q = 0; q < n_tmp; ++q) {
-      ctx->state(h_tmp[q]);
-      if (h_tmp[q] == h_state)
-        throw HipError(RYUJIN_ERR_ARG, "time_step: temporary vectors must differ from the state vector");
-      for (int r = 0; r < q; ++r)
-        if (h_tmp[r] == h_tmp[q])
-          throw HipError(RYUJIN_ERR_ARG, "time_step: temporary vectors must be distinct");
-    }
+    if (const int status = check_time_step_args(ctx, h_state, n_tmp, h_tmp, tau_max, tau_out))
+      return status;
     return dispatch_initial_values(ctx, [&](auto tag) {
       return ctx->template time_step<typename decltype(tag)::type>(scheme, h_state, n_tmp, h_tmp, nullptr, tau_max,
                                                                    cfl_recovery, cfl_min, cfl_max, tau_out, t,

@@ -4,10 +4,8 @@ ncclAllReduce of the integrals (sum) and of the nodal maxima (max) runs. Rank an
 environment, the unique id and the results go through files.
 
 usage: error_norms_rccl_worker.py <out prefix> <cells per unit>      (every rank stores <prefix>.rank<r>.npz)"""
-import ctypes as C
 import os
 import sys
-import time
 
 import numpy as np
 
@@ -16,6 +14,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from quantities_rccl_worker import partition_state  # noqa: E402
+from rccl_rendezvous import join_ranks  # noqa: E402
 from ryujin_amd import HyperbolicModule, capi, error_norms, offline  # noqa: E402
 
 X_CUT = 1.2   # the cells whose lower corner has x < X_CUT -- none of them on the last of three ranks
@@ -38,26 +37,7 @@ def select_cells(off, x_cut):
 
 def main():
     out_prefix, cells_per_unit = sys.argv[1], int(sys.argv[2])
-    rendezvous = os.environ["RYUJIN_RCCL_STUB_DIR"]
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    capi.load_synth()
-    lib = capi.load_hip()
-    err = C.CDLL(None).ncclGetErrorString
-    err.restype = C.c_char_p
-    assert b"rccl stub" in err(4), "tests/cpp/librccl_stub.so is not in front of librccl.so"
-    uid = C.create_string_buffer(capi.UNIQUE_ID_BYTES)
-    uid_file = os.path.join(rendezvous, "unique_id")
-    if rank == 0:
-        assert lib.ryujin_hip_comm_unique_id(uid) == 0, lib.ryujin_hip_last_error()
-        with open(uid_file + ".tmp", "wb") as f:
-            f.write(uid.raw)
-        os.rename(uid_file + ".tmp", uid_file)
-    else:
-        while not os.path.exists(uid_file):
-            time.sleep(0.01)
-        uid = C.create_string_buffer(open(uid_file, "rb").read(), capi.UNIQUE_ID_BYTES)
-    comm = C.c_void_p()
-    assert lib.ryujin_hip_comm_init(C.byref(comm), uid, rank, world, 0) == 0, lib.ryujin_hip_last_error()
+    lib, comm, rank, world = join_ranks()
     off = offline.SyntheticOffline(offline.mach3_step_2d(cells_per_unit, n_ranks=world, rank=rank))
     m = HyperbolicModule(off, equation=capi.EQ_EULER, backend="hip", comm=comm, device=0)
     cells = select_cells(off, X_ALL)

@@ -461,38 +461,11 @@ def _check_ranks(single, parts, indices, params, ranks):
 def test_rccl_leg_over_the_test_double(tmp_path):
     """the same partitioned case through the library's ncclAllReduce(sum) of the weighted sums: three processes on one
     GPU over tests/cpp/librccl_stub.so"""
-    import os
-    import signal
-    import subprocess
-    import sys
     import quantities_rccl_worker as worker
     import test_rccl_stub
     world, cpu = 3, 30
-    test_rccl_stub.build_stub()
-    rendezvous = str(tmp_path / "rendezvous")
-    os.makedirs(rendezvous)
     prefix = str(tmp_path / "q")
-    procs = []
-    for rank in range(world):
-        env = dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), LD_PRELOAD=test_rccl_stub.stub_preload(),
-                   RYUJIN_RCCL_STUB_DIR=rendezvous, OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, worker.__file__, prefix, str(cpu)], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                                      start_new_session=True))
-    errs = []
-    try:
-        for p in procs:
-            _, err = p.communicate(timeout=300)
-            errs.append((p.returncode, err))
-    except subprocess.TimeoutExpired:
-        for p in procs:
-            try:
-                os.killpg(p.pid, signal.SIGKILL)
-            except ProcessLookupError:
-                pass
-        pytest.fail(f"{world} ranks over the RCCL stub timed out")
-    for rc, err in errs:
-        assert rc == 0, err[-4000:]
+    test_rccl_stub.launch(world, [prefix, str(cpu)], tmp_path, timeout=300, worker=worker.__file__)
     single = offline.SyntheticOffline(offline.mach3_step_2d(cpu))
     parts = [offline.SyntheticOffline(offline.mach3_step_2d(cpu, n_ranks=world, rank=r)) for r in range(world)]
     ranks = [dict(np.load(f"{prefix}.rank{r}.npz")) for r in range(world)]

@@ -39,8 +39,8 @@ def stub_preload():
     return ":".join([STUB] + ([os.environ["LD_PRELOAD"]] if os.environ.get("LD_PRELOAD") else []))
 
 
-def launch(world, args, tmp_path, timeout=600):
-    """`world` processes of rccl_worker.py on device 0, the stub in front of RCCL; kills the whole group on a hang"""
+def launch(world, args, tmp_path, timeout=600, worker=os.path.join(ROOT, "tests", "rccl_worker.py")):
+    """`world` processes of the script `worker` on device 0, the stub in front of RCCL; kills the whole group on a hang"""
     import signal
     build_stub()
     rendezvous = str(tmp_path / "rendezvous")
@@ -49,9 +49,8 @@ def launch(world, args, tmp_path, timeout=600):
     for rank in range(world):
         env = dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), LD_PRELOAD=stub_preload(), RYUJIN_RCCL_STUB_DIR=rendezvous,
                    OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "rccl_worker.py"), *args], env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                                      start_new_session=True))
+        procs.append(subprocess.Popen([sys.executable, worker, *args], env=env, stdout=subprocess.PIPE,
+                                      stderr=subprocess.PIPE, text=True, start_new_session=True))
     errs = []
     try:
         for p in procs:
