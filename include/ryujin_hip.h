@@ -485,6 +485,24 @@ int ryujin_hip_tile_statistics(ryujin_hip_ctx *ctx, double *stored_fraction, dou
  * tests): 6 d_ij, 7 l_ij, 8 lij_next (plain CSR over n_relevant rows; d_ij is never exchanged, its ghost rows
  * stay zero as in the reference), 9 r_i (k per row, n_relevant rows) */
 int ryujin_hip_debug_fetch(ryujin_hip_ctx *ctx, int what, double *out, size_t n_doubles);
+/* Which kernels the LAST step() ran (ryujin_amd/csrc/step_plan.hpp: the plan decided once per update) and what its
+ * sweeps of steps 5 and 6 launched, as RYUJIN_DEBUG_PLAN_LENGTH ints in this order:
+ *    0 step2 (0 alpha_then_dij, 1 dij_alpha_sc, 2 records, 3 dij_alpha)   1 step2_split   2 fast_riemann
+ *    3 diag_width   4 step4_single_walk   5 step4_has_stages   6 step4_friction   7 step4_stores_p   8 dg
+ *    9 step5 (0 none, 1 stage0_per_tile, 2 stage0_per_slice, 3 stage0_groups, 4 recompute, 5 pij_lij)
+ *   10 step5_groups   11 wide   12 has_V   13 pij_stored (as ryujin_hip_limiter_statistics)
+ *   14 tiles_predicted_from_history   15 step6 (0 none, 1 per_slice, 2 cached, 3 high_order)   16 step6_flags
+ *   17 step7 (0 none, 1 last_cached, 2 high_order)   18 fuse_precompute   19 checked
+ *   20 number of launches of the step-5 sweep, 21 of the step-6 sweep (one on one rank; on several the export part,
+ *      then the interior part; an empty part is not launched)
+ *   22, 23 and 24, 25: per launch of step 5 its number of slices and gridDim.y (the waves that share a slice)
+ *   26 - 28 and 29 - 31: per launch of step 6 its number of slices, gridDim.y, and whether the four waves of a block
+ *      shared a slice (per slice -- the three kernels light, repair, heavy -- counts as one launch)
+ * The per-launch values are recorded where the kernels are launched, not evaluated again. Host values only: no
+ * synchronisation, no device work. Writes min(n, RYUJIN_DEBUG_PLAN_LENGTH) ints, returns RYUJIN_DEBUG_PLAN_LENGTH
+ * (a negative status on error). All zero before the first step(). */
+#define RYUJIN_DEBUG_PLAN_LENGTH 32
+int ryujin_hip_debug_plan(ryujin_hip_ctx *ctx, int *out, int n);
 /* device time [ms] of the sweeps of the last step (hipEvent pairs; ms[n] = the reference's Scope timer
  * "time step [H] n", n = 2..7; ms[1] unused (step 1 is a separate call); ms[0] = the indicator kernel
  * alone when step 2 runs as two kernels, else 0); enable = nonzero switches the event recording on. */

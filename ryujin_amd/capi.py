@@ -283,7 +283,7 @@ HIP_SYMBOLS = [
     "ryujin_hip_prepare_state_vector", "ryujin_hip_step", "ryujin_hip_sadd", "ryujin_hip_time_step", "ryujin_hip_time_step_n",
     "ryujin_hip_get_timers_accum",
     "ryujin_hip_set_cfl", "ryujin_hip_get_cfl", "ryujin_hip_set_id_violation_strategy",
-    "ryujin_hip_get_alpha", "ryujin_hip_get_counters", "ryujin_hip_limiter_statistics", "ryujin_hip_debug_fetch",
+    "ryujin_hip_get_alpha", "ryujin_hip_get_counters", "ryujin_hip_limiter_statistics", "ryujin_hip_debug_fetch", "ryujin_hip_debug_plan",
     "ryujin_hip_set_timers", "ryujin_hip_get_timers", "ryujin_hip_synchronize",
     "ryujin_hip_event_record", "ryujin_hip_event_elapsed_ms", "ryujin_hip_last_error",
     "ryujin_hip_version", "ryujin_hip_debug_layout", "ryujin_hip_debug_pow", "ryujin_hip_debug_function", "ryujin_hip_debug_rk_outcome",
@@ -370,6 +370,7 @@ def load_hip():
         lib.ryujin_hip_state_download_owned.argtypes = [vp, C.c_int, c_double_p]
         lib.ryujin_hip_state_download_prepared.argtypes = [vp, C.c_int, c_double_p]
         lib.ryujin_hip_debug_addresses.argtypes = [vp, c_u64_p]
+        lib.ryujin_hip_debug_plan.argtypes = [vp, c_int_p, C.c_int]
         lib.ryujin_hip_synchronize.argtypes = [vp]
         lib.ryujin_hip_event_record.argtypes = [vp, C.c_int]
         lib.ryujin_hip_event_elapsed_ms.argtypes = [vp, c_double_p]

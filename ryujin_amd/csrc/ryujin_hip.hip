@@ -521,6 +521,30 @@ struct ryujin_hip_ctx {
    * forms the rest from the operands in last_s0 */
   StepPlan last_plan{};
   Stage0Src last_s0{};
+  /* what steps 5 and 6 of the latest update launched (ryujin_hip_debug_plan): written by the sweep lambdas next to the
+   * launch itself, one record per part of the sweep (one on one rank; the export and the interior part on several).
+   * Host values only. */
+  struct LaunchRecord {
+    uint32_t n_slices = 0, grid_y = 0;
+    bool shares_slices = false;
+  };
+  struct LaunchLog {
+    static constexpr int kParts = 2;
+    int n_step5 = 0, n_step6 = 0;
+    LaunchRecord step5[kParts], step6[kParts];
+  } last_launches{};
+  void record_step5(const DeviceMesh &mm, const uint32_t grid_y)
+  {
+    if (last_launches.n_step5 < LaunchLog::kParts)
+      last_launches.step5[last_launches.n_step5] = LaunchRecord{mm.slice_end - mm.slice_begin, grid_y, false};
+    ++last_launches.n_step5;
+  }
+  void record_step6(const DeviceMesh &mm, const uint32_t grid_y, const bool shares_slices)
+  {
+    if (last_launches.n_step6 < LaunchLog::kParts)
+      last_launches.step6[last_launches.n_step6] = LaunchRecord{mm.slice_end - mm.slice_begin, grid_y, shares_slices};
+    ++last_launches.n_step6;
+  }
   /* SliceFlags (kernels_limiter.hpp), [n_slices] each; `unlimited` starts at 0 = "limited": the first update of a
    * context stores P_ij everywhere */
   DeviceBuffer<uint8_t> d_slice_unlimited, d_slice_first_stored, d_slice_todo;
@@ -1725,6 +1749,7 @@ void ryujin_hip_ctx::step5_limiter(const StepPlan &plan, const StepArgs<E::DIMEN
                            dim3(grid.x, NY), block, 0, launch_stream, eparams, mm, d_scalars.ptr, old.U.ptr,
                            d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr,
                            NY == 1 ? d_V.ptr : nullptr, flags, storage);
+        record_step5(mm, NY);
       };
       constexpr std::integral_constant<int, 1> one{};
       if (plan.step5 == Step5::stage0_per_tile) {
@@ -1745,6 +1770,7 @@ void ryujin_hip_ctx::step5_limiter(const StepPlan &plan, const StepArgs<E::DIMEN
           hipLaunchKernelGGL((k_pij_lij_recompute<DIM, NY>), dim3(grid.x, NY), block, 0, launch_stream, eparams,
                              mm, d_scalars.ptr, a.weight, old.U.ptr, d_alpha.ptr, d_dij.ptr, nw.U.ptr, d_r.ptr,
                              d_bounds.ptr, d_pij.ptr, d_lij.ptr);
+          record_step5(mm, NY);
         });
         return;
       }
@@ -1756,6 +1782,7 @@ void ryujin_hip_ctx::step5_limiter(const StepPlan &plan, const StepArgs<E::DIMEN
                            d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_V.ptr);
       });
     });
+    record_step5(mm, 1);
   });
   if (plan.checked) /* the first limiter pass in the checked control flow (limiter.template.h:110-134,244-322) */
     sweep([&](const DeviceMesh &mm, dim3 grid) {
@@ -1792,6 +1819,7 @@ void ryujin_hip_ctx::step6_high_order_next(const StepPlan &plan, const StepArgs<
         launch_mode(std::integral_constant<int, kHoLight>{});
         hipLaunchKernelGGL(k_pij_repair<E>, grid, block, 0, launch_stream, mm, last_s0, d_pij.ptr, a.slice_flags);
         launch_mode(std::integral_constant<int, kHoHeavy>{});
+        record_step6(mm, 1, false);
         return;
       }
     }
@@ -1801,6 +1829,7 @@ void ryujin_hip_ctx::step6_high_order_next(const StepPlan &plan, const StepArgs<
         hipLaunchKernelGGL((k_high_order_next_cached<E, kWidth, kWidth, true>), dim3(n_launch), block, 0,
                            launch_stream, eparams, mm, nw.U.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_lij_next.ptr,
                            V, last_s0, SliceFlags{unlimited, nullptr, nullptr});
+        record_step6(mm, 1, true);
         return;
       }
     }
@@ -1815,6 +1844,7 @@ void ryujin_hip_ctx::step6_high_order_next(const StepPlan &plan, const StepArgs<
                            mm, nw.U.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_lij_next.ptr,
                            FusedSadd{0., 0., nullptr});
       });
+    record_step6(mm, 1, false);
   });
   if (plan.checked) /* the update after the first pass (:1121-1126) and the second pass's success (:1155-1161) */
     sweep([&](const DeviceMesh &mm, dim3 grid) {
@@ -1911,6 +1941,7 @@ int ryujin_hip_ctx::step(int h_old, int stages, const int *h_stage, const double
   if (plan.violated)
     throw HipError(RYUJIN_ERR_ARG, std::string("internal: ") + plan.violated);
   last_plan = plan;
+  last_launches = LaunchLog{};
   pending_precompute = false;
 
   /* scalars: tau_max := tau_max_in, flags := 0 -- carried by the first sweep of step 2 (step_begin) */
@@ -3145,6 +3176,49 @@ int ryujin_hip_chain_info(ryujin_hip_ctx *ctx, unsigned long long *n_chained_til
     if (n_chained_entries)
       *n_chained_entries = ctx->d_tiles.n == 0 ? 0ull : (masks ? ctx->L.n_chained_entries : 63ull * ctx->L.n_end_lane_tiles);
     return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_debug_plan(ryujin_hip_ctx *ctx, int *out, int n)
+{
+  return guarded([&]() {
+    if (!ctx || (n > 0 && !out) || n < 0)
+      throw HipError(RYUJIN_ERR_ARG, "null context or output");
+    const StepPlan &p = ctx->last_plan;
+    const auto &log = ctx->last_launches;
+    int v[RYUJIN_DEBUG_PLAN_LENGTH] = {(int)p.step2,
+                                       p.step2_split,
+                                       p.fast_riemann,
+                                       p.diag_width,
+                                       p.step4_single_walk,
+                                       p.step4_has_stages,
+                                       p.step4_friction,
+                                       p.step4_stores_p,
+                                       p.dg,
+                                       (int)p.step5,
+                                       (int)p.step5_groups,
+                                       p.wide,
+                                       p.has_V,
+                                       p.pij_stored,
+                                       p.tiles_predicted_from_history,
+                                       (int)p.step6,
+                                       p.step6_flags,
+                                       (int)p.step7,
+                                       p.fuse_precompute,
+                                       p.checked,
+                                       log.n_step5,
+                                       log.n_step6};
+    static_assert(22 + 5 * ryujin_hip_ctx::LaunchLog::kParts == RYUJIN_DEBUG_PLAN_LENGTH, "layout of the record");
+    for (int q = 0; q < ryujin_hip_ctx::LaunchLog::kParts; ++q) {
+      v[22 + 2 * q] = (int)log.step5[q].n_slices;
+      v[23 + 2 * q] = (int)log.step5[q].grid_y;
+      v[26 + 3 * q] = (int)log.step6[q].n_slices;
+      v[27 + 3 * q] = (int)log.step6[q].grid_y;
+      v[28 + 3 * q] = log.step6[q].shares_slices;
+    }
+    for (int q = 0; q < std::min(n, (int)RYUJIN_DEBUG_PLAN_LENGTH); ++q)
+      out[q] = v[q];
+    return (int)RYUJIN_DEBUG_PLAN_LENGTH;
   });
 }
 

@@ -542,6 +542,32 @@ class HyperbolicModule:
                     n_chained_tiles=ch.value, chained_tile_fraction=(ch.value / n.value if n.value else 0.0),
                     chained_entry_fraction=(ce.value / (64.0 * n.value) if n.value else 0.0))
 
+    PLAN_STEP2 = ("alpha_then_dij", "dij_alpha_sc", "records", "dij_alpha")
+    PLAN_STEP5 = ("none", "stage0_per_tile", "stage0_per_slice", "stage0_groups", "recompute", "pij_lij")
+    PLAN_STEP6 = ("none", "per_slice", "cached", "high_order")
+    PLAN_STEP7 = ("none", "last_cached", "high_order")
+
+    def last_plan(self) -> dict:
+        """Which kernels the latest step() ran (the StepPlan of ryujin_amd/csrc/step_plan.hpp, field by field) and,
+        under "step5_launches" / "step6_launches", what each launch of those two sweeps was given where it was made:
+        the number of slices, gridDim.y and -- step 6 -- whether the four waves of a block shared a slice
+        (ryujin_hip_debug_plan; device backend only; host values, no synchronisation)."""
+        n = 32
+        v = (C.c_int * n)()
+        rc = self._lib.ryujin_hip_debug_plan(self._ctx, v, n)
+        if rc != n:
+            self._check(rc if rc < 0 else capi.RYUJIN_ERR_ARG)
+        flags = ("step2_split", "fast_riemann", None, "step4_single_walk", "step4_has_stages", "step4_friction",
+                 "step4_stores_p", "dg", None, None, "wide", "has_V", None, "tiles_predicted_from_history", None,
+                 "step6_flags", None, "fuse_precompute", "checked")
+        out = dict(step2=self.PLAN_STEP2[v[0]], diag_width=v[3], step5=self.PLAN_STEP5[v[9]], step5_groups=v[10],
+                   pij_stored=v[13], step6=self.PLAN_STEP6[v[15]], step7=self.PLAN_STEP7[v[17]])
+        out.update({name: bool(v[1 + q]) for q, name in enumerate(flags) if name})
+        out["step5_launches"] = [dict(n_slices=v[22 + 2 * q], grid_y=v[23 + 2 * q]) for q in range(min(v[20], 2))]
+        out["step6_launches"] = [dict(n_slices=v[26 + 3 * q], grid_y=v[27 + 3 * q], shares_slices=bool(v[28 + 3 * q]))
+                                 for q in range(min(v[21], 2))]
+        return out
+
     def debug_fetch(self, what: str) -> np.ndarray:
         """`*_all`: over all locally relevant rows, i.e. including the ghost rows / ghost range received from
         the neighbour ranks."""

@@ -4,6 +4,11 @@
 //   step_plan_cases path equation dim max_row_len n_slices limited_fraction [resident_waves5 resident_waves6 fold]
 //                               the kernel path of one configuration (defaults of create()) as JSON: one name per launch
 //                               of a one-launch sweep, as rocprofv3 prints it
+//   step_plan_cases plan equation dim max_row_len n_slices limited_fraction stages [n_launch_slices ...]
+//                               every field of the plan of one configuration (defaults of create(), a step() outside
+//                               the device-resident driver: no pending pre-pass) under the names of
+//                               HyperbolicModule.last_plan(), and per given launch size what the sweeps of steps 5
+//                               and 6 make of it: gridDim.y of step 5, whether step 6 shares slices
 // (test infrastructure; built by tests/test_step_plan.py)
 #include <cstdio>
 #include <cstdlib>
@@ -98,10 +103,10 @@ namespace
     return k;
   }
 
-  int run_path(int argc, char **argv)
+  /* the inputs of a context created with the defaults of create() and of ryujin_hip_default_params (gamma = 7/5:
+   * rarefaction exponent 7) */
+  StepPlanInput default_input(char **argv)
   {
-    if (argc < 7)
-      return 2;
     StepPlanInput in;
     const std::string eq = argv[2];
     in.equation = eq == "euler" ? PlanEquation::euler
@@ -111,14 +116,27 @@ namespace
     in.max_row_len = (uint32_t)std::atoi(argv[4]);
     in.n_slices = (uint32_t)std::atoll(argv[5]);
     in.limited_fraction = std::atof(argv[6]);
-    /* the defaults of create() and of ryujin_hip_default_params (gamma = 7/5: rarefaction exponent 7) */
-    in.resident_waves_step5 = argc > 7 ? (uint32_t)std::atoi(argv[7]) : 2048u;
-    in.resident_waves_step6 = argc > 8 ? (uint32_t)std::atoi(argv[8]) : 4096u;
-    in.bc_fold_max_slices = argc > 9 ? (uint32_t)std::atoi(argv[9]) : 4096u;
+    in.resident_waves_step5 = 2048u;
+    in.resident_waves_step6 = 4096u;
+    in.bc_fold_max_slices = 4096u;
     in.per_slice_max_limited = 0.8;
     in.fusable_precompute = in.equation == PlanEquation::euler || in.equation == PlanEquation::shallow_water;
-    in.pending_precompute = true; /* a stage of the device-resident SSPRK33 driver */
     in.rarefaction_power = 7;
+    return in;
+  }
+
+  int run_path(int argc, char **argv)
+  {
+    if (argc < 7)
+      return 2;
+    StepPlanInput in = default_input(argv);
+    if (argc > 7)
+      in.resident_waves_step5 = (uint32_t)std::atoi(argv[7]);
+    if (argc > 8)
+      in.resident_waves_step6 = (uint32_t)std::atoi(argv[8]);
+    if (argc > 9)
+      in.bc_fold_max_slices = (uint32_t)std::atoi(argv[9]);
+    in.pending_precompute = true; /* a stage of the device-resident SSPRK33 driver */
     const StepPlan p = plan_step(in);
     if (p.unsupported || p.violated) {
       std::fprintf(stderr, "%s\n", p.unsupported ? p.unsupported : p.violated);
@@ -129,6 +147,44 @@ namespace
     const auto k = kernel_path(in, p);
     for (size_t i = 0; i < k.size(); ++i)
       std::printf("%s\"%s\"", i ? ", " : "", k[i].c_str());
+    std::printf("]}\n");
+    return 0;
+  }
+
+  int run_plan(int argc, char **argv)
+  {
+    if (argc < 8)
+      return 2;
+    StepPlanInput in = default_input(argv);
+    in.stages = std::atoi(argv[7]);
+    const StepPlan p = plan_step(in);
+    if (p.unsupported || p.violated) {
+      std::fprintf(stderr, "%s\n", p.unsupported ? p.unsupported : p.violated);
+      return 1;
+    }
+    const char *step2[] = {"alpha_then_dij", "dij_alpha_sc", "records", "dij_alpha"};
+    const char *step5[] = {"none", "stage0_per_tile", "stage0_per_slice", "stage0_groups", "recompute", "pij_lij"};
+    const char *step6[] = {"none", "per_slice", "cached", "high_order"};
+    const char *step7[] = {"none", "last_cached", "high_order"};
+    std::printf("{\"step2\": \"%s\", \"step2_split\": %s, \"fast_riemann\": %s, \"diag_width\": %d, "
+                "\"step4_single_walk\": %s, \"step4_has_stages\": %s, \"step4_friction\": %s, \"step4_stores_p\": %s, "
+                "\"dg\": %s, \"step5\": \"%s\", \"step5_groups\": %u, \"wide\": %s, \"has_V\": %s, \"pij_stored\": %d, "
+                "\"tiles_predicted_from_history\": %s, \"step6\": \"%s\", \"step6_flags\": %s, \"step7\": \"%s\", "
+                "\"fuse_precompute\": %s, \"checked\": %s, \"launches\": [",
+                step2[(int)p.step2], b(p.step2_split), b(p.fast_riemann), p.diag_width, b(p.step4_single_walk),
+                b(p.step4_has_stages), b(p.step4_friction), b(p.step4_stores_p), b(p.dg), step5[(int)p.step5],
+                p.step5_groups, b(p.wide), b(p.has_V), p.pij_stored, b(p.tiles_predicted_from_history),
+                step6[(int)p.step6], b(p.step6_flags), step7[(int)p.step7], b(p.fuse_precompute), b(p.checked));
+    for (int q = 8; q < argc; ++q) {
+      const uint32_t n_launch = (uint32_t)std::atoll(argv[q]);
+      const uint32_t grid_x = (n_launch + kPlanWavesPerBlock - 1) / kPlanWavesPerBlock;
+      /* gridDim.y of the step-5 launch (step5_limiter in ryujin_hip.hip): the waves that share a slice */
+      const uint32_t grid_y = p.step5 == Step5::stage0_groups
+                                  ? p.step5_groups
+                                  : (p.step5 == Step5::recompute ? p.recompute_groups(grid_x) : 1u);
+      std::printf("%s{\"n_slices\": %u, \"step5_grid_y\": %u, \"recompute_groups\": %u, \"step6_shares_slices\": %s}",
+                  q > 8 ? ", " : "", n_launch, grid_y, p.recompute_groups(grid_x), b(p.step6_shares_slices(n_launch)));
+    }
     std::printf("]}\n");
     return 0;
   }
@@ -263,5 +319,7 @@ int main(int argc, char **argv)
     return run_lattice();
   if (argc >= 2 && !std::strcmp(argv[1], "path"))
     return run_path(argc, argv);
+  if (argc >= 2 && !std::strcmp(argv[1], "plan"))
+    return run_plan(argc, argv);
   return 2;
 }

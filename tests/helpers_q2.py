@@ -61,3 +61,46 @@ def q2_periodic_offline(dim, n_elements, length=1.0):
     off.row_starts, off.columns, off.mi = row_starts, columns, mi
     off.max_row_len = max(len(r) for r in rows)
     return off, positions
+
+
+def q2_periodic_offline_sparse(dim, n_elements, length=1.0):
+    """q2_periodic_offline without the dense n x n matrices (2-D only): the same rows, columns, c_ij and m_ij entry by
+    entry from the 1-D factors, for lattices of tens of thousands of nodes (tests/test_step_plan.py compares the two on
+    a small lattice)."""
+    assert dim == 2 and n_elements >= 3
+    h = length / n_elements
+    M1, D1 = _q2_1d(n_elements, h)
+    n1 = M1.shape[0]
+    n = n1 * n1
+    nbr = [np.flatnonzero(M1[a] != 0.0) for a in range(n1)]            # ascending
+    i0, i1 = np.divmod(np.arange(n), n1)
+    counts = np.array([len(nbr[a]) for a in range(n1)])
+    widths = counts[i0] * counts[i1]
+    row_starts = np.concatenate([[0], np.cumsum(widths)]).astype(np.uint64)
+    rows_i, j0, j1 = [], [], []
+    for a in range(n1):                                               # all rows with i0 = a at once
+        for b in range(n1):
+            i = a * n1 + b
+            ja, jb = np.meshgrid(nbr[a], nbr[b], indexing="ij")       # ascending in j = ja n1 + jb
+            ja, jb = ja.reshape(-1), jb.reshape(-1)
+            diag = (ja == a) & (jb == b)
+            order = np.concatenate([np.flatnonzero(diag), np.flatnonzero(~diag)])   # diagonal first, then ascending
+            rows_i.append(np.full(order.size, i))
+            j0.append(ja[order])
+            j1.append(jb[order])
+    ii, j0, j1 = np.concatenate(rows_i), np.concatenate(j0), np.concatenate(j1)
+    e0, e1 = ii // n1, ii % n1
+    columns = (j0 * n1 + j1).astype(np.uint32)
+    mij = M1[e0, j0] * M1[e1, j1]
+    cij = np.stack([D1[e0, j0] * M1[e1, j1], M1[e0, j0] * D1[e1, j1]], axis=1)
+    mi = np.add.reduceat(mij, row_starts[:-1].astype(np.int64))
+    assert (mi > 0).all()
+    off = OfflineView(dim, 0, 0, n, n, 1, row_starts, columns, cij, mij, mi, 1.0 / mi, mi.sum(), [],
+                      np.zeros((0, dim)), [], [], [], [])
+    x1 = 0.5 * h * np.arange(n1)
+    grids = np.meshgrid(x1, x1, indexing="ij")
+    positions = np.stack([g.reshape(-1) for g in grids], axis=1)
+    off.positions = positions
+    off.row_starts, off.columns, off.mi = row_starts, columns, mi
+    off.max_row_len = int(widths.max())
+    return off, positions

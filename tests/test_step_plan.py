@@ -117,3 +117,67 @@ def test_kernel_path_of_the_benchmark_configurations(checker, key):
     assert r["pij_stored"] == (STORED[key] if first is None else 1)
     # the last sweep carries the next pre-pass on the large Euler and shallow-water meshes, never on C1 or EulerAEOS
     assert r["fuse_precompute"] == (key in ("step2d", "sw2d", "cylinder3d", "sedov3d"))
+
+
+# ---- the case table of tests/test_gpu_plan_variants.py against plan_step()
+
+import helpers_plan_cases as plan_cases  # noqa: E402
+
+
+def _checked_plan(checker, equation, off_dim, widths, n_owned, limited_fraction, stages, launch_sizes):
+    n_slices = (n_owned + 63) // 64  # host_layout.hpp: n_slices = ceil(n_owned / 64)
+    r = _run(checker, "plan", equation, off_dim, int(widths.max()), n_slices, limited_fraction, stages, *launch_sizes)
+    return n_slices, r
+
+
+def _assert_table_entry(r, n_slices, plan, step5_launches, step6_launches):
+    launches = r.pop("launches")
+    assert r == plan, {k: (r[k], plan.get(k)) for k in r if r[k] != plan.get(k)}
+    assert [dict(n_slices=q["n_slices"], grid_y=q["step5_grid_y"]) for q in launches] == step5_launches
+    assert [dict(n_slices=q["n_slices"], grid_y=1, shares_slices=q["step6_shares_slices"])
+            for q in launches] == step6_launches
+    assert sum(q["n_slices"] for q in launches) == n_slices
+
+
+@pytest.mark.parametrize("name", sorted(plan_cases.CASES) + ["erk33"])
+def test_case_table_of_the_gpu_variants_is_what_plan_step_decides(checker, name):
+    """Every entry of tests/helpers_plan_cases.py: the mesh of the case is built, n_owned and the widest row are taken
+    from it, and the plan and the per-launch decisions plan_step() makes of them must equal the table's literals -- the
+    table the GPU test holds HyperbolicModule.last_plan() against."""
+    case = plan_cases.ERK33_CASE if name == "erk33" else plan_cases.CASES[name]
+    off = case["mesh"]()
+    assert off.n_owned == case["n_points"]
+    widths = plan_cases.widths_of(off)
+    for update in (case, case["second_update"]):
+        if update is None:
+            continue
+        sizes = [q["n_slices"] for q in update["step5_launches"]]
+        n_slices, r = _checked_plan(checker, case["equation"], off.dim, widths, off.n_owned, update["limited_fraction"],
+                                    case["stages"], sizes)
+        _assert_table_entry(r, n_slices, update["plan"], update["step5_launches"], update["step6_launches"])
+
+
+def test_case_table_two_ranks(checker):
+    from ryujin_amd import offline
+    case = plan_cases.TWO_RANK_CASE
+    for rank, expected in enumerate(case["ranks"]):
+        off = offline.SyntheticOffline(offline.rectangle_2d(case["n"], case["lower"], case["upper"], n_ranks=2, rank=rank))
+        assert off.n_owned == expected["n_owned"]
+        sizes = [s for s, _, _ in expected["launches"]]
+        assert sizes[0] == (off.n_export + 63) // 64  # the export part: ceil(n_export / 64) slices
+        n_slices, r = _checked_plan(checker, case["equation"], 2, plan_cases.widths_of(off), off.n_owned, 1.0, 0, sizes)
+        _assert_table_entry(r, n_slices, case["plan"], [dict(n_slices=s, grid_y=y) for s, y, _ in expected["launches"]],
+                            [dict(n_slices=s, grid_y=1, shares_slices=b) for s, _, b in expected["launches"]])
+
+
+def test_sparse_q2_lattice_is_the_dense_one():
+    """helpers_q2.q2_periodic_offline_sparse (the lattices of the k_pij_lij_recompute cases) entry by entry against the
+    dense assembly"""
+    import numpy as np
+    from helpers_q2 import q2_periodic_offline, q2_periodic_offline_sparse
+    a, xa = q2_periodic_offline(2, 5)
+    b, xb = q2_periodic_offline_sparse(2, 5)
+    assert np.array_equal(a.row_starts, b.row_starts) and np.array_equal(a.columns, b.columns)
+    assert np.array_equal(a._keep["cij"], b._keep["cij"]) and np.array_equal(a._keep["mij"], b._keep["mij"])
+    assert np.array_equal(xa, xb) and a.max_row_len == b.max_row_len
+    np.testing.assert_allclose(a.mi, b.mi, rtol=4e-16)  # (row sums in another order)
