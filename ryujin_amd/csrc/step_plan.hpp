@@ -124,8 +124,11 @@ namespace ryujin_hip
     /* Euler, stages == 0, limiter on: P_ij (part 1) is recomputed in step 5 instead of stored in step 4.
      * A/B on MI355X: -7 % per update in 2-D (k=4, 9 columns). In 3-D (k=5, 27 columns) step 4 drops from 2.01
      * to 1.34 ms on 4.2 M gridpoints but step 5 grows from 2.16 to 2.77-2.94 ms (27 flux evaluations per row at
-     * 240 registers): -0.7 % ... +1.5 % per update, inside the run-to-run spread -- so only for dim <= 2. */
-    const bool recompute_p = is_euler && in.dim <= 2 && in.stages == 0 && n_iterations != 0 && !in.dg;
+     * 240 registers): -0.7 % ... +1.5 % per update, inside the run-to-run spread -- so only for dim <= 2.
+     * Rows of at most 64 entries: k_pij_lij_recompute keeps the undecided pairs of a row in ONE 64-bit mask indexed by
+     * the column (wider rows take k_pij_lij<WIDE>, which walks the columns in blocks of 63). */
+    const bool recompute_p =
+        is_euler && in.dim <= 2 && in.stages == 0 && n_iterations != 0 && !in.dg && in.max_row_len <= 64;
     /* Euler and EulerAEOS, stages == 0, Q1 stencil widths: step 4 does not touch P_ij; step 5 forms it once from
      * d_ij, m_ij and the per-node vectors, limits it and stores it for steps 6 and 7 (kernels_limiter_stage0.hpp)
      * -- any dimension */
@@ -212,6 +215,8 @@ namespace ryujin_hip
       p.violated = "step plan: P_ij per tile needs V_i, one wave per slice and dim <= 2";
     else if (p.per_slice() && !(p.has_V && p.step5 == StepPlan::Step5::stage0_per_slice))
       p.violated = "step plan: P_ij per slice needs V_i";
+    else if (p.wide && p.step5 != StepPlan::Step5::none && p.step5 != StepPlan::Step5::pij_lij)
+      p.violated = "step plan: rows of more than 64 entries need k_pij_lij<WIDE> in step 5";
     else if (p.checked && p.pij_stored != 1)
       p.violated = "step plan: the checked kernels read all of P_ij";
     return p;

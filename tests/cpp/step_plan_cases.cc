@@ -4,11 +4,13 @@
 //   step_plan_cases path equation dim max_row_len n_slices limited_fraction [resident_waves5 resident_waves6 fold]
 //                               the kernel path of one configuration (defaults of create()) as JSON: one name per launch
 //                               of a one-launch sweep, as rocprofv3 prints it
-//   step_plan_cases plan equation dim max_row_len n_slices limited_fraction stages [n_launch_slices ...]
+//   step_plan_cases plan equation dim max_row_len n_slices limited_fraction stages [n_launch_slices ...] [key=1 ...]
 //                               every field of the plan of one configuration (defaults of create(), a step() outside
 //                               the device-resident driver: no pending pre-pass) under the names of
 //                               HyperbolicModule.last_plan(), and per given launch size what the sweeps of steps 5
-//                               and 6 make of it: gridDim.y of step 5, whether step 6 shares slices
+//                               and 6 make of it: gridDim.y of step 5, whether step 6 shares slices. Options:
+//                               newton=N (riemann_newton_max_iterations), checked=1 (debug_expensive_bounds_check),
+//                               friction=1 (a Manning coefficient), no_split=1 (debug_no_small_mesh_split)
 // (test infrastructure; built by tests/test_step_plan.py)
 #include <cstdio>
 #include <cstdlib>
@@ -157,6 +159,27 @@ namespace
       return 2;
     StepPlanInput in = default_input(argv);
     in.stages = std::atoi(argv[7]);
+    std::vector<const char *> sizes;
+    for (int q = 8; q < argc; ++q) {
+      const char *eq = std::strchr(argv[q], '=');
+      if (eq == nullptr) {
+        sizes.push_back(argv[q]);
+        continue;
+      }
+      const std::string key(argv[q], eq - argv[q]);
+      const int value = std::atoi(eq + 1);
+      if (key == "newton")
+        in.riemann_newton_max_iterations = value;
+      else if (key == "checked")
+        in.checked = value != 0;
+      else if (key == "friction")
+        in.friction = value != 0;
+      else if (key == "no_split") {
+        if (value != 0)
+          in.resident_waves_step5 = in.resident_waves_step6 = 0; /* as create() */
+      } else
+        return 2;
+    }
     const StepPlan p = plan_step(in);
     if (p.unsupported || p.violated) {
       std::fprintf(stderr, "%s\n", p.unsupported ? p.unsupported : p.violated);
@@ -175,15 +198,15 @@ namespace
                 b(p.step4_has_stages), b(p.step4_friction), b(p.step4_stores_p), b(p.dg), step5[(int)p.step5],
                 p.step5_groups, b(p.wide), b(p.has_V), p.pij_stored, b(p.tiles_predicted_from_history),
                 step6[(int)p.step6], b(p.step6_flags), step7[(int)p.step7], b(p.fuse_precompute), b(p.checked));
-    for (int q = 8; q < argc; ++q) {
-      const uint32_t n_launch = (uint32_t)std::atoll(argv[q]);
+    for (size_t q = 0; q < sizes.size(); ++q) {
+      const uint32_t n_launch = (uint32_t)std::atoll(sizes[q]);
       const uint32_t grid_x = (n_launch + kPlanWavesPerBlock - 1) / kPlanWavesPerBlock;
       /* gridDim.y of the step-5 launch (step5_limiter in ryujin_hip.hip): the waves that share a slice */
       const uint32_t grid_y = p.step5 == Step5::stage0_groups
                                   ? p.step5_groups
                                   : (p.step5 == Step5::recompute ? p.recompute_groups(grid_x) : 1u);
       std::printf("%s{\"n_slices\": %u, \"step5_grid_y\": %u, \"recompute_groups\": %u, \"step6_shares_slices\": %s}",
-                  q > 8 ? ", " : "", n_launch, grid_y, p.recompute_groups(grid_x), b(p.step6_shares_slices(n_launch)));
+                  q > 0 ? ", " : "", n_launch, grid_y, p.recompute_groups(grid_x), b(p.step6_shares_slices(n_launch)));
     }
     std::printf("]}\n");
     return 0;
@@ -267,6 +290,8 @@ namespace
                             fail("the step-5 kernel and the storage mode agree");
                           if (in.checked && p.pij_stored != 1)
                             fail("the checked build stores P_ij everywhere");
+                          if (p.wide && !(p.step5 == Step5::none || p.step5 == Step5::pij_lij))
+                            fail("rows of more than 64 entries take k_pij_lij<WIDE>, the one step-5 kernel with blocks");
                           if (p.tiles_predicted_from_history && !p.per_tile())
                             fail("tiles are predicted only where they are stored per tile");
                           if (p.step4_stores_p != !(p.step5 == Step5::recompute || stage0))

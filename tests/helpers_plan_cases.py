@@ -29,12 +29,12 @@ def perturbed(U, seed=42, amp=1e-3):
 
 def _plan(step2, diag_width, step5, step5_groups, has_V, pij_stored, step6, step6_flags, step7="last_cached", *,
           step2_split=False, fast_riemann=False, step4_single_walk=False, step4_has_stages=False, step4_stores_p=True,
-          tiles_predicted_from_history=False):
+          tiles_predicted_from_history=False, wide=False, step4_friction=False, checked=False):
     return dict(step2=step2, step2_split=step2_split, fast_riemann=fast_riemann, diag_width=diag_width,
-                step4_single_walk=step4_single_walk, step4_has_stages=step4_has_stages, step4_friction=False,
-                step4_stores_p=step4_stores_p, dg=False, step5=step5, step5_groups=step5_groups, wide=False,
+                step4_single_walk=step4_single_walk, step4_has_stages=step4_has_stages, step4_friction=step4_friction,
+                step4_stores_p=step4_stores_p, dg=False, step5=step5, step5_groups=step5_groups, wide=wide,
                 has_V=has_V, pij_stored=pij_stored, tiles_predicted_from_history=tiles_predicted_from_history,
-                step6=step6, step6_flags=step6_flags, step7=step7, fuse_precompute=False, checked=False)
+                step6=step6, step6_flags=step6_flags, step7=step7, fuse_precompute=False, checked=checked)
 
 
 def _euler_groups(width, groups):

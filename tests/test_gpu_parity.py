@@ -1183,36 +1183,14 @@ def test_wide_ragged_stencil_generic_kernels(oracle):
     """Stencils wider than anything a Q1 mesh produces (up to 49 entries per row, strongly ragged near
     the boundary): exercises the generic, non-unrolled sweeps (k_dij_alpha, k_dij_diag, the two-pass
     k_high_order) and the 64-entry limit of a SELL-64 slice. The matrices are synthetic but consistent
-    (c_ij = -c_ji, m_ij = m_ji > 0, m_i = sum_j m_ij), which is all step() relies on."""
-    from helpers_layout import OfflineView
-    nx = ny = 24
-    R = 3                                   # (2R+1)^2 = 49 entries in the interior
-    h = 1.0 / nx
-    idx = lambda ix, iy: iy * nx + ix       # noqa: E731
-    rows, cij, mij = [], [], []
-    for iy in range(ny):
-        for ix in range(nx):
-            i = idx(ix, iy)
-            nb = []
-            for dy in range(-R, R + 1):
-                for dx in range(-R, R + 1):
-                    jx, jy = ix + dx, iy + dy
-                    if (dx, dy) != (0, 0) and 0 <= jx < nx and 0 <= jy < ny:
-                        w = h * h / (1.0 + dx * dx + dy * dy) ** 2
-                        nb.append((idx(jx, jy), (0.5 * h * w / (h * h) * dx, 0.5 * h * w / (h * h) * dy), w / 9.0))
-            nb.sort()
-            rows.append([i] + [j for j, _, _ in nb])
-            cij.extend([(0.0, 0.0)] + [c for _, c, _ in nb])
-            mij.extend([h * h * 0.5] + [m for _, _, m in nb])
-    n = nx * ny
-    row_starts = np.cumsum([0] + [len(r) for r in rows]).astype(np.uint64)
+    (c_ij = -c_ji, m_ij = m_ji > 0, m_i = sum_j m_ij), which is all step() relies on: the lattice generator of
+    tests/helpers_row_width.py."""
+    import helpers_row_width as rw
+    # 7 x 7 stencils, 49 entries in the interior, on a 24 x 24 lattice open in both directions
+    off = rw.lattice_offline((24, 24), 49, open_axes=(0, 1), norm="max")
+    rows = np.split(off.columns, off.row_starts[1:-1].astype(np.int64))
     assert max(len(r) for r in rows) == 49 and min(len(r) for r in rows) == 16
-    columns = np.concatenate([np.array(r, dtype=np.uint32) for r in rows])
-    mij = np.array(mij)
-    mi = np.add.reduceat(mij, row_starts[:-1].astype(np.int64))
-    off = OfflineView(2, 0, 0, n, n, 1, row_starts, columns, np.array(cij), mij, mi, 1.0 / mi, mi.sum(),
-                      [], np.zeros((0, 2)), [], [], [], [])
-    pos = np.array([[(ix + 0.5) * h, (iy + 0.5) * h] for iy in range(ny) for ix in range(nx)])
+    pos = off.positions
     U0 = _perturbed(euler_radial_contrast(pos, inner=(1.0, 0.0, 5.0), outer=(0.5, 0.0, 0.5), radius=0.25,
                                           center=(0.5, 0.5)))
     mods = []
@@ -1228,7 +1206,6 @@ def test_wide_ragged_stencil_generic_kernels(oracle):
                 old, new = new, old
             U_start = old.download()
         mods.append((m, old, new))
-    off.row_starts = row_starts
     _compare_step(off, mods)
 
 

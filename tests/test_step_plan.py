@@ -181,3 +181,46 @@ def test_sparse_q2_lattice_is_the_dense_one():
     assert np.array_equal(a._keep["cij"], b._keep["cij"]) and np.array_equal(a._keep["mij"], b._keep["mij"])
     assert np.array_equal(xa, xb) and a.max_row_len == b.max_row_len
     np.testing.assert_allclose(a.mi, b.mi, rtol=4e-16)  # (row sums in another order)
+
+
+# ---- the case table of tests/test_gpu_row_widths.py against plan_step()
+
+import helpers_row_width_cases as width_cases  # noqa: E402
+
+
+@pytest.mark.parametrize("name", sorted(width_cases.CASES))
+def test_case_table_of_the_row_widths_is_what_plan_step_decides(checker, name):
+    """Every entry of tests/helpers_row_width_cases.py: the lattice of the case is built, n_owned and the widest row are
+    taken from it, and the plan and the launches plan_step() makes of them -- with the case's parameter edits, and once
+    more with debug_no_small_mesh_split where the case runs twice -- must equal the table's literals."""
+    case = width_cases.CASES[name]
+    off = case["mesh"]()
+    assert off.n_owned == case["n_points"]
+    widths = plan_cases.widths_of(off)
+    assert widths.max() == case["width"]
+    for run, launches in enumerate(case["runs"]):
+        sizes = [q["n_slices"] for q in launches["step5_launches"]]
+        options = case["options"] + (("no_split=1",) if run == 1 else ())
+        n_slices, r = _checked_plan(checker, case["equation"], off.dim, widths, off.n_owned, 1.0, case["stages"],
+                                    sizes + list(options))
+        _assert_table_entry(r, n_slices, case["plan"], launches["step5_launches"], launches["step6_launches"])
+    assert len(case["runs"]) == (2 if case["plan"]["step5"] == "recompute" and off.dim == 2 and
+                                 case["plan"]["fast_riemann"] else 1)
+
+
+def test_euler_aeos_with_33_entries_is_refused_and_32_is_not(checker):
+    refused = width_cases.AEOS_REFUSED
+    out = subprocess.run([checker, "plan", "euler_aeos", "2", str(refused["width"]), "15", "1.0", "0", "15"],
+                         capture_output=True, text=True)
+    assert out.returncode == 1 and out.stderr.strip() == refused["message"]
+    off = width_cases._lattice(refused["shape"], refused["width"])()
+    assert plan_cases.widths_of(off).max() == 33 and refused["accepted"]["width"] == 32
+
+
+def test_wide_rows_never_take_the_recompute_kernel(checker):
+    """k_pij_lij_recompute keeps the undecided pairs of a row in one 64-bit mask indexed by the column: Euler up to two
+    dimensions leaves it at 65 entries for k_pij_lij<WIDE> (found by euler_2d_65 of tests/test_gpu_row_widths.py)"""
+    for dim in (1, 2):
+        assert _run(checker, "plan", "euler", dim, 64, 15, 1.0, 0, 15)["step5"] == "recompute"
+        r = _run(checker, "plan", "euler", dim, 65, 15, 1.0, 0, 15)
+        assert r["step5"] == "pij_lij" and r["wide"] and r["step4_stores_p"] and r["has_V"]
