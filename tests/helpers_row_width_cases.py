@@ -49,13 +49,24 @@ def _ring(n, width):
     """1-D: a ring (the row sums of an open chain vanish only with c_ij of both signs that cancel across every cut).
     Rows of width - 2 or width - 3 entries, widened in every slice: the nodes a with 8 <= a mod 64 < 24 are paired with
     a + s, s the first offset beyond the stencil -- one or two more entries per row --, and for an even width the nodes
-    14 and 14 + s + 1 mod 64 with each other."""
+    14 and 14 + s + 1 mod 64 with each other.
+    More than 64 entries (s >= 32: the run and its partners a + s no longer overlap, no row would get two more entries):
+    every node of the run is paired with a + s AND a + s + 1, all indices modulo n -- the run has the full width, its
+    partners one or two entries more than the other rows --, and for an even width the nodes 14 mod 64 with a + s + 2 as
+    well; s is raised until s mod 64 lies in [17, 38], so that no partner is a node of another slice's run."""
     def make():
         base = width - 2 if width % 2 else width - 3
         s = (base - 1) // 2 + 1
         a = np.arange(n)
         if base == 1:   # width 4: rows of three entries, a single pair per slice
             base, pairs = 3, np.stack([a[a % 64 == 10], a[a % 64 == 10] + 2], axis=1)
+        elif width > 64:
+            while not 17 <= s % 64 <= 38:   # the partners 8 + s ... 23 + s + 2 stay clear of the runs of other slices
+                s += 1
+            run, extra = a[(a % 64 >= 8) & (a % 64 < 24)], a[a % 64 == 14]
+            pairs = np.concatenate([np.stack([run, (run + s) % n], axis=1), np.stack([run, (run + s + 1) % n], axis=1)])
+            if width % 2 == 0:
+                pairs = np.concatenate([pairs, np.stack([extra, (extra + s + 2) % n], axis=1)])
         else:
             run = a[(a % 64 >= 8) & (a % 64 < 24)]
             pairs = np.stack([run, run + s], axis=1)
@@ -96,9 +107,12 @@ def extremal_nodes(off):
     return np.unique(np.asarray(nodes, dtype=np.int64))
 
 
-def _extrema(off, compress, expand):
+def _extrema(off, compress, expand, more=None):
+    """`more`: further nodes, as a function of the offline data (the multi-rank cases place extrema next to a cut)"""
     def after_warm(U):
         nodes = extremal_nodes(off)
+        if more is not None:
+            nodes = np.unique(np.concatenate([nodes, np.asarray(more(off), dtype=np.int64)]))
         up = np.isin(np.arange(len(nodes)) % 4, (0, 3))   # (rows and their neighbours alternate in the list)
         U[nodes[up]] = compress(U[nodes[up]])
         U[nodes[~up]] = expand(U[nodes[~up]])
@@ -106,7 +120,7 @@ def _extrema(off, compress, expand):
     return after_warm
 
 
-def _euler_patches(off):
+def _euler_patches(off, more=None):
     t = _patch_table(off, 2)
     v = np.zeros((off.n_owned, off.dim))
     v[:, 0] = 0.5
@@ -114,10 +128,10 @@ def _euler_patches(off):
         v[:, 1] = -0.25
     f = np.array([2.0] * (off.dim + 1) + [4.0])   # twice the density and momentum, four times the energy
     return dict(U0=euler_from_primitive(1.0 + 0.5 * t[:, 0], v, 1.0 + 2.0 * t[:, 1]), dirichlet=None,
-                after_warm=_extrema(off, lambda U: U * f, lambda U: U / f))
+                after_warm=_extrema(off, lambda U: U * f, lambda U: U / f, more))
 
 
-def _sw_patches(off):
+def _sw_patches(off, more=None):
     """water of depth 1 ... 1.5 over a smooth bathymetry (ryujin_hip_offline::initial_precomputed), a uniform discharge"""
     x = off.positions
     Z = 0.1 * np.cos(2.0 * np.pi * x[:, 0]) * (np.sin(2.0 * np.pi * x[:, 1] + 0.3) if off.dim > 1 else 1.0)
@@ -125,16 +139,16 @@ def _sw_patches(off):
     U0 = np.zeros((off.n_owned, off.dim + 1))
     U0[:, 0] = 1.0 + 0.5 * _patch_table(off, 1)[:, 0]
     U0[:, 1] = 0.3 * U0[:, 0]
-    return dict(U0=U0, dirichlet=None, after_warm=_extrema(off, lambda U: 2.0 * U, lambda U: 0.5 * U))
+    return dict(U0=U0, dirichlet=None, after_warm=_extrema(off, lambda U: 2.0 * U, lambda U: 0.5 * U, more))
 
 
-def _scalar_patches(off):
+def _scalar_patches(off, more=None):
     """values in (0.5, 2.5) around a smooth wave: nowhere constant (the KPP flux is transcendental; in constant regions
     the Roe average of the reference amplifies last-bit differences, helpers_plan_cases._kpp)"""
     x = off.positions
     u = 1.5 + 0.5 * np.sin(2.0 * np.pi * x[:, 0]) * np.cos(2.0 * np.pi * x[:, 1] + 0.3) + \
         0.5 * (_patch_table(off, 1)[:, 0] - 0.5)
-    return dict(U0=u.reshape(-1, 1), dirichlet=None, after_warm=_extrema(off, lambda U: U + 1.0, lambda U: U - 1.0))
+    return dict(U0=u.reshape(-1, 1), dirichlet=None, after_warm=_extrema(off, lambda U: U + 1.0, lambda U: U - 1.0, more))
 
 
 # ------------------------------------------------------------------ parameter edits
@@ -203,6 +217,9 @@ R, D, F, T = "records", "dij_alpha", False, True
 _entry("euler_1d_4", LINE, 10, 4, "euler", _euler_patches, _euler_recompute(R, 9), (4,))
 _entry("euler_1d_9", LINE, 10, 9, "euler", _euler_patches, _euler_recompute(R, 9), (4,))
 _entry("euler_1d_10", LINE, 10, 10, "euler", _euler_patches, _euler_recompute(R, 27), (4,))
+# ... and k_pij_lij<Euler<1>, false, true> above 64 entries: two blocks, and a third block of one column
+for _w in (65, 128):
+    _entry(f"euler_1d_{_w}", LINE, 10, _w, "euler", _euler_patches, _stored(D, 0, T, fast_riemann=True))
 # 2-D: k_pij_lij_recompute up to 64 entries -- <2, 4> on these 15 slices, <2, 1> with debug_no_small_mesh_split --,
 # k_pij_lij<Euler<2>, false, true> above
 for _w, _step2, _diag in ((10, R, 27), (27, R, 27), (28, R, 0), (32, R, 0), (33, D, 0), (64, D, 0)):
@@ -229,6 +246,7 @@ _entry("euler_2d_erk33_128", PLANE, 15, 128, "euler", _euler_patches,
 
 # shallow water: bathymetry in the precomputed values, Manning friction in the 33 case; the two walks of step 4
 _entry("sw_1d_4", LINE, 10, 4, "shallow_water", _sw_patches, _stored(R, 9, F))
+_entry("sw_1d_65", LINE, 10, 65, "shallow_water", _sw_patches, _stored(D, 0, T))
 for _w, _step2, _diag, _wide in ((10, R, 27, F), (32, R, 0, F), (64, D, 0, F), (65, D, 0, T), (128, D, 0, T)):
     _entry(f"sw_2d_{_w}", PLANE, 15, _w, "shallow_water", _sw_patches, _stored(_step2, _diag, _wide))
 _entry("sw_2d_33", PLANE, 15, 33, "shallow_water", _sw_patches, _stored(D, 0, F, step4_friction=True), edit=_manning,

@@ -155,12 +155,12 @@ def partition(off, info, owner, bathymetry=None):
             keep = rows[g][1:] if owner[g] == r else [j for j in rows[g][1:] if owner[j] == r]
             cols = sorted(keep, key=lambda j: lidx[j])
             lrows.append([lidx[g]] + [lidx[j] for j in cols])
-            for j in [g] + cols:
-                lc.append(off.cij_csr[entry[(g, j)]])
-                lm.append(off.mij_csr[entry[(g, j)]])
-                if dg is not None:
-                    l_inc.append(dg[0][entry[(g, j)]])
-                    l_minv.append(dg[1][entry[(g, j)]])
+            at = [entry[(g, j)] for j in [g] + cols]   # (one gather per row: rows of a thousand entries occur)
+            lc.append(off.cij_csr[at])
+            lm.append(off.mij_csr[at])
+            if dg is not None:
+                l_inc.append(dg[0][at])
+                l_minv.append(dg[1][at])
         row_starts = np.cumsum([0] + [len(x) for x in lrows]).astype(np.uint64)
         columns = np.concatenate([np.array(x, dtype=np.uint32) for x in lrows])
         send_off, send_idx, row_send_off, row_send_row, row_send_col = [0], [], [0], [], []
@@ -183,7 +183,8 @@ def partition(off, info, owner, bathymetry=None):
                 if is_bdry[l2g[lrows[i][c]]]:
                     p_i.append(i), p_col.append(c), p_j.append(lrows[i][c])
         mi = off.mi[l2g]
-        v = OfflineView(off.dim, n_export, n_owned, n_owned, len(l2g), 1, row_starts, columns, np.array(lc), np.array(lm),
+        v = OfflineView(off.dim, n_export, n_owned, n_owned, len(l2g), 1, row_starts, columns, np.concatenate(lc),
+                        np.concatenate(lm),
                         mi, 1.0 / mi, off.measure_of_omega, b_i, g_normal[b_g].reshape(-1, off.dim), g_id[b_g],
                         p_i, p_col, p_j)
         k = v._keep
@@ -199,7 +200,7 @@ def partition(off, info, owner, bathymetry=None):
             setattr(o, name, capi.as_ptr(k[name], capi.c_u32_p))
         if dg is not None:
             from helpers_dg import attach_dg
-            attach_dg(v, np.array(l_inc), np.array(l_minv))
+            attach_dg(v, np.concatenate(l_inc), np.concatenate(l_minv))
         v.positions = off.positions[l2g]
         v.global_ids = np.array(l2g, dtype=np.int64)
         v.b_positions = off.positions[b_g].reshape(-1, off.dim)

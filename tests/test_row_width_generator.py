@@ -93,3 +93,17 @@ def test_the_oracle_alone_covers_the_columns(oracle, name):
     first_pass = cases.oracle_first_pass(case, oracle, off, dirichlet, states, weights, tau)
     covered = cases.coverage(off, first_pass, case["width"])
     assert min(covered.values()) > 0, {k: v for k, v in covered.items() if v == 0}
+
+
+@pytest.mark.parametrize("name", ["euler_1d_65", "euler_1d_128", "sw_1d_65"])
+def test_rings_of_more_than_64_entries(name):
+    """the rings with two partners per widened node, all indices modulo n (tests/helpers_row_width_cases.py: _ring): the
+    widest row has exactly the requested width -- not 64 --, and EVERY slice of 64 rows holds rows of at least three
+    widths, the widest among them"""
+    case = cases.CASES[name]
+    off = _mesh(name)
+    widths = rw.check_consistency(off, case["width"])
+    assert widths.max() == case["width"] and case["n_points"] % 64 == 0
+    for s in range(case["n_points"] // 64):
+        in_slice = widths[64 * s: 64 * s + 64]
+        assert len(np.unique(in_slice)) >= 3 and in_slice.max() == case["width"], (s, np.unique(in_slice))

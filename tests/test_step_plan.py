@@ -224,3 +224,38 @@ def test_wide_rows_never_take_the_recompute_kernel(checker):
         assert _run(checker, "plan", "euler", dim, 64, 15, 1.0, 0, 15)["step5"] == "recompute"
         r = _run(checker, "plan", "euler", dim, 65, 15, 1.0, 0, 15)
         assert r["step5"] == "pij_lij" and r["wide"] and r["step4_stores_p"] and r["has_V"]
+
+
+def test_one_dimensional_rows_of_more_than_64_entries_take_the_wide_kernels(checker):
+    """euler_1d_65, euler_1d_128 and sw_1d_65 of the table: `wide`, k_pij_lij<..<1>, false, true> and k_high_order, by
+    the names rocprofv3 prints"""
+    for name, E in (("euler_1d_65", "Euler<1>"), ("euler_1d_128", "Euler<1>"), ("sw_1d_65", "ShallowWater<1>")):
+        case = width_cases.CASES[name]
+        assert case["plan"]["wide"] and case["plan"]["step5"] == "pij_lij" and case["plan"]["step6"] == "high_order"
+        r = _run(checker, "path", case["equation"], 1, case["width"], 10, 1.0)
+        assert r["kernels"][-3:] == [f"k_pij_lij<{E}, false, true>", f"k_high_order<{E}, false, true>",
+                                     f"k_high_order<{E}, true, false>"], r
+
+
+# ---- the multi-rank case table of tests/test_gpu_row_widths_ranks.py against plan_step()
+
+import helpers_row_width_ranks as rank_cases  # noqa: E402
+
+
+@pytest.mark.parametrize("name", sorted(rank_cases.RANK_CASES))
+def test_case_table_of_the_row_widths_on_ranks_is_what_plan_step_decides(checker, oracle, name):
+    """Every rank of every entry of tests/helpers_row_width_ranks.py: the lattice is partitioned, the rank's widest
+    owned row and slice count go to plan_step() with the case's parameter edits, and the plan and what the export and
+    the interior launch make of it must equal the table's literals. The export part is ceil(n_export / 64) slices
+    (ryujin_hip_ctx::sweep); a rank without an interior part has one launch."""
+    built = rank_cases.built(name, oracle)
+    case = built["case"]
+    for view, expected in zip(built["views"], case["ranks"]):
+        assert (view.n_owned, view.n_export) == (expected["n_owned"], expected["n_export"])
+        sizes = [s for s, _, _ in expected["launches"]]
+        n_all = (view.n_owned + 63) // 64
+        assert sizes[0] == min(n_all, (view.n_export + 63) // 64) and len(sizes) == (2 if sizes[0] < n_all else 1)
+        n_slices, r = _checked_plan(checker, case["equation"], built["off"].dim, plan_cases.widths_of(view), view.n_owned,
+                                    1.0, 0, sizes + list(case["options"]))
+        _assert_table_entry(r, n_slices, case["plan"], [dict(n_slices=s, grid_y=y) for s, y, _ in expected["launches"]],
+                            [dict(n_slices=s, grid_y=1, shares_slices=b) for s, _, b in expected["launches"]])
