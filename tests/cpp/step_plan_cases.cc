@@ -10,7 +10,8 @@
 //                               HyperbolicModule.last_plan(), and per given launch size what the sweeps of steps 5
 //                               and 6 make of it: gridDim.y of step 5, whether step 6 shares slices. Options:
 //                               newton=N (riemann_newton_max_iterations), checked=1 (debug_expensive_bounds_check),
-//                               friction=1 (a Manning coefficient), no_split=1 (debug_no_small_mesh_split)
+//                               friction=1 (a Manning coefficient), no_split=1 (debug_no_small_mesh_split),
+//                               dg=1 (the discontinuous ansatz)
 // (test infrastructure; built by tests/test_step_plan.py)
 #include <cstdio>
 #include <cstdlib>
@@ -174,6 +175,8 @@ namespace
         in.checked = value != 0;
       else if (key == "friction")
         in.friction = value != 0;
+      else if (key == "dg")
+        in.dg = value != 0;
       else if (key == "no_split") {
         if (value != 0)
           in.resident_waves_step5 = in.resident_waves_step6 = 0; /* as create() */

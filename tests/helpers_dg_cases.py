@@ -1,0 +1,563 @@
+"""The case table of tests/test_gpu_dg_variants.py: the DISCONTINUOUS-ansatz branch of step() -- k_low_order*<.., DG = true>
+with and without stage vectors, the bounds combined over the stencil, k_pij_lij<E, DG = true, WIDE> -- in one to three
+dimensions, on rows of up to 189 entries.
+
+Two kinds of meshes:
+  real dG stencils (tests/helpers_dg.py: dg_offline): dG-Q1 and dG-Q2 on tensor-product meshes, the degree-2 ones graded
+    -- m_i, (M^-1)_ij and the incidence values vary from cell to cell, the incidence is fractional. Rows of 6 / 9 (1-D),
+    12 - 20 / 27 - 45 (2-D), 32 - 56 / 108 - 189 (3-D) entries, most of them structural zeros;
+  synthetic dG data on the lattices of tests/helpers_row_width_cases.py (synthetic_dg): every entry of the row couples,
+    the widest row sits exactly at a block boundary of the wide kernels (64 | 65, 127 | 128).
+
+An entry holds, as helpers_row_width_cases.py: mesh recipe, Description, data, the warm-up ON THE ORACLE and, as literals,
+the plan and the launches the update must run; tests/test_step_plan.py pins the literals against plan_step() (`dg=1`).
+Every single-rank case is compared TWICE (compared_states): as the first update of a fresh context and as its second --
+the bounds buffers are swapped once per update, so both pointer parities are compared, in the checked kernels too.
+
+What a case must show on the oracle alone before it counts (tests/test_dg_cases_cpu.py, asserted again on the GPU):
+  status 0 and no warning; coverage(): first-pass l_ij strictly between 0 and 1 in every block of 63 column positions, in
+  the first and the last column position of every block, in the last column of a widest row and in rows of every width;
+  incidence_arms(): both arms of fmax((alpha_i + alpha_j) / 2, incidence_ij) decide somewhere (degree 2 and synthetic;
+  for dG-Q1 the incidence is 0 or 1, the second arm cannot lose with a positive value: not applicable);
+  dg_branch_effect(): the same data without the discontinuous ansatz gives another U_new.
+On a REAL dG stencil the column positions are not alike: an entry (i, j) with j in a face neighbour's cell and off the
+common face has c_ij = m_ij = (M^-1)_ij = 0, its P_ij is exactly 0 and its l_ij exactly 1 whatever the data -- among them
+position 1 of every row with a lower neighbour and the last position of every row with an upper one. There the
+conditions on "the first / the last column" are stated for the first / last position of the block (of a widest row) that
+holds a structurally non-zero entry in some row; on the synthetic data they are the plain ones."""
+from __future__ import annotations
+
+import numpy as np
+
+import helpers_row_width as rw
+import helpers_row_width_cases as width_cases
+from helpers_dg import attach_dg, dg_offline, graded
+from helpers_plan_cases import _case, _plan
+from helpers_row_width_cases import BLOCK, summation_slack  # noqa: F401 -- re-exported for the tests
+from ryujin_amd import HyperbolicModule, capi
+
+R, D, A = "records", "dij_alpha", "alpha_then_dij"
+
+
+# ------------------------------------------------------------------ meshes
+
+def _dg_mesh(n_cells, degree, grade=False, boundary_id=capi.BC_DO_NOTHING):
+    def make():
+        h = tuple(graded(k, 1.6 + 0.3 * d) for d, k in enumerate(n_cells)) if grade else 1.0 / n_cells[0]
+        off, info = dg_offline(n_cells, h, degree, boundary_id)
+        off.dg_info = info
+        return off
+    return make
+
+
+def synthetic_dg(off, seed=5):
+    """attach dG matrices to a lattice: a symmetric incidence matrix, uniform in [0, 1] per unordered pair and 0 on the
+    diagonal; (M^-1)_ii = 1 / m_i, (M^-1)_ij = -kappa_ij m_ij / (m_i m_j) with kappa_ij = kappa_ji uniform in [0.5, 1.5]:
+    b_ij = m_i (M^-1)_ij = -b_ji keeps P_ij = -P_ji, and differs from the continuous Neumann term"""
+    tr = rw.transposed_entries(off)
+    widths = rw.widths_of(off)
+    rows = np.repeat(np.arange(off.n_owned), widths)
+    cols = np.asarray(off.columns).astype(np.int64)
+    pair = np.minimum(np.arange(len(cols)), tr)   # one draw per unordered pair
+    rng = np.random.default_rng(seed)
+    incidence = np.where(rows == cols, 0.0, rng.uniform(0.0, 1.0, len(cols))[pair])
+    kappa = rng.uniform(0.5, 1.5, len(cols))[pair]
+    mi = np.asarray(off.mi)
+    minv = np.where(rows == cols, 1.0 / mi[rows], -kappa * np.asarray(off.mij) / (mi[rows] * mi[cols]))
+    attach_dg(off, incidence, minv)
+    return off
+
+
+def _synthetic_mesh(basis):
+    inner = width_cases.CASES[basis]["mesh"]
+    return lambda: synthetic_dg(inner())
+
+
+# ------------------------------------------------------------------ data
+
+def _bump(positions, centre, radius):
+    r2 = ((positions - np.asarray(centre)) ** 2).sum(1) / radius ** 2
+    return np.where(r2 < 1.0, np.exp(1.0 - 1.0 / np.maximum(1.0 - r2, 1e-300)), 0.0)
+
+
+def _euler_blast(centre=0.45, radius=0.18, dirichlet=False):
+    """the blast of tests/test_dg_q1.py: a smooth compact pressure / density bump, gamma = 7/5; centre: one number
+    (every axis) or a point -- next to the boundary for the slip and Dirichlet cases"""
+    def data(off):
+        c = [centre] * off.dim if np.isscalar(centre) else centre
+        bump = _bump(off.positions, c, radius)
+        U = np.zeros((off.n_owned, off.dim + 2))
+        U[:, 0] = 1.0 + 0.6 * bump
+        U[:, -1] = (1.0 + 4.0 * bump) / 0.4
+        return dict(U0=U, dirichlet=U[np.asarray(off._keep["b_i"]).astype(np.int64)] if dirichlet else None)
+    return data
+
+
+def _sw_hump(centre=0.45, radius=0.18):
+    """water at rest over a smooth bathymetry with a compact hump of the free surface"""
+    def data(off):
+        x = off.positions
+        Z = 0.15 * np.cos(4.0 * x[:, 0]) ** 2
+        off.set_initial_precomputed(Z)
+        U = np.zeros((off.n_owned, off.dim + 1))
+        U[:, 0] = 1.0 + 0.4 * _bump(x, [centre] * off.dim, radius) - Z
+        return dict(U0=U, dirichlet=None)
+    return data
+
+
+def _on_the_face_columns(off, per_width=6, n_widest=48):
+    """further nodes made extrema after the warm-up. On a dG stencil: node 0 (the one cell without a lower neighbour: its
+    rows hold the own cell from column position 1 on), and of up to `n_widest` widest rows the nodes of their first and last
+    structurally non-zero columns. On every mesh: `per_width` rows of every width, spread over the mesh, and of those
+    widest rows the nodes in the first and the last column of every block of 63."""
+    widths, rs, rows, position = _pattern(off)
+    cols = np.asarray(off.columns).astype(np.int64)
+    nodes = [0]
+    for w in np.unique(widths):
+        of_width = np.flatnonzero(widths == w)
+        nodes.extend(of_width[np.unique(np.linspace(0, len(of_width) - 1, min(per_width, len(of_width))).astype(np.int64))])
+    widest = np.flatnonzero(widths == widths.max())
+    widest = widest[np.unique(np.linspace(0, len(widest) - 1, min(n_widest, len(widest))).astype(np.int64))]
+    held = structurally_nonzero(off)
+    for q, i in enumerate(widest):
+        e = np.arange(rs[i] + 1, rs[i + 1])
+        e = e[held[e]]
+        at = {e[0], e[-1]}
+        for first in range(1, widths[i], BLOCK):
+            at.update((rs[i] + first, rs[i] + min(first + BLOCK, widths[i]) - 1))
+        nodes.extend(cols[sorted(at)][q % 2::2])   # (alternately: neighbouring extrema would shield each other)
+    return np.unique(np.asarray(nodes, dtype=np.int64))
+
+
+def _with_extrema(data, compress, expand):
+    def recipe(off):
+        out = data(off)
+        out["after_warm"] = width_cases._extrema(off, compress, expand, _on_the_face_columns)
+        return out
+    return recipe
+
+
+def _euler_extrema(data):
+    def recipe(off):
+        f = np.array([2.0] * (off.dim + 1) + [4.0])   # twice the density and momentum, four times the energy
+        return _with_extrema(data, lambda U: U * f, lambda U: U / f)(off)
+    return recipe
+
+
+def _sw_extrema(data):
+    return _with_extrema(data, lambda U: 2.0 * U, lambda U: 0.5 * U)
+
+
+def _polytropic(p):
+    """EulerAEOS with the polytropic gas and strict bounds, as the row-width cases (van der Waals with this blast ends
+    every update with a relaxed-bound warning, on a continuous mesh just the same: tests/test_dg_q1.py)"""
+    p.eos = capi.EOS_POLYTROPIC_GAS
+    p.compute_strict_bounds = 1
+
+
+def _aeos_blast(centre=0.45, radius=0.18):
+    def data(off):
+        import oracle_py
+        from ryujin_amd.initial_states import aeos_from_primitive
+        p = oracle_py.default_params(capi.EQ_EULER_AEOS, off.dim)
+        _polytropic(p)
+        bump = _bump(off.positions, [centre] * off.dim, radius)
+        return dict(U0=aeos_from_primitive(p, 1.0 + 0.6 * bump, np.zeros((off.n_owned, off.dim)), 1.0 + 4.0 * bump),
+                    dirichlet=None)
+    return data
+
+
+def _checked(p):
+    p.debug_expensive_bounds_check = 1
+
+
+def _polytropic_checked(p):
+    _polytropic(p)
+    _checked(p)
+
+
+# ------------------------------------------------------------------ expected plans (literals)
+
+def _dg_plan(step2, diag_width, wide, **kw):
+    """the discontinuous ansatz: step 4 stores P_ij, step 5 is k_pij_lij<E, true, wide> (V_i), k_high_order twice"""
+    plan = _plan(step2, diag_width, "pij_lij", 1, True, 1, "high_order", False, "high_order", wide=wide,
+                 step4_stores_p=True, **kw)
+    return dict(plan, dg=True)
+
+
+def _launches(n_slices):
+    return dict(step5_launches=[dict(n_slices=n_slices, grid_y=1)],
+                step6_launches=[dict(n_slices=n_slices, grid_y=1, shares_slices=False)])
+
+
+CASES = {}
+
+
+def _entry(name, mesh, n_points, width, equation, data, plan, *, warm, edit=None, options=(), stages=0, cfl=0.5,
+           kind="real", incidence=False):
+    """kind: "real" (a dG stencil with structural zeros) or "synthetic"; incidence: the condition on both arms of the
+    fmax applies (degree 2, synthetic)"""
+    n_slices = (n_points + 63) // 64
+    if kind == "real":
+        data = (_sw_extrema if equation == "shallow_water" else _euler_extrema)(data)
+    case = _case(mesh, equation, data, n_points, plan, _launches(n_slices), warm=warm, edit=edit, cfl=cfl, stages=stages)
+    CASES[name] = dict(case, width=width, options=("dg=1",) + tuple(options), kind=kind, incidence=incidence)
+
+
+# Euler dG-Q1 3-D, 6^3 cells: rows of 32 - 56 entries, 27 slices. k_low_order<3, false | true, true, true>,
+# k_pij_lij<Euler<3>, true, false>, step 2 k_dij_alpha on a dG stencil; step<1> and step<2> of ERK33
+_Q1_3D = _dg_mesh((6, 6, 6), 1)
+_entry("euler_q1_3d", _Q1_3D, 1728, 56, "euler", _euler_blast(), _dg_plan(D, 0, False, fast_riemann=True), warm=12)
+for _s in (1, 2):
+    _entry(f"euler_q1_3d_erk33_step{_s}", _Q1_3D, 1728, 56, "euler", _euler_blast(),
+           _dg_plan(D, 0, False, fast_riemann=True, step4_has_stages=True), warm=11, stages=_s)
+
+# dG-Q1 2-D, 24^2 cells (rows of 12 / 16 / 20 entries): step<2> of ERK33 and the checked build for every Description
+_Q1_2D = _dg_mesh((24, 24), 1)
+for _name, _equation, _data, _step2, _kw, _edit, _chk in (
+        ("euler", "euler", _euler_blast(), R, dict(fast_riemann=True), None, _checked),
+        ("sw", "shallow_water", _sw_hump(), R, {}, None, _checked),
+        ("aeos", "euler_aeos", _aeos_blast(), A, dict(step2_split=True), _polytropic, _polytropic_checked)):
+    _entry(f"{_name}_q1_2d_erk33_step2", _Q1_2D, 2304, 20, _equation, _data,
+           _dg_plan(_step2, 27, False, step4_has_stages=True, **_kw), warm=12, edit=_edit, stages=2)
+    _entry(f"{_name}_q1_2d_checked", _Q1_2D, 2304, 20, _equation, _data,
+           _dg_plan(_step2, 27, False, checked=True, **_kw), warm=12, edit=_chk, options=("checked=1",))
+
+_entry("aeos_q1_2d", _Q1_2D, 2304, 20, "euler_aeos", _aeos_blast(), _dg_plan(A, 27, False, step2_split=True), warm=12,
+       edit=_polytropic)
+
+# Euler dG-Q1 2-D, slip and Dirichlet boundaries: the bump sits next to the lower left corner
+for _name, _bc in (("slip", capi.BC_SLIP), ("dirichlet", capi.BC_DIRICHLET)):
+    _entry(f"euler_q1_2d_{_name}", _dg_mesh((24, 24), 1, boundary_id=_bc), 2304, 20, "euler",
+           _euler_blast((0.2, 0.15), dirichlet=_bc == capi.BC_DIRICHLET), _dg_plan(R, 27, False, fast_riemann=True),
+           warm=12)
+
+# dG-Q2: fractional incidence; graded meshes in 2-D and 3-D
+_entry("euler_q2_1d", _dg_mesh((64,), 2, grade=True), 192, 9, "euler", _euler_blast(), _dg_plan(R, 9, False, fast_riemann=True),
+       warm=12, incidence=True)
+_entry("euler_q2_2d", _dg_mesh((12, 12), 2, grade=True), 1296, 45, "euler", _euler_blast(radius=0.25),
+       _dg_plan(D, 0, False, fast_riemann=True), warm=12, incidence=True)
+_entry("sw_q2_2d", _dg_mesh((12, 12), 2, grade=True), 1296, 45, "shallow_water", _sw_hump(radius=0.25),
+       _dg_plan(D, 0, False), warm=12, incidence=True)
+# Euler dG-Q2 3-D, 4^3 cells: rows of up to 189 entries = three blocks of 63. k_pij_lij<Euler<3>, true, true>,
+# k_high_order<.., false, true>
+_entry("euler_q2_3d", _dg_mesh((4, 4, 4), 2, grade=True), 1728, 189, "euler", _euler_blast(0.5, radius=0.4),
+       _dg_plan(D, 0, True, fast_riemann=True), warm=8, incidence=True)
+
+# synthetic dG on the lattices of the row-width cases: WIDE && DG on both sides of each block boundary
+for _name, _basis, _equation in (("euler_2d_64", "euler_2d_64", "euler"), ("euler_2d_65", "euler_2d_65", "euler"),
+                                 ("euler_2d_127", "euler_2d_127", "euler"), ("euler_2d_128", "euler_2d_128", "euler"),
+                                 ("euler_1d_65", "euler_1d_65", "euler"), ("euler_3d_65", "euler_3d_65", "euler"),
+                                 ("sw_2d_65", "sw_2d_65", "shallow_water"),
+                                 ("euler_2d_erk33_128", "euler_2d_erk33_128", "euler")):
+    _b = width_cases.CASES[_basis]
+    _entry(f"synthetic_{_name}", _synthetic_mesh(_basis), _b["n_points"], _b["width"], _equation,
+           lambda off, inner=_b["data"], n_widest=24 if _equation == "shallow_water" else 48:
+           inner(off, more=lambda o: _on_the_face_columns(o, n_widest=n_widest)),
+           _dg_plan(D, 0, _b["width"] > 64, fast_riemann=_equation == "euler", step4_has_stages=_b["stages"] != 0),
+           warm=1, stages=_b["stages"], kind="synthetic", incidence=True)
+
+del _s, _name, _equation, _data, _step2, _kw, _edit, _chk, _bc, _basis, _b
+
+# EulerAEOS on dG stencils wider than 32 entries: step() refuses on the host, before any launch (step_plan.hpp). The
+# smallest meshes with a full row: 3^3 cells of dG-Q1 (the middle cell has six neighbours: 56 entries), 3^2 cells of
+# dG-Q2 (45 entries)
+AEOS_REFUSED = dict(meshes={"q1_3d": (_dg_mesh((3, 3, 3), 1), 56), "q2_2d": (_dg_mesh((3, 3), 2, grade=True), 45)},
+                    message="euler aeos: stencils of more than 32 entries", accepted="aeos_q1_2d", edit=_polytropic)
+
+
+# ------------------------------------------------------------------ running a case
+
+ERK33_WEIGHTS = {1: (-1.0,), 2: width_cases.ERK33_STEP2_WEIGHTS}   # step<1>, step<2> of ERK33
+
+
+def develop(case, oracle):
+    """(offline data, Dirichlet data, states, stage weights, tau): the input of the compared update, developed ON THE
+    ORACLE with status 0 and no warning. states[-1] is the old state; with stage vectors (step<1> / step<2> of ERK33, fed
+    as helpers_row_width_cases.develop feeds them) states[:-1] are the stage vectors and tau the step size of stage 0."""
+    import helpers_plan_cases as plan_cases
+    off, U0, dirichlet, after_warm = plan_cases.build(case)
+    params = plan_cases.params_of(case, oracle, off.dim)
+    m = HyperbolicModule(off, params, backend=oracle.backend())
+    old, new = m.new_state_vector(U0), m.new_state_vector()
+    for _ in range(case["warm"]):
+        m.prepare_state_vector(old, 0.0, dirichlet)
+        m.step(old, [], [], new)
+        assert m.last_status == 0
+        old, new = new, old
+    assert m.n_warnings() == 0, "a warning during the warm-up"
+    U_start = old.download()
+    m.close()
+    if after_warm:
+        U_start = after_warm(U_start)
+    if case["stages"] == 0:
+        return off, dirichlet, [U_start], (), 0.0
+    m = HyperbolicModule(off, params, backend=oracle.backend())
+    v = [m.new_state_vector(U_start)] + [m.new_state_vector() for _ in range(case["stages"])]
+    m.prepare_state_vector(v[0], 0.0, dirichlet)
+    tau = m.step(v[0], [], [], v[1])
+    if case["stages"] == 2:
+        m.prepare_state_vector(v[0], 0.0, dirichlet)   # stage vectors are prepared state vectors
+        m.prepare_state_vector(v[1], 0.0, dirichlet)
+        m.step(v[1], [v[0]], list(ERK33_WEIGHTS[1]), v[2], tau)
+    assert m.last_status == 0 and m.n_warnings() == 0, "a warning in the stages before the compared one"
+    states = [x.download() for x in v]
+    m.close()
+    return off, dirichlet, states, ERK33_WEIGHTS[case["stages"]], tau
+
+
+def oracle_update(case, oracle, off, dirichlet, states, weights, tau, dg=True):
+    """one update on a fresh oracle context (the checked case in its checked control flow): dict of tau, status,
+    warnings, alpha, the first-pass l_ij, U_new. dg = False: the same data WITHOUT the discontinuous ansatz."""
+    import helpers_plan_cases as plan_cases
+    off._o.discontinuous_ansatz = 1 if dg else 0
+    try:
+        m = HyperbolicModule(off, plan_cases.params_of(case, oracle, off.dim), backend=oracle.backend())
+    finally:
+        off._o.discontinuous_ansatz = 1
+    if case["plan"]["checked"]:
+        oracle.lib().ryujin_oracle_set_expensive_bounds_check(m._ctx, 1)
+    v = [m.new_state_vector(U) for U in states]
+    new = m.new_state_vector()
+    for x in v:
+        m.prepare_state_vector(x, 0.0, dirichlet)
+    used = m.step(v[-1], v[:-1], list(weights), new, tau)
+    out = dict(tau=used, status=m.last_status, warnings=m.n_warnings(), alpha=m.alpha()[: off.n_owned],
+               lij_next=m.debug_fetch("lij_next"), U=new.download()[: off.n_owned])
+    m.close()
+    return out
+
+
+_DEVELOPED = {}
+
+
+def developed(name, oracle):
+    """develop() and the oracle's own update from it, computed once per process and never modified:
+    ((offline data, Dirichlet data, states, weights, tau), oracle_update)"""
+    if name not in _DEVELOPED:
+        dev = develop(CASES[name], oracle)
+        _DEVELOPED[name] = (dev, oracle_update(CASES[name], oracle, *dev))
+    return _DEVELOPED[name]
+
+
+# ------------------------------------------------------------------ several ranks
+
+def by_cells(cuts):
+    """ownership by cells (all DoFs of a cell on one rank, as a dG DoFHandler distributes): x slabs, cut at the given
+    cell indices"""
+    def owner(off):
+        info = off.dg_info
+        cell = np.arange(off.n_owned) // info["n_per_cell"]
+        return np.searchsorted(np.asarray(cuts), cell % info["n_cells"][0], side="right").astype(np.int64)
+    return owner
+
+
+def _lattice_slabs(off):
+    import helpers_row_width_ranks as ranks
+    return ranks.slabs(2)(off)
+
+
+# per rank: (n_owned, n_export, [(slices, gridDim.y of step 5, step 6 shares) of the export and the interior launch])
+RANK_CASES = {
+    # rows of up to 189 entries cut by cells: ghost columns with (M^-1)_ij = 0 and a fractional incidence in every block
+    "euler_q2_3d": dict(basis="euler_q2_3d", owner=by_cells((2,)), more=True,
+                        ranks=[(864, 432, [(7, 1, False), (7, 1, False)])] * 2),
+    # FOUR bound vectors over bounds_stride; the first rank is three cells wide
+    "aeos_q1_2d": dict(basis="aeos_q1_2d", owner=by_cells((3, 13)),
+                       ranks=[(288, 96, [(2, 1, False), (3, 1, False)]), (960, 192, [(3, 1, False), (12, 1, False)]),
+                              (1056, 96, [(2, 1, False), (15, 1, False)])]),
+    # WIDE && DG on two slabs of a lattice: the ghost columns fill the last blocks of a row of 128 entries
+    "synthetic_euler_2d_128": dict(basis="synthetic_euler_2d_128", owner=_lattice_slabs, shape=(40, 48), more=True,
+                                   ranks=[(960, 480, [(8, 1, False), (7, 1, False)])] * 2),
+}
+
+_BUILT_RANKS = {}
+
+
+def ghost_column_nodes(off, owner, per_width=12):
+    """for up to `per_width` rows of every width on every rank that couple to another rank: the nodes of the row's FIRST
+    and LAST foreign column with a structurally non-zero entry, in the rank's numbering (helpers_row_width_ranks.py:
+    last_ghost_columns) -- rows of different widths hold their ghost columns in different blocks of 63"""
+    import helpers_row_width_ranks as ranks
+    widths, rs, rows, position = _pattern(off)
+    cols = np.asarray(off.columns).astype(np.int64)
+    foreign = (owner[cols] != owner[rows]) & structurally_nonzero(off)
+    exported = np.bincount(rows[owner[cols] != owner[rows]], minlength=off.n_owned) > 0
+    order = np.lexsort((np.arange(off.n_owned), ~exported, owner))
+    key = np.empty(off.n_owned, dtype=np.int64)
+    key[order] = np.arange(off.n_owned)
+    nodes = []
+    for r in range(int(owner.max()) + 1):
+        for w in np.unique(widths):
+            candidates = np.flatnonzero((owner == r) & (widths == w) & (np.bincount(rows[foreign], minlength=off.n_owned) > 0))
+            for i in candidates[np.unique(np.linspace(0, len(candidates) - 1, min(per_width, len(candidates))).astype(int))] \
+                    if len(candidates) else ():
+                e = np.arange(rs[i], rs[i + 1])
+                e = e[foreign[e]]
+                nodes.extend((cols[e[np.argmax(key[cols[e]])]], cols[e[np.argmin(key[cols[e]])]]))
+    return np.unique(np.asarray(nodes, dtype=np.int64))
+
+
+def _more_extrema(case, nodes_of):
+    """the case with further nodes compressed / expanded after its own extrema"""
+    def recipe(off, inner=case["data"]):
+        out = inner(off)
+        first = out["after_warm"]
+        factor = 2.0 if case["equation"] == "shallow_water" else np.array([2.0] * (off.dim + 1) + [4.0])
+
+        def after_warm(U):
+            U = first(U)
+            nodes = nodes_of(off)
+            up = np.arange(len(nodes)) % 2 == 0
+            U[nodes[up]] = U[nodes[up]] * factor
+            U[nodes[~up]] = U[nodes[~up]] / factor
+            return U
+        out["after_warm"] = after_warm
+        return out
+    return dict(case, data=recipe)
+
+
+def built_ranks(name, oracle):
+    """What every test of a rank case needs, computed once per process and never modified: the single-rank data and
+    state developed on the single-rank oracle, its update, the rank views, every rank's share of the state and the
+    partitioned oracle's update with every intermediate array."""
+    if name in _BUILT_RANKS:
+        return _BUILT_RANKS[name]
+    import helpers_plan_cases as plan_cases
+    from helpers_partitioned import one_update_with_intermediates, run_oracle_ranks
+    entry = RANK_CASES[name]
+    case = CASES[entry["basis"]]
+    if "shape" in entry:   # the lattice of the basis, longer along the cut axis (helpers_row_width_ranks.py)
+        shape = entry["shape"]
+        case = dict(case, mesh=lambda: synthetic_dg(width_cases._lattice(shape, case["width"], 96)()),
+                    n_points=int(np.prod(shape)))
+    if entry.get("more"):
+        def nodes_of(o):
+            nodes = ghost_column_nodes(o, entry["owner"](o))
+            if case["kind"] == "synthetic":   # ... and the last columns of widest rows, as the row-width rank cases
+                import helpers_row_width_ranks as ranks
+                nodes = np.unique(np.concatenate([nodes, ranks.last_ghost_columns(o, entry["owner"](o), per_rank=48)]))
+            return nodes
+        case = _more_extrema(case, nodes_of)
+    assert case["stages"] == 0 and not case["plan"]["checked"]
+    dev = develop(case, oracle)
+    off, dirichlet, states, weights, tau = dev
+    assert dirichlet is None
+    single = oracle_update(case, oracle, *dev)
+    owner = entry["owner"](off)
+    if case["kind"] == "synthetic":
+        import helpers_row_width_ranks as ranks
+        views = ranks.partition_lattice(off, owner)
+    else:
+        from helpers_unstructured import partition
+        views = partition(off, off.dg_info, owner, bathymetry=off._keep.get("initial_precomputed"))
+    U_local = [states[0][v.global_ids] for v in views]
+    make_params = lambda: plan_cases.params_of(case, oracle, off.dim)  # noqa: E731
+    ref = run_oracle_ranks(oracle, views, make_params, one_update_with_intermediates(U_local))
+    _BUILT_RANKS[name] = dict(entry=entry, case=case, off=off, views=views, U_local=U_local, single=single, ref=ref,
+                              make_params=make_params, k=states[0].shape[1])
+    return _BUILT_RANKS[name]
+
+
+def ghost_coverage(view, first_pass_lij, width):
+    """one rank's inputs (helpers_row_width_ranks.ghost_coverage, stated for the structurally non-zero entries): a
+    ghost-column entry strictly between 0 and 1 in every block of 63 column positions in which an owned row holds a
+    structurally non-zero ghost column, in the last such column of a widest row, and a ghost-row entry below 1"""
+    import helpers_row_width_ranks as ranks
+    n = view.n_owned
+    ptr, cols, rows, position = ranks._local_pattern(view)
+    l = np.asarray(first_pass_lij)
+    assert l.size == ptr[-1]
+    nnz = len(cols)
+    held = (np.abs(np.asarray(view._keep["cij"]).reshape(nnz, view.dim)).max(axis=1) > 0.0) | (view._dg[1] != 0.0) | \
+        (np.asarray(view._keep["mij"]) != 0.0)
+    owned, ghost_col = rows < n, cols >= n
+    undecided = (l > 0.0) & (l < 1.0)
+    out = {}
+    for first in range(1, width, BLOCK):
+        in_block = owned & ghost_col & held & (position >= first) & (position < first + BLOCK)
+        if in_block.any():
+            out[f"ghost columns in block {first}..{min(first + BLOCK, width) - 1}"] = int((in_block & undecided).sum())
+    assert out, "a rank without ghost columns"
+    lengths = np.diff(ptr)
+    of_widest = owned & ghost_col & held & (lengths[rows] == width)
+    if of_widest.any():
+        last = position[of_widest].max()
+        out[f"ghost column in the last held column {last} of a widest row"] = \
+            int((of_widest & undecided & (position == last)).sum())
+    out["ghost-row entries below 1"] = int((~owned & (position > 0) & (l < 1.0)).sum())
+    return out
+
+
+def assert_rank_coverage(name, b, ref):
+    import helpers_row_width_ranks as ranks
+    counts = []
+    for r, view in enumerate(b["views"]):
+        covered = ghost_coverage(view, ref[r]["lij_next"], b["case"]["width"])
+        assert min(covered.values()) > 0, (name, r, {k: v for k, v in covered.items() if v == 0})
+        counts.append(covered)
+    union = ranks.first_pass_on_the_single_rank_pattern(b["off"], b["views"], [x["lij_next"] for x in ref])
+    covered = coverage(b["off"], union, b["case"]["width"])
+    assert min(covered.values()) > 0, (name, "union of the owned rows", {k: v for k, v in covered.items() if v == 0})
+    return counts
+
+
+# ------------------------------------------------------------------ what a case must show before it counts
+
+def _pattern(off):
+    widths = rw.widths_of(off)
+    rs = np.concatenate([[0], np.cumsum(widths)])
+    rows = np.repeat(np.arange(off.n_owned), widths)
+    position = np.arange(rs[-1]) - np.repeat(rs[:-1], widths)
+    return widths, rs, rows, position
+
+
+def structurally_nonzero(off):
+    """entries with c_ij, m_ij or (M^-1)_ij other than zero (every entry of a synthetic row; on a dG stencil the own cell
+    and the neighbours' DoFs on the common face)"""
+    nnz = len(np.asarray(off.columns))
+    cij = np.asarray(off._keep["cij"]).reshape(nnz, off.dim)
+    return (np.abs(cij).max(axis=1) > 0.0) | (np.asarray(off._keep["mij"]) != 0.0) | (off._dg[1] != 0.0)
+
+
+def coverage(off, first_pass_lij, width):
+    """dict of counts that must all be positive (see the module docstring). `first` / `last` of a block: the first / last
+    column position of the block at which some row holds a structurally non-zero entry -- the block's own first and last
+    position wherever the data is synthetic."""
+    widths, rs, rows, position = _pattern(off)
+    l = np.asarray(first_pass_lij)[: rs[-1]]
+    inside = (l > 0.0) & (l < 1.0) & (position > 0)
+    per_position = np.bincount(position[inside], minlength=width)
+    can = np.bincount(position[structurally_nonzero(off) & (position > 0)], minlength=width) > 0
+    out = {}
+    for first in range(1, width, BLOCK):
+        last = min(first + BLOCK, width) - 1
+        out[f"block {first}..{last}"] = int(per_position[first:last + 1].sum())
+        held = first + np.flatnonzero(can[first:last + 1])
+        assert len(held), ("a block without a structurally non-zero entry", first, last)
+        out[f"first column {held[0]} of block {first}..{last}"] = int(per_position[held[0]])
+        out[f"last column {held[-1]} of block {first}..{last}"] = int(per_position[held[-1]])
+    widest = widths[rows] == width
+    held = np.flatnonzero(np.bincount(position[structurally_nonzero(off) & widest & (position > 0)], minlength=width))
+    out[f"last column {held[-1]} of a widest row"] = int((inside & widest & (position == held[-1])).sum())
+    for w in np.unique(widths):
+        out[f"width {w}"] = int((inside & (widths[rows] == w)).sum())
+    return out
+
+
+def incidence_arms(off, alpha):
+    """(entries where the incidence decides the fmax, entries where a positive incidence loses it), off the diagonal"""
+    widths, rs, rows, position = _pattern(off)
+    cols = np.asarray(off.columns).astype(np.int64)
+    mean = 0.5 * (alpha[rows] + alpha[cols])
+    inc = off._dg[0]
+    off_diag = position > 0
+    return int((off_diag & (inc > mean)).sum()), int((off_diag & (inc > 0.0) & (inc < mean)).sum())
+
+
+def dg_branch_effect(case, oracle, developed):
+    """max |U_new(dG) - U_new(the same data, discontinuous_ansatz = 0)| relative to the component's scale"""
+    a = oracle_update(case, oracle, *developed)
+    b = oracle_update(case, oracle, *developed, dg=False)
+    scale = np.maximum(np.abs(a["U"]).max(axis=0), 1e-3 * np.abs(a["U"]).max())
+    return float((np.abs(a["U"] - b["U"]) / scale).max())

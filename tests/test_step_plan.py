@@ -259,3 +259,61 @@ def test_case_table_of_the_row_widths_on_ranks_is_what_plan_step_decides(checker
                                     1.0, 0, sizes + list(case["options"]))
         _assert_table_entry(r, n_slices, case["plan"], [dict(n_slices=s, grid_y=y) for s, y, _ in expected["launches"]],
                             [dict(n_slices=s, grid_y=1, shares_slices=b) for s, _, b in expected["launches"]])
+
+
+# ---- the dG case table of tests/test_gpu_dg_variants.py against plan_step()
+
+import helpers_dg_cases as dg_cases  # noqa: E402
+
+
+@pytest.mark.parametrize("name", sorted(dg_cases.CASES))
+def test_case_table_of_the_dg_variants_is_what_plan_step_decides(checker, name):
+    """Every entry of tests/helpers_dg_cases.py: the mesh is built, n_owned and the widest row are taken from it, and the
+    plan and the launches plan_step() makes of them with dg=1 and the case's parameter edits must equal the literals"""
+    case = dg_cases.CASES[name]
+    off = case["mesh"]()
+    assert off.n_owned == case["n_points"] and off.c.contents.discontinuous_ansatz == 1
+    widths = plan_cases.widths_of(off)
+    assert widths.max() == case["width"] and "dg=1" in case["options"]
+    sizes = [q["n_slices"] for q in case["step5_launches"]]
+    n_slices, r = _checked_plan(checker, case["equation"], off.dim, widths, off.n_owned, 1.0, case["stages"],
+                                sizes + list(case["options"]))
+    _assert_table_entry(r, n_slices, case["plan"], case["step5_launches"], case["step6_launches"])
+    assert r["dg"] and r["step4_stores_p"] and r["step5"] == "pij_lij" and r["wide"] == (case["width"] > 64)
+
+
+@pytest.mark.parametrize("name", sorted(dg_cases.RANK_CASES))
+def test_case_table_of_the_dg_variants_on_ranks_is_what_plan_step_decides(checker, oracle, name):
+    """per rank: the widest owned row and the slice count of the partition, the export and the interior launch"""
+    b = dg_cases.built_ranks(name, oracle)
+    case = b["case"]
+    for view, (n_owned, n_export, launches) in zip(b["views"], b["entry"]["ranks"]):
+        assert (view.n_owned, view.n_export) == (n_owned, n_export)
+        sizes = [s for s, _, _ in launches]
+        assert sizes[0] == (n_export + 63) // 64
+        n_slices, r = _checked_plan(checker, case["equation"], b["off"].dim, plan_cases.widths_of(view), n_owned, 1.0, 0,
+                                    sizes + list(case["options"]))
+        _assert_table_entry(r, n_slices, case["plan"], [dict(n_slices=s, grid_y=y) for s, y, _ in launches],
+                            [dict(n_slices=s, grid_y=1, shares_slices=x) for s, _, x in launches])
+
+
+def test_the_plan_mode_takes_dg(checker):
+    """dg=1 moves Euler 2-D with nine columns from the stage-0 kernel to step 4 storing P_ij and k_pij_lij<.., true, ..>;
+    shallow water leaves the single walk; without the key the plan is the continuous one"""
+    cg = _run(checker, "plan", "euler", 2, 9, 15, 1.0, 0, 15)
+    dg = _run(checker, "plan", "euler", 2, 9, 15, 1.0, 0, 15, "dg=1")
+    assert not cg["dg"] and cg["step5"] == "stage0_groups" and not cg["step4_stores_p"]
+    assert dg["dg"] and dg["step5"] == "pij_lij" and dg["step4_stores_p"] and dg["has_V"] and dg["step6"] == "cached"
+    assert _run(checker, "plan", "shallow_water", 2, 9, 15, 1.0, 0, 15)["step4_single_walk"]
+    assert not _run(checker, "plan", "shallow_water", 2, 9, 15, 1.0, 0, 15, "dg=1")["step4_single_walk"]
+    assert _run(checker, "path", "euler", 3, 189, 27, 1.0)["kernels"][-3] == "k_pij_lij<Euler<3>, false, true>"
+
+
+def test_euler_aeos_on_wide_dg_stencils_is_refused(checker):
+    refused = dg_cases.AEOS_REFUSED
+    for key, (mesh, width) in refused["meshes"].items():
+        off = mesh()
+        out = subprocess.run([checker, "plan", "euler_aeos", str(off.dim), str(width), "1", "1.0", "0", "1", "dg=1"],
+                             capture_output=True, text=True)
+        assert out.returncode == 1 and out.stderr.strip() == refused["message"], key
+    assert dg_cases.CASES[refused["accepted"]]["width"] == 20
