@@ -721,9 +721,9 @@ int ryujin_hip_quantities_time_series(ryujin_hip_ctx *ctx, int manifold, double 
  *                 end. All seven schemes, bang-bang recovery with its internal re-run included. A rank without
  *                 boundary entries launches nothing for it.
  * RYUJIN_ERR_ARG: an unknown state or one the context's Description does not have, a zero direction, NULL positions,
- * any entry but configure before configure. RYUJIN_ERR_UNSUPPORTED: scalar conservation (the reference's
- * configurations use the muparser "function" state there), perturbation != 0 (an unseeded generator in the
- * reference), a state in a dimension it is not defined for. */
+ * any entry but configure before configure. RYUJIN_ERR_UNSUPPORTED: scalar conservation (its only state in the
+ * reference is the expression-defined "function" state: ryujin_hip_initial_values_configure_function below),
+ * perturbation != 0 (an unseeded generator in the reference), a state in a dimension it is not defined for. */
 enum {
   RYUJIN_IV_UNIFORM = 0,
   RYUJIN_IV_RADIAL_CONTRAST = 1,
@@ -750,6 +750,73 @@ int ryujin_hip_initial_values_interpolate(ryujin_hip_ctx *ctx, int handle, doubl
 int ryujin_hip_prepare_state_vector_iv(ryujin_hip_ctx *ctx, int handle, double t);
 int ryujin_hip_time_step_iv(ryujin_hip_ctx *ctx, int scheme, int h_state, int n_tmp, const int *h_tmp, double t,
                             double tau_max, int cfl_recovery, double cfl_min, double cfl_max, double *tau_out);
+
+/* ---- The function state: configuration = function, one expression per primitive component ---- */
+/* source/{euler,shallow_water,scalar_conservation}/initial_state_function.h: the primitive state at (x, t) is one
+ * expression per component in the variables x [y [z]] and t, evaluated behind the affine transform above, turned
+ * into the conserved state by the Description's from_primitive_state, the momentum rotated back:
+ *   Euler                (density, velocity x [y [z]], pressure)   E = p / (gamma - 1) + 1/2 rho |v|^2
+ *   EulerAEOS            the same parameters, but from_primitive_state (euler_aeos/hyperbolic_system.h:1473-1493)
+ *                        reads the LAST component as the specific internal energy e: E = rho e + 1/2 rho |v|^2; the
+ *                        equation of state does not enter (unlike the analytic states, which go through
+ *                        from_initial_state)
+ *   shallow water        (water depth, velocity x [y])             (h, h v)
+ *   scalar conservation  (the value)
+ * The reference parses with dealii::FunctionParser (muparser). This library has a parser of its own
+ * (ryujin_amd/csrc/expression.hpp) for the following subset; THIS TABLE IS THE CONTRACT. deal.II is not available
+ * to this project's builds, so its exact choices -- above all the rounding in front of if, |, & and int, and that a
+ * literal exponent 2, 3, 4 is multiplied out -- are restated from its documentation and are not checked against it.
+ *
+ *   literals     decimal numbers with optional fraction and exponent (2, .5, 1.5, 1e-3, 1.5E+2); _pi, _e
+ *   variables    x, then y (dim >= 2), z (dim = 3), and t
+ *   binary operators by rising precedence, left-associative unless noted:
+ *     c ? a : b          right-associative; c is tested != 0
+ *     ||  |              1 or 0; || tests != 0, | rounds its operands first
+ *     &&  &              1 or 0; && tests != 0, & rounds its operands first
+ *     <  >  <=  >=  ==  !=      one level; 1 or 0
+ *     +  -
+ *     *  /
+ *     ^                  right-associative. A literal exponent 2, 3 or 4 is multiplied out from the left (a*a*a*a);
+ *                        everything else is pow(a, b)
+ *   unary - +    bind weaker than ^ (-x^2 = -(x^2)) and stronger than * /; also in an exponent (2^-x)
+ *   functions of one argument
+ *     sin cos tan asin acos atan sinh cosh tanh asinh acosh atanh exp log ln log2 log10 sqrt abs erf erfc
+ *                        (log and ln: the natural logarithm)
+ *     cot csc sec        1 / tan, 1 / sin, 1 / cos
+ *     sign               -1, 0 or 1
+ *     floor ceil         ; rint(a) = floor(a + 1/2); int(a) = a rounded
+ *   functions of several arguments
+ *     pow(a, b)          ; min(a, ...), max(a, ...) with one or more arguments, folded from the left with < ;
+ *     if(c, a, b)        c is rounded first, then tested != 0
+ *   "rounded": to the nearest integer, halves away from zero, trunc(a + (a >= 0 ? 1/2 : -1/2)).
+ *   ?: and if evaluate BOTH arms and then select: the same value for these side-effect free operands, and a NaN of
+ *   the arm not taken is discarded. Space, tab and line ends separate tokens.
+ * RYUJIN_ERR_UNSUPPORTED: rand, rand_seed, sum, avg, string arguments, assignment. RYUJIN_ERR_ARG: everything else
+ * outside the table -- an unknown identifier (pi without the underscore), y in 1-D, unbalanced parentheses, a wrong
+ * number of arguments, an empty string, text behind the expression --, a program of more than
+ * RYUJIN_EXPR_MAX_INSTRUCTIONS instructions (one per literal, variable, operator and function call), more than
+ * RYUJIN_EXPR_MAX_STACK operands alive at once (1+(1+(1+ ... nests one per level), parentheses and calls nested
+ * deeper than 64. ryujin_hip_last_error names the character (counted from 0) where the refusal arose.
+ * Arithmetic: + - * /, sqrt, comparisons, selection and rounding give the same bits on the host and on the device;
+ * pow is the library's own on the device and the C library's on the host, the other functions are each side's.
+ *
+ *   configure_function   n_expressions = the number of primitive components, in the order above; direction,
+ *                        position, positions and b_positions as ryujin_hip_initial_values_configure takes them. It
+ *                        replaces an earlier configure or configure_function, and configure replaces it. A refused
+ *                        call leaves the earlier configuration in place. Afterwards evaluate, interpolate,
+ *                        prepare_state_vector_iv and time_step_iv work as for the analytic states, for scalar
+ *                        conservation too. The programs are evaluated by an interpreter on the device: the operand
+ *                        stack in LDS, the program read through the scalar cache.
+ *   expression_evaluate  needs no context and no device: out[i] = expression(points [n * dim], t) with the host's
+ *                        interpreter (the same source as the device's). n = 0 returns RYUJIN_OK and writes nothing. */
+#define RYUJIN_EXPR_MAX_INSTRUCTIONS 256
+#define RYUJIN_EXPR_MAX_STACK 16
+int ryujin_hip_initial_values_configure_function(ryujin_hip_ctx *ctx, int n_expressions,
+                                                 const char *const *expressions, const double direction[3],
+                                                 const double position[3], const double *positions,
+                                                 const double *b_positions);
+int ryujin_hip_expression_evaluate(const char *expression, int dim, const double *points, size_t n, double t,
+                                   double *out);
 
 /* ---- Error norms: analytic-solution error of a verification run, device resident -- */
 /* The norms of TimeLoop::compute_error() of the reference (source/time_loop.template.h:692-833) between the state

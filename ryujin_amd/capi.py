@@ -173,6 +173,58 @@ def initial_values_struct(name: str, dim: int, direction=None, position=None, pe
     return iv
 
 
+# The function state (configuration = function of the reference): the parameter names of its expressions in primitive
+# order and the reference's defaults (source/<eq>/initial_state_function.h).
+EXPR_MAX_INSTRUCTIONS, EXPR_MAX_STACK = 256, 16
+
+
+def function_expression_names(equation: int, dim: int) -> tuple[tuple[str, str], ...]:
+    """((parameter name, default expression), ...) of the "function" state of a Description, in primitive order"""
+    velocity = tuple((f"velocity {a} expression", d) for a, d in zip("xyz"[:dim], ("3.0", "0.0", "0.0")))
+    if equation in (EQ_EULER, EQ_EULER_AEOS):
+        return (("density expression", "1.4"), *velocity, ("pressure expression", "1.0"))
+    if equation == EQ_SHALLOW_WATER:
+        return (("water depth expression", "1.4"), *velocity)
+    if equation == EQ_SCALAR_CONSERVATION:
+        return (("expression", "0.25 * x"),)
+    raise ValueError(f"unknown equation {equation}")
+
+
+def function_expressions(equation: int, dim: int, expressions) -> tuple[str, ...]:
+    """The expressions of the "function" state in primitive order from a sequence in that order, or from a dict keyed
+    by the reference's parameter names (spaces may be written as underscores) in which a missing key takes the
+    reference's default. ValueError for a wrong count or an unknown key."""
+    names = function_expression_names(equation, dim)
+    if isinstance(expressions, str):
+        expressions = (expressions,)
+    if isinstance(expressions, dict):
+        given = {k.replace("_", " "): v for k, v in expressions.items()}
+        out = tuple(str(given.pop(name, default)) for name, default in names)
+        if given:
+            raise ValueError(f"the function state has no parameter {sorted(given)}")
+        return out
+    out = tuple(str(e) for e in expressions)
+    if len(out) != len(names):
+        raise ValueError(f"the function state takes {len(names)} expressions: {[n for n, _ in names]}")
+    return out
+
+
+def expression_evaluate(expr: str, dim: int, points, t: float) -> np.ndarray:
+    """[n]: the expression over the first `dim` of x y z, then t, at points [n, dim], through the library's host
+    interpreter (ryujin_hip_expression_evaluate; no device). RuntimeError with .status for a refused expression."""
+    lib = load_hip()
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, dim)
+    out = np.zeros(points.shape[0], dtype=np.float64)
+    rc = lib.ryujin_hip_expression_evaluate(expr.encode(), dim, as_ptr(points, c_double_p) if points.size else None,
+                                            points.shape[0], float(t), as_ptr(out, c_double_p) if out.size else None)
+    if rc < 0:
+        error = RuntimeError(f"ryujin_hip_expression_evaluate failed with status {rc}: "
+                             f"{lib.ryujin_hip_last_error().decode()}")
+        error.status = rc
+        raise error
+    return out
+
+
 def component_names(equation: int, dim: int) -> tuple[tuple[str, ...], tuple[str, ...]]:
     """(View::component_names, View::primitive_component_names) of a Description
     (source/<eq>/hyperbolic_system.h)."""
@@ -294,6 +346,7 @@ HIP_SYMBOLS = [
     "ryujin_hip_quantities_time_series",
     "ryujin_hip_initial_values_configure", "ryujin_hip_initial_values_evaluate",
     "ryujin_hip_initial_values_interpolate", "ryujin_hip_prepare_state_vector_iv", "ryujin_hip_time_step_iv",
+    "ryujin_hip_initial_values_configure_function", "ryujin_hip_expression_evaluate",
     "ryujin_hip_error_norms_configure", "ryujin_hip_error_norms_compute",
 ]
 
@@ -400,6 +453,10 @@ def load_hip():
         lib.ryujin_hip_prepare_state_vector_iv.argtypes = [vp, C.c_int, C.c_double]
         lib.ryujin_hip_time_step_iv.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int_p, C.c_double, C.c_double,
                                                 C.c_int, C.c_double, C.c_double, c_double_p]
+        lib.ryujin_hip_initial_values_configure_function.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), c_double_p,
+                                                                     c_double_p, c_double_p, c_double_p]
+        lib.ryujin_hip_expression_evaluate.argtypes = [C.c_char_p, C.c_int, c_double_p, C.c_size_t, C.c_double,
+                                                       c_double_p]
         lib.ryujin_hip_error_norms_configure.argtypes = [vp, C.c_uint32, C.c_int, c_u32_p, C.c_int, c_double_p,
                                                          c_double_p, c_double_p, C.c_int]
         lib.ryujin_hip_error_norms_compute.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int_p, C.c_int, c_double_p,

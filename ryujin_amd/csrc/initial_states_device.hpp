@@ -10,6 +10,10 @@
 // ONE function, initial_state<E>(), serves every consumer (evaluate, interpolate, the Dirichlet kernel): the same
 // (x, t) gives the same bits wherever it is evaluated. The library is built with -ffp-contract=off.
 //
+// The expression-defined state "function" (source/*/initial_state_function.h) has a device function of its own,
+// initial_state_function<E>(), which again serves every consumer: it needs the programs and a column of LDS for the
+// operand stack, which the ten analytic states above it do without.
+//
 // Whatever does not depend on (x, t) -- the normalised direction and its rotation cosines, the Riemann-fan
 // constants of the rarefaction, sqrt(g h_L) of the Ritter solution, the uniform depth of the incline -- is formed
 // once on the host by ryujin_hip_initial_values_configure (InitialValuesParams::c).
@@ -22,6 +26,8 @@
 
 #include "euler_aeos_device.hpp"
 #include "euler_device.hpp"
+#include "expression.hpp"
+#include "scalar_conservation_device.hpp"
 #include "shallow_water_device.hpp"
 
 namespace ryujin_hip
@@ -37,7 +43,10 @@ namespace ryujin_hip
     kIvParaboloid = 6,
     kIvRitterDamBreak = 7,
     kIvSmoothVortex = 8,
-    kIvSlopingFriction = 9
+    kIvSlopingFriction = 9,
+    /* no RYUJIN_IV_* value: configured by ryujin_hip_initial_values_configure_function, evaluated by
+     * initial_state_function() below through kernels of its own */
+    kIvFunction = 10
   };
 
   struct InitialValuesParams {
@@ -333,6 +342,86 @@ namespace ryujin_hip
       for (int d = 0; d < DIM; ++d)
         U[1 + d] = m[d];
       U[1 + DIM] = E_total;
+    }
+  }
+
+  /* ---- configuration = function: one expression in (x, t) per primitive component -------------------------- */
+
+  constexpr int kIvMaxExpressions = 5; /* Euler, dim = 3: density, three velocities, pressure */
+
+  /* The programs of the components back to back, each closed by kExResult with its component as `slot`. The same
+   * for every lane: read through a const __restrict__ kernel argument at wave-uniform indices, i.e. by scalar loads,
+   * and every branch on an opcode is wave-uniform. */
+  struct IvFunctionProgram {
+    int n;
+    int pad;
+    ExprInstruction code[kIvMaxExpressions * (RYUJIN_EXPR_MAX_INSTRUCTIONS + 1)];
+  };
+
+  /* doubles of LDS per block of `block` threads: [slot][lane], operands first, then the components' values; a lane
+   * reads and writes its own column only (no barrier), consecutive lanes consecutive doubles (no bank conflict) */
+  constexpr int iv_function_lds_doubles(const int block)
+  {
+    return (RYUJIN_EXPR_MAX_STACK + kIvMaxExpressions) * block;
+  }
+
+  template <int BLOCK>
+  struct IvLdsStack {
+    double *column; /* &lds[lane] */
+    RYUJIN_DEV double load(const int slot) const { return column[slot * BLOCK]; }
+    RYUJIN_DEV void store(const int slot, const double value) { column[slot * BLOCK] = value; }
+  };
+
+  struct IvDevicePow {
+    RYUJIN_DEV double operator()(const double a, const double b) const { return dev_pow(a, b); }
+  };
+
+  /* initial_state(position, t) of the function state, conserved, U[E::K]: affine_transform of the point, the K
+   * programs at the transformed point and t, from_primitive_state of the Description as Function::compute calls it
+   * (euler/hyperbolic_system.h:1255-1272: p / (gamma - 1) + 1/2 rho |v|^2; euler_aeos/hyperbolic_system.h:1473-1493:
+   * the LAST primitive component is the specific internal energy e, E = rho e + 1/2 rho |v|^2, no equation of state
+   * enters; shallow_water/hyperbolic_system.h:1286-1297: (h, h v); scalar conservation: the value itself), the
+   * momentum rotated back. Every lane of the wave calls it (a lane without a point passes any finite x): the
+   * interpreter's loop is not under a divergent branch. */
+  template <typename E, int BLOCK>
+  RYUJIN_DEV void initial_state_function(const InitialValuesParams &P, const IvFunctionProgram *__restrict__ F,
+                                         const double (&x_in)[E::DIMENSION], const double t, double *column,
+                                         double (&U)[E::K])
+  {
+    constexpr int DIM = E::DIMENSION, K = E::K;
+    static_assert(K <= kIvMaxExpressions, "one expression per primitive component");
+    double x[DIM];
+    iv_transform_point<DIM>(P, x_in, x);
+    IvLdsStack<BLOCK> stack{column};
+    expr_evaluate(F->code, F->n, x[0], x[DIM >= 2 ? 1 : 0], x[DIM >= 3 ? 2 : 0], t, stack, IvDevicePow{});
+    double prim[K];
+#pragma unroll
+    for (int q = 0; q < K; ++q)
+      prim[q] = stack.load(RYUJIN_EXPR_MAX_STACK + q);
+
+    if constexpr (std::is_same<typename E::Params, ScalarParams>::value) {
+      U[0] = prim[0];
+    } else {
+      double m[DIM];
+#pragma unroll
+      for (int d = 0; d < DIM; ++d)
+        m[d] = prim[0] * prim[1 + d];
+      iv_transform_vector<DIM>(P, m);
+      U[0] = prim[0];
+#pragma unroll
+      for (int d = 0; d < DIM; ++d)
+        U[1 + d] = m[d];
+      if constexpr (!std::is_same<typename E::Params, ShallowWaterParams>::value) {
+        double v2 = prim[1] * prim[1];
+#pragma unroll
+        for (int d = 1; d < DIM; ++d)
+          v2 += prim[1 + d] * prim[1 + d];
+        const double kinetic = 0.5 * prim[0] * v2;
+        if constexpr (std::is_same<typename E::Params, EulerAeosParams>::value)
+          U[1 + DIM] = prim[0] * prim[1 + DIM] + kinetic;
+        else
+          U[1 + DIM] = prim[1 + DIM] / (P.c[0] - 1.) + kinetic;
+      }
     }
   }
 } // namespace ryujin_hip

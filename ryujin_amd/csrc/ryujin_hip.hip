@@ -483,6 +483,7 @@ struct ryujin_hip_ctx {
   bool iv_configured = false;
   InitialValuesParams iv{};
   DeviceBuffer<double> d_iv_positions, d_iv_b_positions;
+  DeviceBuffer<IvFunctionProgram> d_iv_function; /* iv.state == kIvFunction: the programs of the components */
   DeviceBuffer<double> d_iv_points, d_iv_values; /* scratch of evaluate(), grown on demand */
   /* Dirichlet data of a prepare_state_vector() evaluated on the device at t + c tau_rk (c = 0: at t) */
   struct IvStage {
@@ -1337,8 +1338,16 @@ void ryujin_hip_ctx::initial_values_points(const double *d_points, size_t n, dou
 {
   if (n == 0)
     return;
-  hipLaunchKernelGGL(k_initial_values_points<E>, dim3(grid_for(n, kInitialValuesBlock)), dim3(kInitialValuesBlock), 0,
-                     stream, iv, (uint32_t)n, d_points, t, stride, d_out);
+  if (iv.state == kIvFunction) {
+    hipLaunchKernelGGL(k_initial_values_function_points<E>, dim3(grid_for(n, kInitialValuesBlock)),
+                       dim3(kInitialValuesBlock), 0, stream, iv, d_iv_function.ptr, (uint32_t)n, d_points, t, stride,
+                       d_out);
+  } else if constexpr (is_scalar_v<E>) {
+    throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: scalar conservation has the function state only");
+  } else {
+    hipLaunchKernelGGL(k_initial_values_points<E>, dim3(grid_for(n, kInitialValuesBlock)), dim3(kInitialValuesBlock),
+                       0, stream, iv, (uint32_t)n, d_points, t, stride, d_out);
+  }
   HIP_CHECK(hipGetLastError());
 }
 
@@ -1353,8 +1362,15 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStag
      * every kernel of the previous stage that read the buffer (compute stream order; the export part of the previous
      * pre-pass may have applied boundary conditions on comm_stream) and behind the step-4 kernel of the first stage,
      * which left tau_rk. Nothing on the host waits for tau. */
-    if constexpr (is_scalar_v<E>) {
-      throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: scalar conservation is not offered");
+    if (iv.state == kIvFunction) {
+      join_export();
+      hipLaunchKernelGGL(k_initial_values_function_dirichlet<E>, dim3(grid_for(n_bdry, kInitialValuesBlock)),
+                         dim3(kInitialValuesBlock), 0, stream, iv, d_iv_function.ptr, n_bdry, d_iv_b_positions.ptr,
+                         d_b_id.ptr, iv_stage.t, iv_stage.c, d_scalars.ptr, d_dirichlet.ptr);
+      HIP_CHECK(hipGetLastError());
+      have_dirichlet = true;
+    } else if constexpr (is_scalar_v<E>) {
+      throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: scalar conservation has the function state only");
     } else {
       join_export();
       hipLaunchKernelGGL(k_initial_values_dirichlet<E>, dim3(grid_for(n_bdry, kInitialValuesBlock)),
@@ -3884,21 +3900,58 @@ int ryujin_hip_quantities_time_series(ryujin_hip_ctx *ctx, int manifold, double 
 
 namespace
 {
-  /* the Descriptions that have analytic states here: everything but scalar conservation */
+  /* the Descriptions that have analytic states here: everything but scalar conservation, which has the function
+   * state (ryujin_hip_initial_values_configure_function) and nothing else */
   template <typename F>
   auto dispatch_initial_values(ryujin_hip_ctx *ctx, F &&f)
   {
-    if (ctx->params.equation == RYUJIN_EQ_SCALAR_CONSERVATION)
+    if (ctx->params.equation == RYUJIN_EQ_SCALAR_CONSERVATION && ctx->iv.state != kIvFunction)
       throw HipError(RYUJIN_ERR_UNSUPPORTED,
-                     "initial values: scalar conservation is not offered (the reference's configurations use "
-                     "the muparser \"function\" state there)");
-    return dispatch_equation(ctx->params.equation, ctx->dim, [&](auto tag) {
-      using E = typename decltype(tag)::type;
-      if constexpr (std::is_same<typename E::Params, ScalarParams>::value)
-        return RYUJIN_ERR_UNSUPPORTED;
-      else
-        return f(tag);
-    });
+                     "initial values: scalar conservation has the function state only "
+                     "(ryujin_hip_initial_values_configure_function)");
+    return dispatch_equation(ctx->params.equation, ctx->dim, [&](auto tag) { return f(tag); });
+  }
+
+  /* InitialValues::parse_parameters_callback (initial_values.template.h:154-196): `position`, and the rolls of
+   * affine_transform (:78-106) that take the normalised `direction` onto the x-axis */
+  void set_initial_values_frame(InitialValuesParams &P, const int dim, const double *direction,
+                                const double *position)
+  {
+    for (int d = 0; d < dim; ++d)
+      P.position[d] = position[d];
+    double n[3] = {0., 0., 0.}, norm2 = 0.;
+    for (int d = 0; d < dim; ++d)
+      norm2 += direction[d] * direction[d];
+    const double norm = std::sqrt(norm2);
+    if (!(norm > 0.) || std::isinf(norm))
+      throw HipError(RYUJIN_ERR_ARG, "initial values: direction is the zero vector (or not finite)");
+    for (int d = 0; d < dim; ++d)
+      n[d] = direction[d] / norm;
+    if (dim == 3) {
+      const double r = std::sqrt(n[0] * n[0] + n[2] * n[2]);
+      P.roll_z = r > 1.0e-14;
+      P.nz_x = n[0] / r;
+      P.nz_z = n[2] / r;
+    }
+    if (dim >= 2) {
+      const double r = std::sqrt(n[0] * n[0] + n[1] * n[1]);
+      P.roll_y = r > 1.0e-14;
+      P.ny_x = n[0] / r;
+      P.ny_y = n[1] / r;
+    }
+  }
+
+  /* the node positions and the boundary positions in the library's grouped order; a second configure replaces the
+   * first: nothing enqueued may still read the old positions or programs */
+  void upload_initial_values_positions(ryujin_hip_ctx *ctx, const double *positions, const double *b_positions)
+  {
+    const size_t dim = (size_t)ctx->dim;
+    ctx->d_iv_positions.upload(positions, (size_t)ctx->L.n_relevant * dim);
+    std::vector<double> grouped((size_t)ctx->n_bdry * dim);
+    for (uint32_t e = 0; e < ctx->n_bdry; ++e)
+      for (size_t d = 0; d < dim; ++d)
+        grouped[(size_t)e * dim + d] = b_positions[(size_t)ctx->bdry_perm[e] * dim + d];
+    ctx->d_iv_b_positions.upload(grouped);
   }
 
   /* InitialValues::parse_parameters_callback (initial_values.template.h:154-196) and the constructors of the
@@ -3926,30 +3979,7 @@ namespace
     P.state = in.state;
     for (int q = 0; q < 16; ++q)
       P.p[q] = in.params[q];
-    for (int d = 0; d < dim; ++d)
-      P.position[d] = in.position[d];
-
-    /* initial_direction_ /= initial_direction_.norm(), then the rolls of affine_transform (:78-106) */
-    double n[3] = {0., 0., 0.}, norm2 = 0.;
-    for (int d = 0; d < dim; ++d)
-      norm2 += in.direction[d] * in.direction[d];
-    const double norm = std::sqrt(norm2);
-    if (!(norm > 0.) || std::isinf(norm))
-      throw HipError(RYUJIN_ERR_ARG, "initial values: direction is the zero vector (or not finite)");
-    for (int d = 0; d < dim; ++d)
-      n[d] = in.direction[d] / norm;
-    if (dim == 3) {
-      const double r = std::sqrt(n[0] * n[0] + n[2] * n[2]);
-      P.roll_z = r > 1.0e-14;
-      P.nz_x = n[0] / r;
-      P.nz_z = n[2] / r;
-    }
-    if (dim >= 2) {
-      const double r = std::sqrt(n[0] * n[0] + n[1] * n[1]);
-      P.roll_y = r > 1.0e-14;
-      P.ny_x = n[0] / r;
-      P.ny_y = n[1] / r;
-    }
+    set_initial_values_frame(P, dim, in.direction, in.position);
 
     const ryujin_hip_params &hp = ctx.params;
     if (eq == RYUJIN_EQ_EULER_AEOS) {
@@ -4066,18 +4096,68 @@ int ryujin_hip_initial_values_configure(ryujin_hip_ctx *ctx, const ryujin_hip_in
     const InitialValuesParams P = make_initial_values_params(*ctx, *initial_values);
     if ((!positions && ctx->L.n_relevant > 0) || (!b_positions && ctx->n_bdry > 0))
       throw HipError(RYUJIN_ERR_ARG, "initial values: positions missing");
-    const size_t dim = (size_t)ctx->dim;
-    /* a second configure replaces the first: nothing enqueued may still read the old positions */
     ctx->finish();
     ctx->iv_configured = false;
-    ctx->d_iv_positions.upload(positions, (size_t)ctx->L.n_relevant * dim);
-    std::vector<double> grouped((size_t)ctx->n_bdry * dim);
-    for (uint32_t e = 0; e < ctx->n_bdry; ++e)
-      for (size_t d = 0; d < dim; ++d)
-        grouped[(size_t)e * dim + d] = b_positions[(size_t)ctx->bdry_perm[e] * dim + d];
-    ctx->d_iv_b_positions.upload(grouped);
+    upload_initial_values_positions(ctx, positions, b_positions);
     ctx->iv = P;
     ctx->iv_configured = true;
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_initial_values_configure_function(ryujin_hip_ctx *ctx, int n_expressions,
+                                                 const char *const *expressions, const double direction[3],
+                                                 const double position[3], const double *positions,
+                                                 const double *b_positions)
+{
+  return guarded_ctx(ctx, [&]() {
+    static_assert(kExprOk == RYUJIN_OK && kExprErrArg == RYUJIN_ERR_ARG && kExprErrUnsupported == RYUJIN_ERR_UNSUPPORTED,
+                  "expression.hpp and the header agree");
+    if (!expressions || !direction || !position)
+      throw HipError(RYUJIN_ERR_ARG, "initial values: null argument");
+    if (n_expressions != ctx->K)
+      throw HipError(RYUJIN_ERR_ARG, "initial values: " + std::to_string(n_expressions) + " expressions for " +
+                                         std::to_string(ctx->K) + " primitive components");
+    /* everything that can be refused comes first: a refused call leaves the previous configuration in place */
+    auto program = std::make_unique<IvFunctionProgram>();
+    program->n = 0;
+    program->pad = 0;
+    auto one = std::make_unique<ExprProgram>();
+    for (int q = 0; q < n_expressions; ++q) {
+      std::string error;
+      if (const int status = expr_compile(expressions[q], ctx->dim, *one, error))
+        throw HipError(status, "initial values: component " + std::to_string(q) + ": " + error);
+      std::copy(one->code, one->code + one->n, program->code + program->n);
+      program->n += one->n;
+      program->code[program->n++] = ExprInstruction{kExResult, q, 0.};
+    }
+    InitialValuesParams P{};
+    P.state = kIvFunction;
+    P.c[0] = ctx->params.gamma; /* Euler: from_primitive_state */
+    set_initial_values_frame(P, ctx->dim, direction, position);
+    if ((!positions && ctx->L.n_relevant > 0) || (!b_positions && ctx->n_bdry > 0))
+      throw HipError(RYUJIN_ERR_ARG, "initial values: positions missing");
+    ctx->finish();
+    ctx->iv_configured = false;
+    upload_initial_values_positions(ctx, positions, b_positions);
+    ctx->d_iv_function.upload(program.get(), 1);
+    ctx->iv = P;
+    ctx->iv_configured = true;
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_expression_evaluate(const char *expression, int dim, const double *points, size_t n, double t,
+                                   double *out)
+{
+  return guarded([&]() {
+    if (!expression || (n > 0 && (!points || !out)))
+      throw HipError(RYUJIN_ERR_ARG, "expression_evaluate: null argument");
+    auto program = std::make_unique<ExprProgram>();
+    std::string error;
+    if (const int status = expr_compile(expression, dim, *program, error))
+      throw HipError(status, error);
+    expr_evaluate_points(*program, dim, points, n, t, out);
     return RYUJIN_OK;
   });
 }

@@ -130,6 +130,20 @@ def aeos_from_primitive(params, rho, vel, p):
     return U
 
 
+def aeos_from_primitive_state(rho, vel, e):
+    """HyperbolicSystemView::from_primitive_state (source/euler_aeos/hyperbolic_system.h:1473-1493): primitive
+    (rho, v, e) with e the SPECIFIC INTERNAL ENERGY -> (rho, rho v, rho e + rho |v|^2 / 2); no equation of state
+    enters. What the reference's "function" state calls with its "pressure expression" in the last slot."""
+    rho = np.asarray(rho, dtype=np.float64)
+    vel = np.asarray(vel, dtype=np.float64)
+    e = np.asarray(e, dtype=np.float64)
+    U = np.empty(vel.shape[:-1] + (vel.shape[-1] + 2,), dtype=np.float64)
+    U[..., 0] = rho
+    U[..., 1:-1] = rho[..., None] * vel
+    U[..., -1] = rho * e + 0.5 * rho * np.sum(vel * vel, axis=-1)
+    return U
+
+
 # ---------------------------------------------------------------------------
 # Analytic solutions of the reference's verification configurations (1-D ones take x relative to
 # the `position` of subsection "E - InitialValues", direction +1)

@@ -267,6 +267,30 @@ class HyperbolicModule:
             self._ctx, C.byref(iv), capi.as_ptr(pos, capi.c_double_p) if pos.size else None,
             capi.as_ptr(bpos, capi.c_double_p) if bpos.size else None))
 
+    def initial_values_configure_function(self, expressions, *, direction=None, position=None) -> None:
+        """Select the expression-defined state "function" (ryujin_hip_initial_values_configure_function): one
+        expression in x [y [z]] and t per primitive component -- a sequence in primitive order, or a dict keyed by the
+        reference's parameter names ("density expression", "velocity x expression", ..., "pressure expression";
+        "water depth expression"; "expression") in which a missing key takes the reference's default. The grammar is
+        tabulated in include/ryujin_hip.h. Replaces an earlier initial_values_configure and is replaced by it."""
+        texts = capi.function_expressions(self.params.equation, self.dim, expressions)
+        d = (1.0,) + (0.0,) * (self.dim - 1) if direction is None else tuple(np.atleast_1d(direction).astype(float))
+        x = (0.0,) * self.dim if position is None else tuple(np.atleast_1d(position).astype(float))
+        if len(d) != self.dim or len(x) != self.dim:
+            raise ValueError(f"direction and position take {self.dim} components")
+        d3 = np.array(d + (0.0,) * (3 - self.dim))
+        x3 = np.array(x + (0.0,) * (3 - self.dim))
+        pos = np.ascontiguousarray(self.offline.positions, dtype=np.float64).reshape(-1)
+        assert pos.size == self.n_relevant * self.dim
+        bpos = np.ascontiguousarray(self.offline.b_positions, dtype=np.float64).reshape(-1) \
+            if self.offline.n_bdry else np.zeros(0)
+        assert bpos.size == self.offline.n_bdry * self.dim
+        array = (C.c_char_p * len(texts))(*[e.encode() for e in texts])
+        self._check(self._f("initial_values_configure_function")(
+            self._ctx, len(texts), array, capi.as_ptr(d3, capi.c_double_p), capi.as_ptr(x3, capi.c_double_p),
+            capi.as_ptr(pos, capi.c_double_p) if pos.size else None,
+            capi.as_ptr(bpos, capi.c_double_p) if bpos.size else None))
+
     def initial_values_evaluate(self, points, t: float) -> np.ndarray:
         """[n, k]: initial_state(points[n, dim], t) of the configured state, evaluated on the device"""
         points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, self.dim)

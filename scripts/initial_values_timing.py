@@ -20,7 +20,13 @@
 3. `--trace-target`: nothing but 200 steps of time_step_iv on vortex-256, to be run under
    `rocprofv3 --kernel-trace --stats -- python scripts/initial_values_timing.py --trace-target` for the Dirichlet
    kernel's own time (no counters are collected in that run).
-Usage: initial_values_timing.py [--steps 40] [--passes 5] [--warmup 10] [--skip-large]   (prints markdown)"""
+4. `--function-state`: the expression-defined "function" state (ryujin_hip_initial_values_configure_function) with
+   the isentropic vortex written as expressions, against the built-in state, the drivers alternating in one process:
+   prepare_state_vector_iv per call on the 256 x 256 mesh (device events over 200 calls; the Dirichlet kernel is the
+   only kernel of the call that differs), ERK33 wall clock per step there (iv function, iv built-in, fn numpy), and
+   interpolate of 2.5 M points (device events). Only this part runs; profiles/initial_values_function_timing.md.
+Usage: initial_values_timing.py [--steps 40] [--passes 5] [--warmup 10] [--skip-large] [--function-state]
+(prints markdown)"""
 import argparse
 import ctypes as C
 import os
@@ -39,6 +45,7 @@ ap.add_argument("--passes", type=int, default=5)
 ap.add_argument("--warmup", type=int, default=10)
 ap.add_argument("--skip-large", action="store_true")
 ap.add_argument("--trace-target", action="store_true")
+ap.add_argument("--function-state", action="store_true")
 args = ap.parse_args()
 lib = capi.load_hip()
 
@@ -166,6 +173,107 @@ def measure_interpolate():
     m.close()
     off.close()
 
+
+def vortex_expressions(mach=1.0, beta=5.0, gamma=1.4):
+    """ryujin_amd.initial_states.euler_isentropic_vortex_primitive, statement by statement"""
+    xb = f"(x - {mach!r} * t)"
+    f = f"({beta!r} / (2 * _pi) * exp(0.5 - 0.5 * ({xb} * {xb} + y * y)))"
+    T = f"(1 - ({gamma!r} - 1) / (2 * {gamma!r}) * {f} * {f})"
+    rho = f"pow({T}, 1 / ({gamma!r} - 1))"
+    return [rho, f"{mach!r} - {f} * y", f"{f} * {xb}", f"pow({rho}, {gamma!r})"]
+
+
+def measure_function_state():
+    frame = dict(direction=(1.0, 1.0), position=(-1.0, -1.0))
+    configure = {
+        "built-in": lambda m: m.initial_values_configure("isentropic vortex", mach_number=1.0, beta=5.0, **frame),
+        "function": lambda m: m.initial_values_configure_function(vortex_expressions(), **frame),
+    }
+    e = C.c_double()
+
+    def events(m, body):
+        lib.ryujin_hip_synchronize(m._ctx)
+        lib.ryujin_hip_event_record(m._ctx, 0)
+        body()
+        lib.ryujin_hip_event_record(m._ctx, 1)
+        assert lib.ryujin_hip_event_elapsed_ms(m._ctx, C.byref(e)) == 0
+        return e.value
+
+    f = lambda v: f"{np.median(v):.4f} ({min(v):.4f} - {max(v):.4f})"  # noqa: E731
+
+    # a. prepare_state_vector_iv per call, b. ERK33 per step: vortex-256
+    off = offline.SyntheticOffline(offline.rectangle_2d(256, (-5.0, -5.0), (5.0, 5.0), bc=capi.BC_DIRICHLET))
+    m = HyperbolicModule(off, params(capi.EQ_EULER, 2), backend="hip")
+    m.cfl = 0.3
+    configure["built-in"](m)
+    state = m.new_state_vector()
+    m.initial_values_interpolate(state, 0.0)
+    temps = [m.new_state_vector() for _ in range(3)]
+    bpos = off.b_positions
+    exact = lambda t: ist.euler_isentropic_vortex(bpos, t)  # noqa: E731
+    calls = 200
+    prepare = {k: [] for k in configure}
+    step = {"iv function": [], "iv built-in": [], "fn numpy": []}
+    t = 0.0
+    for p in range(args.passes + 1):
+        for key in configure:
+            configure[key](m)
+            ms = events(m, lambda: [m.prepare_state_vector(state, t, "device") for _ in range(calls)]) / calls
+            t = rk_steps(m, state, temps, 0.3, args.warmup if p == 0 else 2, t, "iv")
+            w0 = time.perf_counter()
+            t = rk_steps(m, state, temps, 0.3, args.steps, t, "iv")
+            wall = (time.perf_counter() - w0) * 1e3 / args.steps
+            if p > 0:
+                prepare[key].append(ms)
+                step["iv " + key].append(wall)
+        t = rk_steps(m, state, temps, 0.3, 2, t, "fn", exact)
+        w0 = time.perf_counter()
+        t = rk_steps(m, state, temps, 0.3, args.steps, t, "fn", exact)
+        if p > 0:
+            step["fn numpy"].append((time.perf_counter() - w0) * 1e3 / args.steps)
+    assert np.isfinite(state.download()).all()
+    print(f"\n### function state, vortex-256: {off.n_owned} gridpoints, {off.n_bdry} boundary map entries, "
+          f"{args.passes} passes\n")
+    print("| | ms, median pass (min - max) |")
+    print("|---|---|")
+    for key in configure:
+        print(f"| prepare_state_vector_iv per call, {key} (device events over {calls} calls) | {f(prepare[key])} |")
+    for key, v in step.items():
+        print(f"| ERK33 wall clock per step, {key} ({args.steps} steps) | {f(v)} |")
+    med = lambda v: float(np.median(v))  # noqa: E731
+    print(f"\nDirichlet kernel, function - built-in = "
+          f"{(med(prepare['function']) - med(prepare['built-in'])) * 1e3:.2f} us per call; ERK33 step: iv function / "
+          f"iv built-in = {med(step['iv function']) / med(step['iv built-in']):.3f}, fn numpy / iv function = "
+          f"{med(step['fn numpy']) / med(step['iv function']):.3f}.")
+    m.close()
+    off.close()
+
+    # c. interpolate, 2.5 M points
+    off = offline.SyntheticOffline(offline.rectangle_2d(1580, (-5.0, -5.0), (5.0, 5.0), bc=capi.BC_DIRICHLET))
+    m = HyperbolicModule(off, params(capi.EQ_EULER, 2), backend="hip")
+    sv = m.new_state_vector()
+    dev = {k: [] for k in configure}
+    for p in range(args.passes + 1):
+        for key in configure:
+            configure[key](m)
+            ms = events(m, lambda: m.initial_values_interpolate(sv, 0.25))
+            if p > 0:
+                dev[key].append(ms)
+    print(f"\n### function state, interpolate: {off.n_relevant} points, {args.passes} passes\n")
+    print("| | ms, median (min - max), device events |")
+    print("|---|---|")
+    for key in configure:
+        print(f"| initial_values_interpolate, {key} | {f(dev[key])} |")
+    print(f"\nfunction / built-in = {med(dev['function']) / med(dev['built-in']):.2f}.")
+    m.close()
+    off.close()
+
+
+if args.function_state:
+    print(f"<!-- scripts/initial_values_timing.py --function-state --steps {args.steps} --passes {args.passes} "
+          f"--warmup {args.warmup} -->")
+    measure_function_state()
+    sys.exit(0)
 
 if args.trace_target:
     off, m, cfl, _ = vortex(256)()

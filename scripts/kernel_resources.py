@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Register / scratch / occupancy table of the HIP kernels from hipcc's -Rpass-analysis=kernel-resource-usage
+"""Register / scratch / occupancy / LDS table of the HIP kernels from hipcc's -Rpass-analysis=kernel-resource-usage
 (no GPU needed). usage: kernel_resources.py [substring filter ...]  [-D...]"""
 import os
 import re
@@ -21,6 +21,7 @@ for name, d, block in zip(names, dem, re.split(r"remark: Function Name: ", txt)[
     if filters and not any(f in short for f in filters):
         continue
     g = lambda k: (re.search(k + r": (\d+)", block) or [None, ""])[1]  # noqa: E731
-    print("%-78s vgpr %4s agpr %4s scratch %4s occ %s" % (short[:78], g("VGPRs"), g("AGPRs"),
-                                                          g(r"ScratchSize \[bytes/lane\]"),
-                                                          g(r"Occupancy \[waves/SIMD\]")))
+    print("%-78s vgpr %4s agpr %4s scratch %4s occ %s lds %s" % (short[:78], g("VGPRs"), g("AGPRs"),
+                                                                 g(r"ScratchSize \[bytes/lane\]"),
+                                                                 g(r"Occupancy \[waves/SIMD\]"),
+                                                                 g(r"LDS Size \[bytes/block\]")))
