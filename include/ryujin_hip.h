@@ -53,10 +53,13 @@ enum {
   RYUJIN_EQ_SCALAR_CONSERVATION = 3
 };
 
-/* FluxLibrary (source/scalar_conservation/flux_library.h). "function" takes a muparser expression in
- * the reference; here its polynomial subset sum_n c_n u^n per direction (covers "u", "0.5*u*u", ...),
- * with the same central-difference gradient (flux_function.h:80-84). */
-enum { RYUJIN_FLUX_BURGERS = 0, RYUJIN_FLUX_KPP = 1, RYUJIN_FLUX_POLYNOMIAL = 2 };
+/* FluxLibrary (source/scalar_conservation/flux_library.h). "function" takes a muparser expression in u in the
+ * reference, with the central-difference gradient of dealii::FunctionParser (flux_function.h:80-84). Here it comes
+ * twice: RYUJIN_FLUX_POLYNOMIAL, its polynomial subset sum_n c_n u^n per direction in closed form, and
+ * RYUJIN_FLUX_FUNCTION, any expression of the grammar table under "The function state" below in the single variable
+ * u -- THAT TABLE IS THE CONTRACT here too --, evaluated by the library's interpreter on the device
+ * (ryujin_hip_flux_configure_function below). Both form the gradient as (f(u + delta) - f(u - delta)) / (2 * delta). */
+enum { RYUJIN_FLUX_BURGERS = 0, RYUJIN_FLUX_KPP = 1, RYUJIN_FLUX_POLYNOMIAL = 2, RYUJIN_FLUX_FUNCTION = 3 };
 
 /* EquationOfStateLibrary (source/euler_aeos/equation_of_state_library.h): the closed-form members.
  * "sesame" (tabulated, needs EOSPAC) and "function" (muparser) are host-library bound and not offered. */
@@ -140,7 +143,7 @@ typedef struct ryujin_hip_params {
    * source/scalar_conservation/hyperbolic_system.h:510-540 and "/riemann solver" riemann_solver.h:26-55 */
   int sc_flux;                                /* RYUJIN_FLUX_*: burgers */
   double sc_flux_polynomial[3][4];            /* RYUJIN_FLUX_POLYNOMIAL: c_0..c_3 per direction */
-  double sc_derivative_approximation_delta;   /* "function": 1e-10 */
+  double sc_derivative_approximation_delta;   /* "function" (POLYNOMIAL and FUNCTION): 1e-10 */
   int sc_use_greedy_wavespeed;                /* 0 */
   int sc_use_averaged_entropy;                /* 0 */
   int sc_random_entropies;                    /* 0; > 0 is not reproducible in the reference: rejected */
@@ -817,6 +820,38 @@ int ryujin_hip_initial_values_configure_function(ryujin_hip_ctx *ctx, int n_expr
                                                  const double *b_positions);
 int ryujin_hip_expression_evaluate(const char *expression, int dim, const double *points, size_t n, double t,
                                    double *out);
+
+/* ---- The function flux: FluxLibrary "function" of the scalar conservation equation ---- */
+/* source/scalar_conservation/flux_function.h: ONE expression string in the variable u, its components separated by
+ * ';', exactly one per space dimension ("sin(u); cos(u)" in 2-D); the gradient is the central difference quotient
+ * (f(u + delta) - f(u - delta)) / (2 * delta). The grammar is the table above with the single variable u: x, y, z and
+ * t are unknown identifiers here (RYUJIN_ERR_ARG). Any other number of components, an empty component included (a
+ * trailing ';'), is RYUJIN_ERR_ARG; the limits -- RYUJIN_EXPR_MAX_INSTRUCTIONS, RYUJIN_EXPR_MAX_STACK, nesting 64 --
+ * hold per component; ryujin_hip_last_error names the character, counted from 0 in the WHOLE string. A context created
+ * with sc_flux = RYUJIN_FLUX_FUNCTION starts from the reference's default "0.5*u*u" (in every direction) and
+ * sc_derivative_approximation_delta.
+ *   flux_configure_function   valid on a scalar conservation context created with any flux (RYUJIN_ERR_UNSUPPORTED for
+ *                             the other Descriptions, and for what the table refuses with that status); afterwards the
+ *                             context uses the function flux. RYUJIN_ERR_ARG: delta <= 0 or not finite, a parse error.
+ *                             A refused call leaves the earlier flux in place. It may be called between updates (it
+ *                             waits for the stream) and takes effect at the next prepare_state_vector; on several
+ *                             ranks every rank's context is configured by its own call.
+ *                             On the device f(u) and the difference quotient are formed once per node by the
+ *                             interpreter (three runs of the programs); everything behind the precomputed values is
+ *                             the code of the other fluxes. With sc_use_averaged_entropy the Riemann solver evaluates
+ *                             f((u_i + u_j) / 2) per pair as well: steps 2 and 3 then run kernels with the interpreter
+ *                             in their column loop (ryujin_hip_flux_info: step2_interpreted).
+ *   flux_function_evaluate    needs no context and no device: the host interpreter of the same source. value and
+ *                             gradient are [n][dim]; gradient may be NULL; n = 0 returns RYUJIN_OK and writes nothing.
+ *   flux_info                 what the latest update ran, from host values (before the first update: what the next
+ *                             one would run, step2_interpreted = 0): kind = RYUJIN_FLUX_*, n_instructions = the
+ *                             instructions of all components (0 unless the function flux), step2_interpreted = 1 if
+ *                             step 2 ran the interpreter kernel. Any of the three pointers may be NULL. */
+int ryujin_hip_flux_configure_function(ryujin_hip_ctx *ctx, const char *expression,
+                                       double derivative_approximation_delta);
+int ryujin_hip_flux_function_evaluate(const char *expression, int dim, double delta, const double *u, size_t n,
+                                      double *value, double *gradient);
+int ryujin_hip_flux_info(ryujin_hip_ctx *ctx, int *kind, int *n_instructions, int *step2_interpreted);
 
 /* ---- Error norms: analytic-solution error of a verification run, device resident -- */
 /* The norms of TimeLoop::compute_error() of the reference (source/time_loop.template.h:692-833) between the state

@@ -20,7 +20,7 @@ c_int_p = C.POINTER(C.c_int)
 RYUJIN_OK, RYUJIN_WARN, RYUJIN_RESTART = 0, 1, 2
 RYUJIN_ERR_TAU, RYUJIN_ERR_ARG, RYUJIN_ERR_HIP, RYUJIN_ERR_COMM, RYUJIN_ERR_UNSUPPORTED = -1, -2, -3, -4, -5
 EQ_EULER, EQ_SHALLOW_WATER, EQ_EULER_AEOS, EQ_SCALAR_CONSERVATION = 0, 1, 2, 3
-FLUX_BURGERS, FLUX_KPP, FLUX_POLYNOMIAL = 0, 1, 2
+FLUX_BURGERS, FLUX_KPP, FLUX_POLYNOMIAL, FLUX_FUNCTION = 0, 1, 2, 3
 EOS_POLYTROPIC_GAS, EOS_NOBLE_ABEL_STIFFENED_GAS, EOS_VAN_DER_WAALS, EOS_JONES_WILKINS_LEE = 0, 1, 2, 3
 BC_DO_NOTHING, BC_PERIODIC, BC_SLIP, BC_NO_SLIP, BC_DIRICHLET, BC_DYNAMIC, BC_DIRICHLET_MOMENTUM = range(7)
 IDV_WARN, IDV_RAISE_EXCEPTION = 0, 1
@@ -225,6 +225,26 @@ def expression_evaluate(expr: str, dim: int, points, t: float) -> np.ndarray:
     return out
 
 
+def flux_function_evaluate(expr: str, dim: int, u, delta: float = 1e-10, gradient: bool = True):
+    """(value [n, dim], gradient [n, dim] or None) of the function flux `expr` -- one string in u, `dim` components
+    separated by ';' -- at the states u [n], through the library's host interpreter
+    (ryujin_hip_flux_function_evaluate; no device). RuntimeError with .status for a refused expression."""
+    lib = load_hip()
+    u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+    value = np.zeros((u.size, dim), dtype=np.float64)
+    grad = np.zeros((u.size, dim), dtype=np.float64) if gradient else None
+    rc = lib.ryujin_hip_flux_function_evaluate(expr.encode(), dim, float(delta),
+                                               as_ptr(u, c_double_p) if u.size else None, u.size,
+                                               as_ptr(value, c_double_p) if value.size else None,
+                                               as_ptr(grad, c_double_p) if gradient and grad.size else None)
+    if rc < 0:
+        error = RuntimeError(f"ryujin_hip_flux_function_evaluate failed with status {rc}: "
+                             f"{lib.ryujin_hip_last_error().decode()}")
+        error.status = rc
+        raise error
+    return value, grad
+
+
 def component_names(equation: int, dim: int) -> tuple[tuple[str, ...], tuple[str, ...]]:
     """(View::component_names, View::primitive_component_names) of a Description
     (source/<eq>/hyperbolic_system.h)."""
@@ -348,6 +368,7 @@ HIP_SYMBOLS = [
     "ryujin_hip_initial_values_interpolate", "ryujin_hip_prepare_state_vector_iv", "ryujin_hip_time_step_iv",
     "ryujin_hip_initial_values_configure_function", "ryujin_hip_expression_evaluate",
     "ryujin_hip_error_norms_configure", "ryujin_hip_error_norms_compute",
+    "ryujin_hip_flux_configure_function", "ryujin_hip_flux_function_evaluate", "ryujin_hip_flux_info",
 ]
 
 
@@ -461,5 +482,9 @@ def load_hip():
                                                          c_double_p, c_double_p, C.c_int]
         lib.ryujin_hip_error_norms_compute.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int_p, C.c_int, c_double_p,
                                                        c_double_p]
+        lib.ryujin_hip_flux_configure_function.argtypes = [vp, C.c_char_p, C.c_double]
+        lib.ryujin_hip_flux_function_evaluate.argtypes = [C.c_char_p, C.c_int, C.c_double, c_double_p, C.c_size_t,
+                                                          c_double_p, c_double_p]
+        lib.ryujin_hip_flux_info.argtypes = [vp, c_int_p, c_int_p, c_int_p]
         _hip = lib
     return _hip

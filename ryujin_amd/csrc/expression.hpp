@@ -5,7 +5,9 @@
 // recursive-descent parser for the subset of that grammar tabulated in include/ryujin_hip.h ("The function state"),
 // compiled once into a flat postfix program of fixed-size instructions that ONE interpreter body, expr_evaluate(),
 // runs on the host (ryujin_hip_expression_evaluate, tests/cpp/expression_cases.cc) and on the device
-// (initial_states_device.hpp). Host standard library only -- no HIP, no context. Under hipcc RYUJIN_EXPR_HD makes the
+// (initial_states_device.hpp). The flux of the scalar conservation equation (FluxLibrary "function", one string in the
+// variable u with a component per direction) is its second consumer: flux_compile() and flux_evaluate_points() at the
+// end of this file, the kernels in scalar_conservation_device.hpp. Host standard library only -- no HIP, no context. Under hipcc RYUJIN_EXPR_HD makes the
 // interpreter a host and device function; the parser is host code.
 //
 // The interpreter keeps the top of the operand stack in a register and everything below it behind a `Stack`
@@ -46,7 +48,7 @@ namespace ryujin_hip
 
   enum ExprOp : int {
     kExConst = 0, /* push value */
-    kExVar,       /* push variable `slot`: 0 x, 1 y, 2 z, 3 t */
+    kExVar,       /* push variable `slot`: 0 x, 1 y, 2 z, 3 t (the flux: 0 u) */
     /* two operands */
     kExAdd, kExSub, kExMul, kExDiv,
     kExPow,                                   /* a ^ b and pow(a, b) through pow_fn */
@@ -194,13 +196,39 @@ namespace ryujin_hip
     double operator()(const double a, const double b) const { return std::pow(a, b); }
   };
 
+  /* The variable names an expression may use, in the order of their slots. The first `n_spatial` of them are
+   * coordinates: the one with index v is defined from dimension v + 1 on. */
+  struct ExprVariables {
+    const char *const *names;
+    int n, n_spatial;
+  };
+
+  inline ExprVariables expr_variables_xyzt()
+  {
+    static const char *const names[4] = {"x", "y", "z", "t"};
+    return ExprVariables{names, 4, 3};
+  }
+
+  /* the flux of the scalar conservation equation: the state alone (x, y, z and t are unknown identifiers) */
+  inline ExprVariables expr_variables_u()
+  {
+    static const char *const names[1] = {"u"};
+    return ExprVariables{names, 1, 0};
+  }
+
   class ExprParser
   {
   public:
-    ExprParser(const char *text, const int dim, ExprProgram &program)
+    /* the expression is text[begin, end), end = npos: up to the terminator; positions count in the whole of `text` */
+    ExprParser(const char *text, const int dim, ExprProgram &program,
+               const ExprVariables &variables = expr_variables_xyzt(), const size_t begin = 0,
+               const size_t end = (size_t)-1)
         : s_(text)
-        , len_(std::strlen(text))
+        , len_(end == (size_t)-1 ? std::strlen(text) : end)
+        , pos_(begin)
+        , begin_(begin)
         , dim_(dim)
+        , vars_(variables)
         , prog_(program)
     {
     }
@@ -212,7 +240,7 @@ namespace ryujin_hip
       prog_.depth = 0;
       if (dim_ < 1 || dim_ > 3)
         fail(kExprErrArg, 0, "dimension outside 1 .. 3");
-      for (size_t i = 0; i < len_ && !status_; ++i)
+      for (size_t i = begin_; i < len_ && !status_; ++i)
         if (s_[i] == '"' || s_[i] == '\'')
           fail(kExprErrUnsupported, i, "string arguments are not offered");
       skip();
@@ -235,8 +263,9 @@ namespace ryujin_hip
 
   private:
     const char *s_;
-    size_t len_, pos_ = 0;
+    size_t len_, pos_, begin_;
     int dim_;
+    ExprVariables vars_;
     ExprProgram &prog_;
     int live_ = 0, nesting_ = 0;
     int status_ = 0;
@@ -515,10 +544,9 @@ namespace ryujin_hip
         return fail(kExprErrUnsupported, at, "'" + name + "' is not offered");
 
       if (!call) {
-        static const char *const variables[4] = {"x", "y", "z", "t"};
-        for (int v = 0; v < 4; ++v)
-          if (name == variables[v]) {
-            if (v < 3 && v >= dim_)
+        for (int v = 0; v < vars_.n; ++v)
+          if (name == vars_.names[v]) {
+            if (v < vars_.n_spatial && v >= dim_)
               return fail(kExprErrArg, at,
                           "variable '" + name + "' is not defined in dimension " + std::to_string(dim_));
             return emit(kExVar, +1, at, 0., v);
@@ -588,14 +616,16 @@ namespace ryujin_hip
     }
   };
 
-  /* `expression` over the first `dim` of x y z, then t -> `program`; kExprOk or the refusal with its message */
-  inline int expr_compile(const char *expression, const int dim, ExprProgram &program, std::string &error)
+  /* `expression` over `variables` (by default the first `dim` of x y z, then t) -> `program`; kExprOk or the refusal
+   * with its message */
+  inline int expr_compile(const char *expression, const int dim, ExprProgram &program, std::string &error,
+                          const ExprVariables &variables = expr_variables_xyzt())
   {
     if (!expression) {
       error = "expression: null string";
       return kExprErrArg;
     }
-    return ExprParser(expression, dim, program).compile(error);
+    return ExprParser(expression, dim, program, variables).compile(error);
   }
 
   /* out[i] = program(points[i * dim ..], t) with the host's library */
@@ -607,6 +637,98 @@ namespace ryujin_hip
       const double *p = points + i * (size_t)dim;
       out[i] = expr_evaluate(program.code, program.n, p[0], dim > 1 ? p[1] : 0., dim > 2 ? p[2] : 0., t, stack,
                              ExprHostPow{});
+    }
+  }
+
+  /* ---- the flux of the scalar conservation equation: FluxLibrary "function" -------------------------------------- */
+
+  /* source/scalar_conservation/flux_function.h: ONE string in the variable u, split at ';' into the components of the
+   * flux, one per space dimension; the gradient is the central difference quotient of dealii::FunctionParser. The
+   * programs of the components lie back to back, each closed by kExResult with its direction as `slot` (the layout of
+   * IvFunctionProgram, initial_states_device.hpp): the same for every lane of a wave. */
+  constexpr int kFluxMaxComponents = 3;
+
+  struct FluxProgram {
+    int n;              /* instructions, the kExResult closers included */
+    int n_instructions; /* ... without them: what the limit RYUJIN_EXPR_MAX_INSTRUCTIONS counts, summed over the components */
+    ExprInstruction code[kFluxMaxComponents * (RYUJIN_EXPR_MAX_INSTRUCTIONS + 1)];
+  };
+
+  /* `expression` in u with exactly `dim` components -> `program`; kExprOk or the refusal with its message. The limits
+   * (instructions, operands, nesting) hold per component; a character position counts in the whole string. */
+  inline int flux_compile(const char *expression, const int dim, FluxProgram &program, std::string &error)
+  {
+    program.n = 0;
+    program.n_instructions = 0;
+    if (!expression) {
+      error = "flux: null string";
+      return kExprErrArg;
+    }
+    if (dim < 1 || dim > kFluxMaxComponents) {
+      error = "flux: dimension outside 1 .. 3";
+      return kExprErrArg;
+    }
+    const size_t len = std::strlen(expression);
+    size_t semicolon[kFluxMaxComponents] = {len, len, len}; /* the first three of them */
+    int n_components = 1;
+    for (size_t i = 0; i < len; ++i)
+      if (expression[i] == ';') {
+        if (n_components <= kFluxMaxComponents)
+          semicolon[n_components - 1] = i;
+        ++n_components;
+      }
+    if (n_components != dim) {
+      const size_t at = n_components > dim ? semicolon[dim - 1] : len; /* the first ';' too many, or the end */
+      error = "flux: " + std::to_string(n_components) + " component(s) separated by ';' in dimension " +
+              std::to_string(dim) + " at character " + std::to_string(at) + " of \"" + expression + "\"";
+      return kExprErrArg;
+    }
+    ExprProgram *one = new ExprProgram;
+    int status = kExprOk;
+    for (int d = 0; d < dim; ++d) {
+      const size_t begin = d == 0 ? 0 : semicolon[d - 1] + 1;
+      const size_t end = d == dim - 1 ? len : semicolon[d];
+      std::string message;
+      status = ExprParser(expression, dim, *one, expr_variables_u(), begin, end).compile(message);
+      if (status != kExprOk) {
+        error = "flux: component " + std::to_string(d) + ": " + message;
+        break;
+      }
+      for (int i = 0; i < one->n; ++i)
+        program.code[program.n++] = one->code[i];
+      program.n_instructions += one->n;
+      program.code[program.n++] = ExprInstruction{kExResult, d, 0.};
+    }
+    delete one;
+    return status;
+  }
+
+  /* operands below the top one, then the values the kExResult closers leave */
+  struct FluxHostStack {
+    double v[RYUJIN_EXPR_MAX_STACK + kFluxMaxComponents];
+    double load(const int slot) const { return v[slot]; }
+    void store(const int slot, const double value) { v[slot] = value; }
+  };
+
+  /* value [n][dim] = f(u[i]) and, unless NULL, gradient [n][dim] = (f(u + delta) - f(u - delta)) / (2 * delta), in
+   * the operation order of the precompute kernel (scalar_conservation_device.hpp), with the host's library */
+  inline void flux_evaluate_points(const FluxProgram &program, const int dim, const double delta, const double *u,
+                                   const size_t n, double *value, double *gradient)
+  {
+    FluxHostStack stack;
+    for (size_t i = 0; i < n; ++i) {
+      expr_evaluate(program.code, program.n, u[i], 0., 0., 0., stack, ExprHostPow{});
+      for (int d = 0; d < dim; ++d)
+        value[i * (size_t)dim + d] = stack.load(RYUJIN_EXPR_MAX_STACK + d);
+      if (!gradient)
+        continue;
+      double plus[kFluxMaxComponents];
+      expr_evaluate(program.code, program.n, u[i] + delta, 0., 0., 0., stack, ExprHostPow{});
+      for (int d = 0; d < dim; ++d)
+        plus[d] = stack.load(RYUJIN_EXPR_MAX_STACK + d);
+      expr_evaluate(program.code, program.n, u[i] - delta, 0., 0., 0., stack, ExprHostPow{});
+      for (int d = 0; d < dim; ++d)
+        gradient[i * (size_t)dim + d] = (plus[d] - stack.load(RYUJIN_EXPR_MAX_STACK + d)) / (2 * delta);
     }
   }
 } // namespace ryujin_hip

@@ -372,6 +372,12 @@ struct ryujin_hip_ctx {
   ShallowWaterParams swparams{};
   EulerAeosParams aeosparams{};
   ScalarParams scparams{};
+  /* RYUJIN_FLUX_FUNCTION (ryujin_hip_flux_configure_function): the programs of the flux components, and what the
+   * latest update ran (ryujin_hip_flux_info; host values) */
+  DeviceBuffer<FluxProgram> d_flux_function;
+  int flux_n_instructions = 0;
+  int last_flux_kind = -1, last_flux_n_instructions = 0, last_step2_interpreted = 0;
+  bool flux_interpreted_pairs() const { return scparams.flux == RYUJIN_FLUX_FUNCTION && scparams.use_averaged_entropy; }
   DeviceBuffer<double> d_Z; /* initial_precomputed (bathymetry), shallow water only */
 
   template <typename E>
@@ -727,7 +733,7 @@ void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params
       p.equation != RYUJIN_EQ_EULER_AEOS && p.equation != RYUJIN_EQ_SCALAR_CONSERVATION)
     throw HipError(RYUJIN_ERR_UNSUPPORTED, "unknown equation");
   if (p.equation == RYUJIN_EQ_SCALAR_CONSERVATION) {
-    if (p.sc_flux < RYUJIN_FLUX_BURGERS || p.sc_flux > RYUJIN_FLUX_POLYNOMIAL)
+    if (p.sc_flux < RYUJIN_FLUX_BURGERS || p.sc_flux > RYUJIN_FLUX_FUNCTION)
       throw HipError(RYUJIN_ERR_UNSUPPORTED, "unknown flux");
     if (p.sc_flux == RYUJIN_FLUX_KPP && p.dim == 3)
       throw HipError(RYUJIN_ERR_UNSUPPORTED, "KPP is only defined in (1 or) 2 space dimensions");
@@ -791,8 +797,22 @@ void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params
     for (int n = 0; n < 4; ++n)
       scparams.poly[d][n] = p.sc_flux_polynomial[d][n];
   /* flux.h:33-34; the "function" flux reads its own parameter (flux_function.h:40-44) */
-  scparams.delta = p.sc_flux == RYUJIN_FLUX_POLYNOMIAL ? p.sc_derivative_approximation_delta
-                                                       : 1.e4 * std::numeric_limits<double>::epsilon();
+  scparams.delta = p.sc_flux == RYUJIN_FLUX_POLYNOMIAL || p.sc_flux == RYUJIN_FLUX_FUNCTION
+                       ? p.sc_derivative_approximation_delta
+                       : 1.e4 * std::numeric_limits<double>::epsilon();
+  if (p.equation == RYUJIN_EQ_SCALAR_CONSERVATION && p.sc_flux == RYUJIN_FLUX_FUNCTION) {
+    /* the default expression of flux_function.h:32, in every direction (as "burgers"), until
+     * ryujin_hip_flux_configure_function replaces it */
+    if (!(p.sc_derivative_approximation_delta > 0.) || !std::isfinite(p.sc_derivative_approximation_delta))
+      throw HipError(RYUJIN_ERR_ARG, "flux: derivative approximation delta must be positive and finite");
+    static const char *const defaults[3] = {"0.5*u*u", "0.5*u*u; 0.5*u*u", "0.5*u*u; 0.5*u*u; 0.5*u*u"};
+    auto program = std::make_unique<FluxProgram>();
+    std::string error;
+    if (const int status = flux_compile(defaults[p.dim >= 1 && p.dim <= 3 ? p.dim - 1 : 0], p.dim, *program, error))
+      throw HipError(status, error);
+    d_flux_function.upload(program.get(), 1);
+    flux_n_instructions = program->n_instructions;
+  }
   scparams.evc_factor = p.indicator_evc_factor;
   scparams.lim_relaxation_factor = p.limiter_relaxation_factor;
 
@@ -1467,7 +1487,16 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStag
     exchange_vector(s.prec.ptr, 4, true);
   } else if constexpr (std::is_same<typename E::Params, ScalarParams>::value) {
     sweep([&](const DeviceMesh &mm, dim3 grid) {
-      if (fold_bc)
+      if (eparams.flux == RYUJIN_FLUX_FUNCTION) {
+        /* the interpreter: a kernel of its own, one wave per block and slice */
+        const dim3 slices(mm.slice_end - mm.slice_begin), wave(kFluxFunctionBlock);
+        if (fold_bc)
+          hipLaunchKernelGGL((k_precompute_sc_function<E::DIMENSION, true>), slices, wave, 0, launch_stream, eparams, mm,
+                             bc, d_flux_function.ptr, s.U.ptr, s.prec.ptr);
+        else
+          hipLaunchKernelGGL((k_precompute_sc_function<E::DIMENSION, false>), slices, wave, 0, launch_stream, eparams,
+                             mm, bc, d_flux_function.ptr, s.U.ptr, s.prec.ptr);
+      } else if (fold_bc)
         hipLaunchKernelGGL((k_precompute_sc<E::DIMENSION, true>), grid, block, 0, launch_stream, eparams, mm, bc, s.U.ptr,
                          s.prec.ptr);
       else
@@ -1560,9 +1589,18 @@ void ryujin_hip_ctx::step2_dij_alpha(const StepPlan &plan, const State &old)
                          old.rrec.ptr, d_dij.ptr);
     });
   } else if constexpr (is_scalar_v<E>) {
+    /* the function flux enters step 2 through f((u_i + u_j) / 2) of the averaged entropy alone */
+    const bool interpreted = flux_interpreted_pairs();
+    last_flux_kind = eparams.flux;
+    last_flux_n_instructions = eparams.flux == RYUJIN_FLUX_FUNCTION ? flux_n_instructions : 0;
+    last_step2_interpreted = interpreted ? 1 : 0;
     sweep([&](const DeviceMesh &mm, dim3 grid) {
-      hipLaunchKernelGGL(k_dij_alpha_sc<DIM>, grid, block, 0, launch_stream, eparams, mm, old.U.ptr,
-                         old.prec.ptr, d_dij.ptr, d_alpha.ptr);
+      if (interpreted)
+        hipLaunchKernelGGL(k_dij_alpha_sc_function<DIM>, grid, block, 0, launch_stream, eparams, mm,
+                           d_flux_function.ptr, old.U.ptr, old.prec.ptr, d_dij.ptr, d_alpha.ptr);
+      else
+        hipLaunchKernelGGL(k_dij_alpha_sc<DIM>, grid, block, 0, launch_stream, eparams, mm, old.U.ptr,
+                           old.prec.ptr, d_dij.ptr, d_alpha.ptr);
     });
     mark(8);
     exchange_vector(d_alpha.ptr, 1, true);
@@ -1608,10 +1646,16 @@ void ryujin_hip_ctx::step3_diagonal_tau(const StepPlan &plan, const State &old)
     if constexpr (is_aeos_v<E>)
       hipLaunchKernelGGL(k_dij_boundary_aeos<DIM>, dim3(grid_for(n_pairs)), block, 0, stream, eparams,
                          n_pairs, d_p_i.ptr, d_p_j.ptr, d_p_pos.ptr, d_p_cji.ptr, old.rrec.ptr, d_dij.ptr);
-    else if constexpr (is_scalar_v<E>)
-      hipLaunchKernelGGL(k_dij_boundary_sc<DIM>, dim3(grid_for(n_pairs)), block, 0, stream, eparams,
-                         n_pairs, d_p_i.ptr, d_p_j.ptr, d_p_pos.ptr, d_p_cji.ptr, old.U.ptr,
-                         old.prec.ptr, d_dij.ptr);
+    else if constexpr (is_scalar_v<E>) {
+      if (flux_interpreted_pairs())
+        hipLaunchKernelGGL(k_dij_boundary_sc_function<DIM>, dim3(grid_for(n_pairs, kFluxFunctionBlock)),
+                           dim3(kFluxFunctionBlock), 0, stream, eparams, d_flux_function.ptr, n_pairs, d_p_i.ptr,
+                           d_p_j.ptr, d_p_pos.ptr, d_p_cji.ptr, old.U.ptr, old.prec.ptr, d_dij.ptr);
+      else
+        hipLaunchKernelGGL(k_dij_boundary_sc<DIM>, dim3(grid_for(n_pairs)), block, 0, stream, eparams,
+                           n_pairs, d_p_i.ptr, d_p_j.ptr, d_p_pos.ptr, d_p_cji.ptr, old.U.ptr,
+                           old.prec.ptr, d_dij.ptr);
+    }
     else
       hipLaunchKernelGGL(k_dij_boundary<E>, dim3(grid_for(n_pairs)), block, 0, stream, eparams,
                          n_pairs, d_p_i.ptr, d_p_j.ptr, d_p_pos.ptr, d_p_cji.ptr, old.U.ptr, d_dij.ptr);
@@ -4158,6 +4202,69 @@ int ryujin_hip_expression_evaluate(const char *expression, int dim, const double
     if (const int status = expr_compile(expression, dim, *program, error))
       throw HipError(status, error);
     expr_evaluate_points(*program, dim, points, n, t, out);
+    return RYUJIN_OK;
+  });
+}
+
+/* ---- FluxLibrary "function" of the scalar conservation equation ---- */
+
+int ryujin_hip_flux_configure_function(ryujin_hip_ctx *ctx, const char *expression,
+                                       double derivative_approximation_delta)
+{
+  return guarded_ctx(ctx, [&]() {
+    if (ctx->params.equation != RYUJIN_EQ_SCALAR_CONSERVATION)
+      throw HipError(RYUJIN_ERR_UNSUPPORTED, "flux: only the scalar conservation equation takes a flux");
+    /* everything that can be refused comes first: a refused call leaves the earlier flux in place */
+    if (!expression)
+      throw HipError(RYUJIN_ERR_ARG, "flux: null expression");
+    if (!(derivative_approximation_delta > 0.) || !std::isfinite(derivative_approximation_delta))
+      throw HipError(RYUJIN_ERR_ARG, "flux: derivative approximation delta must be positive and finite");
+    auto program = std::make_unique<FluxProgram>();
+    std::string error;
+    if (const int status = flux_compile(expression, ctx->dim, *program, error))
+      throw HipError(status, error);
+    ctx->finish(); /* nothing enqueued may still read the earlier programs */
+    ctx->d_flux_function.upload(program.get(), 1);
+    ctx->flux_n_instructions = program->n_instructions;
+    ctx->scparams.flux = RYUJIN_FLUX_FUNCTION;
+    ctx->scparams.delta = derivative_approximation_delta;
+    for (auto &s : ctx->states) /* (scalar conservation leaves no precomputed values behind a step; all the same) */
+      if (s)
+        s->precomputed = false;
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_flux_function_evaluate(const char *expression, int dim, double delta, const double *u, size_t n,
+                                      double *value, double *gradient)
+{
+  return guarded([&]() {
+    if (!expression || (n > 0 && (!u || !value)))
+      throw HipError(RYUJIN_ERR_ARG, "flux_function_evaluate: null argument");
+    if (!(delta > 0.) || !std::isfinite(delta))
+      throw HipError(RYUJIN_ERR_ARG, "flux_function_evaluate: delta must be positive and finite");
+    auto program = std::make_unique<FluxProgram>();
+    std::string error;
+    if (const int status = flux_compile(expression, dim, *program, error))
+      throw HipError(status, error);
+    flux_evaluate_points(*program, dim, delta, u, n, value, gradient);
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_flux_info(ryujin_hip_ctx *ctx, int *kind, int *n_instructions, int *step2_interpreted)
+{
+  return guarded_ctx(ctx, [&]() {
+    if (ctx->params.equation != RYUJIN_EQ_SCALAR_CONSERVATION)
+      throw HipError(RYUJIN_ERR_UNSUPPORTED, "flux: only the scalar conservation equation takes a flux");
+    const bool ran = ctx->last_flux_kind >= 0;
+    if (kind)
+      *kind = ran ? ctx->last_flux_kind : ctx->scparams.flux;
+    if (n_instructions)
+      *n_instructions = ran ? ctx->last_flux_n_instructions
+                            : (ctx->scparams.flux == RYUJIN_FLUX_FUNCTION ? ctx->flux_n_instructions : 0);
+    if (step2_interpreted)
+      *step2_interpreted = ran ? ctx->last_step2_interpreted : 0;
     return RYUJIN_OK;
   });
 }

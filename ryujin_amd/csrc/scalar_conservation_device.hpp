@@ -1,8 +1,10 @@
 // Device-side scalar conservation Description and the sweeps that differ for it.
 //
 // Restates (operation order preserved):
-//   FluxLibrary           source/scalar_conservation/flux_{burgers,kpp,function}.h ("function" restricted
-//                         to polynomials, central-difference gradient as dealii::FunctionParser)
+//   FluxLibrary           source/scalar_conservation/flux_{burgers,kpp,function}.h ("function": its polynomial
+//                         subset in closed form, and any expression of the grammar table of ryujin_hip.h through
+//                         the interpreter of expression.hpp -- the *_function kernels at the end of this file;
+//                         central-difference gradient as dealii::FunctionParser in both)
 //   HyperbolicSystemView  source/scalar_conservation/hyperbolic_system.h:264-480
 //   RiemannSolver         source/scalar_conservation/riemann_solver.template.h:21-175 (random entropies = 0)
 //   Indicator             source/scalar_conservation/indicator.h:160-205
@@ -11,6 +13,7 @@
 
 #pragma once
 
+#include "expression.hpp"
 #include "kernels_euler.hpp"
 #include "ryujin_hip.h"
 
@@ -86,10 +89,12 @@ namespace ryujin_hip
       return u >= k ? 1. : -1.;
     }
 
-    /* RiemannSolver::compute */
-    static RYUJIN_DEV double lambda_max(const Params &P, const double u_i, const double u_j,
-                                        const double (&prec_i)[NPREC], const double (&prec_j)[NPREC],
-                                        const double (&n)[DIM])
+    /* RiemannSolver::compute. GIVEN: f(k)[DIM] at k = (u_i + u_j) / 2 was evaluated by the caller (the function
+     * flux: the interpreter runs where the wave is not divergent) and replaces flux_value(P, k, d) */
+    template <bool GIVEN>
+    static RYUJIN_DEV double lambda_max_impl(const Params &P, const double u_i, const double u_j,
+                                             const double (&prec_i)[NPREC], const double (&prec_j)[NPREC],
+                                             const double (&n)[DIM], const double *f_k_given)
     {
       double f_i = prec_i[0] * n[0], f_j = prec_j[0] * n[0];
       double df_i = prec_i[DIM] * n[0], df_j = prec_j[DIM] * n[0];
@@ -110,10 +115,18 @@ namespace ryujin_hip
       }
       if (P.use_averaged_entropy) {
         const double k = 0.5 * (u_i + u_j);
-        double f_k = flux_value(P, k, 0) * n[0];
+        double f_k;
+        if constexpr (GIVEN) {
+          f_k = f_k_given[0] * n[0];
 #pragma unroll
-        for (int d = 1; d < DIM; ++d)
-          f_k += flux_value(P, k, d) * n[d];
+          for (int d = 1; d < DIM; ++d)
+            f_k += f_k_given[d] * n[d];
+        } else {
+          f_k = flux_value(P, k, 0) * n[0];
+#pragma unroll
+          for (int d = 1; d < DIM; ++d)
+            f_k += flux_value(P, k, d) * n[d];
+        }
         const double eta_i = fabs(k - u_i);
         const double q_i = kruzkov_entropy_derivative(k, u_i) * (f_i - f_k);
         const double eta_j = fabs(k - u_j);
@@ -130,21 +143,52 @@ namespace ryujin_hip
       return lambda;
     }
 
-    static RYUJIN_DEV double dij_from_states(const Params &P, const double u_i, const double (&prec_i)[NPREC],
-                                             const double u_j, const double (&prec_j)[NPREC],
-                                             const double (&c)[DIM])
+    static RYUJIN_DEV double lambda_max(const Params &P, const double u_i, const double u_j,
+                                        const double (&prec_i)[NPREC], const double (&prec_j)[NPREC],
+                                        const double (&n)[DIM])
+    {
+      return lambda_max_impl<false>(P, u_i, u_j, prec_i, prec_j, n, nullptr);
+    }
+
+    static RYUJIN_DEV double lambda_max(const Params &P, const double u_i, const double u_j,
+                                        const double (&prec_i)[NPREC], const double (&prec_j)[NPREC],
+                                        const double (&n)[DIM], const double (&f_k)[DIM])
+    {
+      return lambda_max_impl<true>(P, u_i, u_j, prec_i, prec_j, n, f_k);
+    }
+
+    /* |c| and n = c / |c| */
+    static RYUJIN_DEV double normalise(const double (&c)[DIM], double (&n)[DIM])
     {
       double norm2 = c[0] * c[0];
 #pragma unroll
       for (int d = 1; d < DIM; ++d)
         norm2 += c[d] * c[d];
       const double norm = sqrt(norm2);
-      double n[DIM];
       const double inverse_norm = 1. / norm; /* dealii::Tensor / scalar multiplies by the inverse */
 #pragma unroll
       for (int d = 0; d < DIM; ++d)
         n[d] = c[d] * inverse_norm;
+      return norm;
+    }
+
+    static RYUJIN_DEV double dij_from_states(const Params &P, const double u_i, const double (&prec_i)[NPREC],
+                                             const double u_j, const double (&prec_j)[NPREC],
+                                             const double (&c)[DIM])
+    {
+      double n[DIM];
+      const double norm = normalise(c, n);
       return norm * lambda_max(P, u_i, u_j, prec_i, prec_j, n);
+    }
+
+    /* ... with f((u_i + u_j) / 2)[DIM] from the caller */
+    static RYUJIN_DEV double dij_from_states(const Params &P, const double u_i, const double (&prec_i)[NPREC],
+                                             const double u_j, const double (&prec_j)[NPREC],
+                                             const double (&c)[DIM], const double (&f_k)[DIM])
+    {
+      double n[DIM];
+      const double norm = normalise(c, n);
+      return norm * lambda_max(P, u_i, u_j, prec_i, prec_j, n, f_k);
     }
 
     /* Limiter::limit: a clip, always decided by the "fast" part */
@@ -440,5 +484,177 @@ namespace ryujin_hip
     const size_t stride = M.bounds_stride;
     bounds[i] = u_min_r;
     bounds[stride + i] = u_max_r;
+  }
+  /* ================================================================== FluxLibrary "function": the interpreter */
+  /* The flux is an expression in u per direction (expression.hpp: flux_compile), evaluated by the interpreter the
+   * function initial state uses: the programs through a const __restrict__ argument at wave-uniform indices (scalar
+   * loads), the operand stack a [slot][lane] column of LDS -- RYUJIN_EXPR_MAX_STACK operands, then the DIM values the
+   * programs leave. Kernels of their own: the kernels above keep their registers and take no LDS. EVERY lane of a wave
+   * runs the interpreter, a lane without work on a finite argument, and stores nothing: the interpreter's loop and its
+   * branches on the opcode stay wave-uniform.
+   * Without sc_use_averaged_entropy the flux enters the update through the precomputed values alone: only
+   * k_precompute_sc_function runs, steps 2 and 3 are the kernels above. */
+
+  constexpr int kFluxFunctionBlock = 64; /* the per-node and per-pair kernels: one wave per block */
+
+  constexpr int flux_function_lds_doubles(const int dim, const int block)
+  {
+    return (RYUJIN_EXPR_MAX_STACK + dim) * block;
+  }
+
+  template <int BLOCK>
+  struct FluxLdsStack {
+    double *column; /* &lds[thread] */
+    RYUJIN_DEV double load(const int slot) const { return column[slot * BLOCK]; }
+    RYUJIN_DEV void store(const int slot, const double value) { column[slot * BLOCK] = value; }
+  };
+
+  struct FluxDevicePow {
+    RYUJIN_DEV double operator()(const double a, const double b) const { return dev_pow(a, b); }
+  };
+
+  /* f(u)[DIM] */
+  template <int DIM, int BLOCK>
+  RYUJIN_DEV void flux_function_value(const FluxProgram *__restrict__ F, const double u, double *column,
+                                      double (&f)[DIM])
+  {
+    FluxLdsStack<BLOCK> stack{column};
+    expr_evaluate(F->code, F->n, u, 0., 0., 0., stack, FluxDevicePow{});
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      f[d] = stack.load(RYUJIN_EXPR_MAX_STACK + d);
+  }
+
+  /* step 1: f(u) and (f(u + delta) - f(u - delta)) / (2 * delta) per node; one wave per slice */
+  template <int DIM, bool WITH_BC>
+  __global__ void __launch_bounds__(kFluxFunctionBlock)
+  k_precompute_sc_function(const ScalarParams P, const DeviceMesh M, const BcFold B,
+                           const FluxProgram *__restrict__ F, double *U, double *__restrict__ prec)
+  {
+    using E = ScalarConservation<DIM>;
+    __shared__ double lds[flux_function_lds_doubles(DIM, kFluxFunctionBlock)];
+    const uint32_t i = (M.slice_begin + blockIdx.x) * 64 + threadIdx.x;
+    bool active = i < M.n_owned && i < M.slice_end * 64;
+    if (active) {
+      if constexpr (WITH_BC)
+        apply_bc_row<E>(P, B, i, U);
+      active = M.row_len[i] != 1;
+    }
+    const double u = active ? U[(size_t)i * 2] : 0.;
+    double f[DIM], f_plus[DIM], f_minus[DIM];
+    flux_function_value<DIM, kFluxFunctionBlock>(F, u, lds + threadIdx.x, f);
+    flux_function_value<DIM, kFluxFunctionBlock>(F, u + P.delta, lds + threadIdx.x, f_plus);
+    flux_function_value<DIM, kFluxFunctionBlock>(F, u - P.delta, lds + threadIdx.x, f_minus);
+    if (!active)
+      return;
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) {
+      prec[(size_t)i * E::NPREC + d] = f[d];
+      prec[(size_t)i * E::NPREC + DIM + d] = (f_plus[d] - f_minus[d]) / (2 * P.delta);
+    }
+  }
+
+  /* step 2 with sc_use_averaged_entropy: k_dij_alpha_sc with f((u_i + u_j) / 2) of every column evaluated by all
+   * lanes in front of the divergent part */
+  template <int DIM>
+  __global__ void __launch_bounds__(kBlock)
+  k_dij_alpha_sc_function(const ScalarParams P, const DeviceMesh M, const FluxProgram *__restrict__ F,
+                          const double *__restrict__ U, const double *__restrict__ prec, double *__restrict__ dij,
+                          double *__restrict__ alpha)
+  {
+    using E = ScalarConservation<DIM>;
+    constexpr int NP = E::NPREC;
+    __shared__ double lds[flux_function_lds_doubles(DIM, kBlock)];
+    step_begin(M);
+    const RowCtx r = row_context(M);
+    if (!r.valid) /* wave-uniform */
+      return;
+    const bool row_active = r.len > 1;
+    const uint32_t i = row_active ? r.row : (r.row < M.n_owned ? r.row : M.n_owned - 1);
+    const double u_i = U[(size_t)i * 2];
+    double prec_i[NP];
+    E::load_prec(prec, i, prec_i);
+    double f_i[DIM];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      f_i[d] = prec_i[d];
+    /* Indicator::reset */
+    double u_abs_max = fabs(u_i), left = 0., right = 0.;
+    for (uint32_t c = 0; c < r.width; ++c) {
+      const uint64_t colbase = (uint64_t)r.base + c;
+      const uint64_t pos = colbase * 64 + r.lane;
+      const uint32_t j = ld_stream(M.cols + pos);
+      double c_ij[DIM], prec_j[NP];
+      load_entry<DIM>(M.cij, colbase, r.lane, c_ij);
+      const double u_j = U[(size_t)j * 2];
+      E::load_prec(prec, j, prec_j);
+      const bool entry = row_active && c < r.len;
+      /* k of RiemannSolver::compute; a lane without an entry passes u_i */
+      const double k = entry ? 0.5 * (u_i + u_j) : u_i;
+      double f_k[DIM];
+      flux_function_value<DIM, kBlock>(F, k, lds + threadIdx.x, f_k);
+      if (!entry)
+        continue;
+      /* Indicator::accumulate */
+      u_abs_max = fmax(u_abs_max, fabs(u_j));
+      const double d_eta_j = E::kruzkov_entropy_derivative(u_i, u_j);
+      double f_j[DIM];
+#pragma unroll
+      for (int d = 0; d < DIM; ++d)
+        f_j[d] = prec_j[d];
+      left += d_eta_j * E::dot(f_j, c_ij);
+      right += d_eta_j * E::dot(f_i, c_ij);
+      if (c > 0 && j > i)
+        dij[pos] = E::dij_from_states(P, u_i, prec_i, u_j, prec_j, c_ij, f_k);
+    }
+    if (row_active) {
+      const double hd_i = M.mi[i] * M.measure_of_omega_inverse;
+      const double numerator = left - right;
+      const double denominator = fabs(left) + fabs(right);
+      const double regularization = 100. * DBL_MIN;
+      const double quotient =
+          fabs(numerator) / (denominator + fmax(hd_i * fabs(u_abs_max), regularization));
+      alpha[i] = fmin(1., P.evc_factor * quotient);
+    }
+  }
+
+  /* step 3, boundary pairs, with sc_use_averaged_entropy: the early returns of k_dij_boundary_sc as one predicate */
+  template <int DIM>
+  __global__ void __launch_bounds__(kFluxFunctionBlock)
+  k_dij_boundary_sc_function(const ScalarParams P, const FluxProgram *__restrict__ F, const uint32_t n_pairs,
+                             const uint32_t *__restrict__ p_i, const uint32_t *__restrict__ p_j,
+                             const uint32_t *__restrict__ p_pos, const double *__restrict__ cji,
+                             const double *__restrict__ U, const double *__restrict__ prec,
+                             double *__restrict__ dij)
+  {
+    using E = ScalarConservation<DIM>;
+    __shared__ double lds[flux_function_lds_doubles(DIM, kFluxFunctionBlock)];
+    const uint32_t q = blockIdx.x * (uint32_t)kFluxFunctionBlock + threadIdx.x;
+    bool active = q < n_pairs;
+    uint32_t i = 0, j = 0;
+    if (active) {
+      i = p_i[q];
+      j = p_j[q];
+      active = !(j < i);
+    }
+    double u_i = 0., u_j = 0.;
+    if (active) {
+      u_i = U[(size_t)i * 2];
+      u_j = U[(size_t)j * 2];
+    }
+    /* d_ji: the pair is seen from j, k = (u_j + u_i) / 2 as RiemannSolver::compute forms it */
+    double f_k[DIM];
+    flux_function_value<DIM, kFluxFunctionBlock>(F, 0.5 * (u_j + u_i), lds + threadIdx.x, f_k);
+    if (!active)
+      return;
+    double prec_i[E::NPREC], prec_j[E::NPREC], c_ji[DIM];
+    E::load_prec(prec, i, prec_i);
+    E::load_prec(prec, j, prec_j);
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      c_ji[d] = cji[(size_t)q * DIM + d];
+    const double d_ji = E::dij_from_states(P, u_j, prec_j, u_i, prec_i, c_ji, f_k);
+    const uint32_t pos = p_pos[q];
+    dij[pos] = fmax(dij[pos], d_ji);
   }
 } // namespace ryujin_hip

@@ -304,6 +304,22 @@ class HyperbolicModule:
         """InitialValues::interpolate_hyperbolic_vector(t) into `state`, ghost rows included (an enqueue)"""
         self._check(self._f("initial_values_interpolate")(self._ctx, state.handle, float(t)))
 
+    # ------------------------------------------------------------------ FluxLibrary "function" (device backend only)
+    def flux_configure_function(self, expression: str, delta: float = 1e-10) -> None:
+        """Switch a scalar conservation module to the expression-defined flux "function"
+        (ryujin_hip_flux_configure_function): one string in u, a component per space dimension separated by ';'
+        ("sin(u); cos(u)"), and the step of the central difference quotient. The grammar is tabulated in
+        include/ryujin_hip.h. Takes effect at the next prepare_state_vector; a refused call (RuntimeError) leaves the
+        earlier flux in place."""
+        self._check(self._f("flux_configure_function")(self._ctx, str(expression).encode(), float(delta)))
+
+    def flux_info(self) -> dict:
+        """What the latest update ran (ryujin_hip_flux_info): kind (capi.FLUX_*), n_instructions of the function
+        flux, step2_interpreted -- whether step 2 ran the interpreter kernel (function flux with averaged entropy)."""
+        kind, n, interpreted = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self._f("flux_info")(self._ctx, C.byref(kind), C.byref(n), C.byref(interpreted)))
+        return dict(kind=kind.value, n_instructions=n.value, step2_interpreted=interpreted.value)
+
     def integrals(self, state: StateVector) -> np.ndarray:
         """sum_i m_i U_i over the owned DoFs of all ranks, computed on the device with a fixed
         summation order (ryujin_hip_state_integrals; device backend only)."""
