@@ -203,6 +203,14 @@ typedef struct ryujin_hip_params {
    * 0: chosen by the library; < 0: off. Results are identical: every slice is processed by
    * exactly one wave either way (ryujin_amd/csrc/kernels_euler.hpp, row_context()). */
   int debug_xcd_chunk;
+  /* Stencil classes: on a uniform structured patch the 64 rows of a SELL-64 slice hold, column by column, the same
+   * c_ij, the same m_ij and the same column offset j - i. create() finds those slices by exact bit comparison and
+   * keeps one table entry per class of slices and column (ryujin_amd/csrc/host_layout.hpp); the 1-D / 2-D sweeps
+   * that gain from it (steps 2 and 4) take c_ij and the column offset of such a slice from the table with scalar loads
+   * instead of streaming 64 copies of them (m_ij is part of the key but read by no kernel). 0: on where it pays (default); < 0: off -- no table is built and
+   * every sweep streams the explicit arrays, as for an unstructured mesh. Results are identical: the same bits reach
+   * the same operations. */
+  int debug_stencil_classes;
 } ryujin_hip_params;
 
 /* ---- offline data (input contract) ------------------------------------- */
@@ -473,6 +481,13 @@ int ryujin_hip_layout_info(ryujin_hip_ctx *ctx, unsigned long long *n_tiles, uns
  * Diagnostics; any pointer may be NULL. */
 int ryujin_hip_chain_info(ryujin_hip_ctx *ctx, unsigned long long *n_chained_tiles,
                           unsigned long long *n_chained_entries);
+/* Stencil classes (ryujin_hip_params::debug_stencil_classes; ryujin_amd/csrc/host_layout.hpp): the number of 64-row
+ * slices whose c_ij and column offsets steps 2 and 4 take from the class table, the number of classes in it, and
+ * the fraction of the matrix entries of the owned rows (padding included) that lie in such slices. All 0 where there
+ * is no table: no uniform slice on the mesh (an unstructured mesh; a partition whose numbering starts with its export
+ * rows may have none either), 3-D, debug_stencil_classes < 0. Diagnostics; any pointer may be NULL. */
+int ryujin_hip_stencil_class_info(ryujin_hip_ctx *ctx, unsigned long long *n_uniform_slices,
+                                  unsigned long long *n_classes, double *uniform_entry_fraction);
 /* Where the latest step stored P_ij per tile (pij_stored == 3): of the (slice, column) tiles between the two latest
  * host synchronisations, the fractions step 5 stored, step 6 read, and step 6 had to form itself because step 5 had
  * not stored them (ryujin_amd/csrc/kernels_limiter_stage0.hpp). 1 / 1 / 0 otherwise. Any pointer may be NULL. */

@@ -20,7 +20,9 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <exception>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -136,7 +138,28 @@ namespace ryujin_hip
   constexpr int kChainMinLanes = 32;
   constexpr uint32_t kChainKindMask = 3, kChainEndLaneOnly = 4; /* bit 2 of `chain`: chain_loads is just the lane at the end of the wave */
 
+  /* STENCIL CLASSES. On a uniform structured patch every row of a 64-row slice has, column by column, bit-identical
+   * c_ij and m_ij and the same column offset j - i: the 64 x (8 DIM + 8 + 4) bytes per column the sweeps stream for
+   * such a slice are 64 copies of one entry. A slice is UNIFORM if all its 64 rows are owned rows as long as the slice
+   * is wide (no padding entries) and, for every column, the bit patterns of the DIM doubles of c_ij and of m_ij and
+   * the offset cols - row agree across the lanes (bit patterns: -0. / 0. and NaN payloads do not merge). The keys
+   * (width; per column the bits and the offset) are deduplicated into a class table with one entry per class and
+   * column, and the slice carries where its class starts in it: the bench mesh (2.5 M gridpoints, 39 044 slices) has
+   * six classes that cover 97.4 % of its slices. The decision is per whole slice, never per column; a slice that is
+   * not uniform, or whose class would be one beyond kStencilClassesMax, carries kStencilClassNone and the sweeps
+   * read the explicit arrays for it, which always exist.
+   * Entry (what the kernels read with wave-uniform scalar loads; 2 + DIM_PADDED 64-bit words, 32 bytes up to two
+   * dimensions): c_ij[0], c_ij[1] (0 in 1-D), [c_ij[2], 3-D only], m_ij, delta (low word; the high word is 0). */
+  constexpr uint32_t kStencilClassNone = 0xffffffffu;
+  constexpr uint32_t kStencilClassesMax = 32;
+  inline uint32_t stencil_class_entry_words(const int dim) { return dim <= 2 ? 4u : 6u; }
+
   struct SellLayout {
+    /* stencil classes (build_stencil_classes()); all empty / zero where no slice is uniform */
+    std::vector<uint32_t> slice_class; /* [n_slices] first entry of the slice's class in class_table, or kStencilClassNone */
+    std::vector<uint64_t> class_table; /* [n_class_entries * stencil_class_entry_words(dim)] */
+    std::vector<uint32_t> class_first; /* [n_classes + 1] first entry of every class (its width: the difference) */
+    uint64_t n_uniform_slices = 0, n_uniform_tiles = 0; /* ... and the 64-entry columns they hold */
     std::vector<TileDesc> tiles;     /* [slice_off[n_slices]] */
     std::vector<uint64_t> chain_loads; /* [slice_off[n_slices]] the lanes of a chained tile that fetch their node themselves */
     uint64_t n_regular_tiles = 0;
@@ -424,6 +447,83 @@ namespace ryujin_hip
       for (const uint64_t n : end_lane)
         n_end_lane_tiles += n;
     }
+
+    /* stencil classes (see kStencilClassNone): call after build(), with the offline data build() was given */
+    void build_stencil_classes(const ryujin_hip_offline &o, const int dim)
+    {
+      const RefView ref(o);
+      const uint32_t W = stencil_class_entry_words(dim);
+      const uint32_t word_m = dim <= 2 ? 2u : 3u, word_delta = word_m + 1u;
+      slice_class.clear();
+      class_table.clear();
+      class_first.clear();
+      n_uniform_slices = n_uniform_tiles = 0;
+      auto bits = [](const double x) {
+        uint64_t b;
+        std::memcpy(&b, &x, sizeof b);
+        return b;
+      };
+      /* the key of every uniform slice: its class entries, column by column (empty: not uniform) */
+      std::vector<std::vector<uint64_t>> keys(n_slices);
+      parallel_chunks(n_slices, [&](const uint64_t s0, const uint64_t s1) {
+        std::vector<uint64_t> key;
+        for (uint32_t s = (uint32_t)s0; s < (uint32_t)s1; ++s) {
+          if ((uint64_t)(s + 1) * kWave > n_owned)
+            continue; /* a slice with padding rows */
+          const uint32_t width = slice_off[s + 1] - slice_off[s];
+          const uint32_t row0 = s * kWave;
+          bool ok = width > 0;
+          for (uint32_t l = 0; l < kWave && ok; ++l)
+            ok = row_len[(size_t)row0 + l] == width; /* no padding entries */
+          key.assign((size_t)width * W, 0);
+          for (uint32_t c = 0; c < width && ok; ++c) {
+            uint64_t *e = key.data() + (size_t)c * W;
+            const uint64_t p0 = ((uint64_t)slice_off[s] + c) * kWave;
+            const int64_t delta = (int64_t)cols[p0] - (int64_t)row0;
+            if (delta <= (int64_t)INT32_MIN || delta > (int64_t)INT32_MAX) {
+              ok = false;
+              break;
+            }
+            for (int d = 0; d < dim; ++d)
+              e[d] = bits(o.cij[ref.data_pos(row0, c, (uint32_t)dim, (uint32_t)d)]);
+            e[word_m] = bits(o.mij[ref.data_pos(row0, c, 1, 0)]);
+            e[word_delta] = (uint64_t)(uint32_t)(int32_t)delta;
+            for (uint32_t l = 1; l < kWave && ok; ++l) {
+              ok = (int64_t)cols[p0 + l] - (int64_t)(row0 + l) == delta &&
+                   bits(o.mij[ref.data_pos(row0 + l, c, 1, 0)]) == e[word_m];
+              for (int d = 0; d < dim && ok; ++d)
+                ok = bits(o.cij[ref.data_pos(row0 + l, c, (uint32_t)dim, (uint32_t)d)]) == e[d];
+            }
+          }
+          if (ok)
+            keys[s] = key;
+        }
+      });
+      /* classes in the order in which the slices meet them */
+      std::map<std::vector<uint64_t>, uint32_t> first_entry;
+      std::vector<uint32_t> of_slice(n_slices, kStencilClassNone);
+      for (uint32_t s = 0; s < n_slices; ++s) {
+        if (keys[s].empty())
+          continue;
+        auto it = first_entry.find(keys[s]);
+        if (it == first_entry.end()) {
+          if (first_entry.size() >= kStencilClassesMax)
+            continue; /* beyond the cap: the explicit arrays */
+          if (class_first.empty())
+            class_first.push_back(0u);
+          it = first_entry.emplace(keys[s], class_first.back()).first;
+          class_table.insert(class_table.end(), keys[s].begin(), keys[s].end());
+          class_first.push_back((uint32_t)(class_table.size() / W));
+        }
+        of_slice[s] = it->second;
+        ++n_uniform_slices;
+        n_uniform_tiles += slice_off[s + 1] - slice_off[s];
+      }
+      if (n_uniform_slices != 0)
+        slice_class = std::move(of_slice);
+    }
+
+    uint32_t n_stencil_classes() const { return class_first.empty() ? 0u : (uint32_t)class_first.size() - 1u; }
 
     /* reference layout -> device layout (padding = 0) */
     std::vector<double> scatter(const ryujin_hip_offline &o, const double *data, uint32_t n_comp) const

@@ -35,6 +35,16 @@ namespace ryujin_hip
 {
   struct DeviceScalars;
 
+  /* an entry of the stencil class table as the 1-D / 2-D sweeps read it (host_layout.hpp, stencil classes: four 64-bit
+   * words): c_ij, m_ij and j - i of one column of every slice of the class */
+  struct StencilClassEntry {
+    double c[2];
+    double m;
+    int32_t delta;
+    uint32_t pad;
+  };
+  static_assert(sizeof(StencilClassEntry) == 32, "four 64-bit words");
+
   /* Start of a step (tau_max := tau_max_in, flags := 0, the restart flag of the previous Runge-Kutta stage
    * folded into its accumulator, the arguments finalize_tau() needs), carried by the first sweep of step 2 and
    * executed by the first thread of its launches: the kernels of step 2 do not touch the scalars, a kernel
@@ -59,6 +69,8 @@ namespace ryujin_hip
     const uint32_t *idx_t;     /* [nnz_total] */
     const TileDesc *tiles;     /* [slice_off[n_slices]] the tile map (host_layout.hpp), or NULL: explicit arrays only */
     const uint64_t *chain_loads; /* [slice_off[n_slices]] with the tile map: the lanes of a chained tile that fetch their node (TileDesc::chain) */
+    const uint32_t *slice_class; /* [n_slices] first entry of the slice's stencil class in class_table or kStencilClassNone; NULL: no uniform slice */
+    const StencilClassEntry *class_table; /* the stencil classes (host_layout.hpp), or NULL */
     uint32_t tail_queue_columns; /* min(63, widest row - 1): columns of the dynamic-LDS queue of undecided pairs (k_pij_lij) */
     /* > 1: the four waves of a block take slices that are band_stride apart (one lattice row / plane of a structured
      * patch) instead of four consecutive ones: row_context() */
@@ -353,6 +365,71 @@ namespace ryujin_hip
       }
     }
     return ld_stream(M.cols + (colbase * 64 + lane));
+  }
+
+  /* ---- STENCIL CLASSES (host_layout.hpp): the 64 rows of a uniform slice hold the same c_ij, m_ij and column offset
+   * in every column, and steps 2 and 4 take c_ij and the offset from the slice's class entry --
+   * through the constant address space with a wave-uniform address, i.e. scalar loads: nothing of them in vmcnt, none
+   * of the 64 x (16 + 4) bytes per column from HBM. (No kernel reads the entry's m_ij: it is part of the key, and kept
+   * in the entry for the retired step-5 variant, DESIGN_HISTORY.md section D.) ONE wave-uniform branch per wave, in front of the
+   * column loop, chooses between two instances of the loop; nothing is decided per column (a conditional vector load
+   * inside a pipelined column loop turns the compiler's counted waits into vmcnt(0), see arrived()). The same bits
+   * into the same operations: the results do not depend on it. Up to two dimensions (the lattice rows of the 3-D
+   * meshes leave few whole uniform slices): the 3-D instantiations compile it out. ---- */
+  template <int DIM>
+  constexpr bool stencil_classes_pay()
+  {
+    return DIM <= 2;
+  }
+  inline bool stencil_classes_pay(const int dim) { return dim <= 2; } /* host: whether create() builds the table at all */
+
+  /* the slice's class (the index of its first entry in the table), or kStencilClassNone */
+  RYUJIN_DEV uint32_t slice_stencil_class(const DeviceMesh &M, const uint32_t slice)
+  {
+    if (M.slice_class == nullptr)
+      return kStencilClassNone;
+    typedef const uint32_t __attribute__((address_space(4))) *const_ptr;
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)*(const_ptr)(uintptr_t)(M.slice_class + slice));
+  }
+
+  RYUJIN_DEV double uniform_double(const int lo, const int hi)
+  {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(hi), __builtin_amdgcn_readfirstlane(lo));
+  }
+
+  /* One wave-uniform branch in front of a column loop that exists twice: loop(std::true_type) for a slice with a stencil
+   * class, loop(std::false_type) for every other; ENABLED = false (3-D, stage vectors, dG) compiles the first out. */
+  template <bool ENABLED, typename Loop>
+  RYUJIN_DEV void dispatch_uniform(const uint32_t cls, Loop &&loop)
+  {
+    if constexpr (ENABLED) {
+      if (cls != kStencilClassNone) /* wave-uniform */
+        loop(std::true_type{});
+      else
+        loop(std::false_type{});
+    } else {
+      loop(std::false_type{});
+    }
+  }
+
+  /* c_ij of entry `e` of the table (e = the slice's class + the column) */
+  template <int DIM>
+  RYUJIN_DEV void class_cij(const DeviceMesh &M, const uint32_t e, double (&c)[DIM])
+  {
+    static_assert(DIM <= 2, "stencil classes up to two dimensions");
+    typedef int v4i __attribute__((ext_vector_type(4)));
+    typedef const v4i __attribute__((address_space(4))) *const_ptr;
+    const v4i v = *(const_ptr)(uintptr_t)(M.class_table + e);
+    c[0] = uniform_double(v.x, v.y);
+    if constexpr (DIM == 2)
+      c[1] = uniform_double(v.z, v.w);
+  }
+
+  /* j - i of entry `e` */
+  RYUJIN_DEV int32_t class_delta(const DeviceMesh &M, const uint32_t e)
+  {
+    typedef const int32_t __attribute__((address_space(4))) *const_ptr;
+    return __builtin_amdgcn_readfirstlane(*(const_ptr)(uintptr_t)(&M.class_table[e].delta));
   }
 
   /* ---- CHAINED GATHERS (TileDesc::chain and chain_loads, host_layout.hpp). On a lattice the node data of the columns
@@ -980,45 +1057,65 @@ namespace ryujin_hip
       typename E::Indicator indicator;
       indicator.reset(P, U_i, prec2[i]);
 
-      uint32_t j_n = ld_stream(cols + ((uint64_t)r.base * 64 + r.lane));
-      uint32_t j_nn = r.width > 1 ? ld_stream(cols + (((uint64_t)r.base + 1) * 64 + r.lane)) : i;
-      double c_n[DIM], U_n[K];
-      load_entry<DIM>(cij, r.base, r.lane, c_n);
-      load_state<K>(U, j_n, U_n);
-      double2 prec_n = prec2[j_n];
-      /* (1-D, 2-D, shallow water: 124 registers and four waves per SIMD. Pinning the waits -- arrived() -- and keeping
-       * the d_ij store back costs 16 registers and the fourth wave here: 0.241 -> 0.247 ms on C2, with the Riemann
-       * record prefetched as well 0.268, profiles/r06l_ab_pinned_waits_c2.log; the loop stays as it was) */
-      for (uint32_t c = 0; c < r.width; ++c) {
-        const uint64_t colbase = (uint64_t)r.base + c;
-        const uint32_t j = j_n;
-        double c_ij[DIM], U_j[K];
+      /* (the column loop exists twice -- stencil classes, above: UNIFORM takes c_ij of column c from the class entry
+       * of the slice, which has no padding; one wave-uniform branch behind the lambda chooses) */
+      constexpr bool kClasses = stencil_classes_pay<DIM>();
+      const uint32_t cls = kClasses ? slice_stencil_class(M, r.slice) : kStencilClassNone;
+      auto column_loop = [&](auto uniform_) __attribute__((always_inline)) {
+        constexpr bool UNIFORM = decltype(uniform_)::value;
+        auto column = [&](const uint64_t colbase) -> uint32_t {
+          if constexpr (UNIFORM) /* j = row + delta: one add, no index load */
+            return (uint32_t)((int32_t)i + class_delta(M, cls + (uint32_t)(colbase - r.base)));
+          else
+            return ld_stream(cols + (colbase * 64 + r.lane));
+        };
+        uint32_t j_n = column(r.base);
+        uint32_t j_nn = r.width > 1 ? column((uint64_t)r.base + 1) : i;
+        double c_n[DIM], U_n[K];
+        if constexpr (UNIFORM)
+          class_cij<DIM>(M, cls, c_n);
+        else
+          load_entry<DIM>(cij, r.base, r.lane, c_n);
+        load_state<K>(U, j_n, U_n);
+        double2 prec_n = prec2[j_n];
+        /* (1-D, 2-D, shallow water: 124 registers and four waves per SIMD. Pinning the waits -- arrived() -- and keeping
+         * the d_ij store back costs 16 registers and the fourth wave here: 0.241 -> 0.247 ms on C2, with the Riemann
+         * record prefetched as well 0.268, profiles/r06l_ab_pinned_waits_c2.log; the loop stays as it was) */
+        for (uint32_t c = 0; c < r.width; ++c) {
+          const uint64_t colbase = (uint64_t)r.base + c;
+          const uint32_t j = j_n;
+          double c_ij[DIM], U_j[K];
 #pragma unroll
-        for (int d = 0; d < DIM; ++d)
-          c_ij[d] = c_n[d];
+          for (int d = 0; d < DIM; ++d)
+            c_ij[d] = c_n[d];
 #pragma unroll
-        for (int q = 0; q < K; ++q)
-          U_j[q] = U_n[q];
-        const double2 prec_j = prec_n;
-        if (c + 1 < r.width) {
-          j_n = j_nn;
-          load_entry<DIM>(cij, colbase + 1, r.lane, c_n);
-          load_state<K>(U, j_n, U_n);
-          prec_n = prec2[j_n];
-          j_nn = (c + 2 < r.width) ? ld_stream(cols + ((colbase + 2) * 64 + r.lane)) : i;
+          for (int q = 0; q < K; ++q)
+            U_j[q] = U_n[q];
+          const double2 prec_j = prec_n;
+          if (c + 1 < r.width) {
+            j_n = j_nn;
+            if constexpr (UNIFORM)
+              class_cij<DIM>(M, cls + c + 1, c_n);
+            else
+              load_entry<DIM>(cij, colbase + 1, r.lane, c_n);
+            load_state<K>(U, j_n, U_n);
+            prec_n = prec2[j_n];
+            j_nn = (c + 2 < r.width) ? column(colbase + 2) : i;
+          }
+          const bool active = UNIFORM ? row_active : (row_active && c < r.len);
+          if (active && (c > 0 || !E::kIndicatorDiagonalIsZero))
+            indicator.accumulate(P, U_j, prec_j, c_ij);
+          /* upper triangle only (:394-408) */
+          const bool mine = active && c > 0 && j > i;
+          if (__any(mine)) {
+            double rec_j[RS];
+            load_record<RS>(rec, j, rec_j);
+            if (mine)
+              dij[colbase * 64 + r.lane] = E::template dij_from_records<GENERAL>(P, rec_i, rec_j, c_ij);
+          }
         }
-        const bool active = row_active && c < r.len;
-        if (active && (c > 0 || !E::kIndicatorDiagonalIsZero))
-          indicator.accumulate(P, U_j, prec_j, c_ij);
-        /* upper triangle only (:394-408) */
-        const bool mine = active && c > 0 && j > i;
-        if (__any(mine)) {
-          double rec_j[RS];
-          load_record<RS>(rec, j, rec_j);
-          if (mine)
-            dij[colbase * 64 + r.lane] = E::template dij_from_records<GENERAL>(P, rec_i, rec_j, c_ij);
-        }
-      }
+      };
+      dispatch_uniform<kClasses>(cls, column_loop);
       if (row_active)
         alpha[i] = indicator.alpha(P, M.mi[i] * M.measure_of_omega_inverse);
     }
@@ -1227,142 +1324,162 @@ namespace ryujin_hip
     double rho_min = DBL_MAX, rho_max = 0., s_min = DBL_MAX;
     double rho_relaxation_numerator = 0., rho_relaxation_denominator = 0., s_interp_max = 0.;
 
-    /* software pipeline (see k_dij_alpha) */
+    /* software pipeline (see k_dij_alpha). The column loop exists twice (stencil classes, above): UNIFORM takes c_ij
+     * of column c from the class entry of the slice -- which has no padding: active == row_active --, the other
+     * streams it; one wave-uniform branch behind the lambda chooses. */
     const uint32_t *__restrict__ cols = M.cols;
     const double *__restrict__ cij = M.cij;
-    uint32_t j_n = ld_stream(cols + ((uint64_t)r.base * 64 + r.lane));
-    uint32_t j_nn = r.width > 1 ? ld_stream(cols + (((uint64_t)r.base + 1) * 64 + r.lane)) : i;
-    double c_n[DIM], U_n[K];
-    load_entry<DIM>(cij, r.base, r.lane, c_n);
-    double d_n = dij[(uint64_t)r.base * 64 + r.lane];
-    load_state<K>(U, j_n, U_n);
-    double alpha_n = alpha[j_n];
-    double s_n = prec[(size_t)j_n * 2 + 0];
+    constexpr bool kClasses = stencil_classes_pay<DIM>() && !HAS_STAGES && !DG;
+    const uint32_t cls = kClasses ? slice_stencil_class(M, r.slice) : kStencilClassNone;
+    auto column_loop = [&](auto uniform_) __attribute__((always_inline)) {
+      constexpr bool UNIFORM = decltype(uniform_)::value;
+      auto column = [&](const uint64_t colbase) -> uint32_t {
+        if constexpr (UNIFORM) /* j = row + delta: one add, no index load */
+          return (uint32_t)((int32_t)i + class_delta(M, cls + (uint32_t)(colbase - r.base)));
+        else
+          return ld_stream(cols + (colbase * 64 + r.lane));
+      };
+      uint32_t j_n = column(r.base);
+      uint32_t j_nn = r.width > 1 ? column((uint64_t)r.base + 1) : i;
+      double c_n[DIM], U_n[K];
+      if constexpr (UNIFORM)
+        class_cij<DIM>(M, cls, c_n);
+      else
+        load_entry<DIM>(cij, r.base, r.lane, c_n);
+      double d_n = dij[(uint64_t)r.base * 64 + r.lane];
+      load_state<K>(U, j_n, U_n);
+      double alpha_n = alpha[j_n];
+      double s_n = prec[(size_t)j_n * 2 + 0];
 
-    for (uint32_t c = 0; c < r.width; ++c) {
-      const uint64_t colbase = (uint64_t)r.base + c;
-      const bool active = row_active && c < r.len;
-      double c_ij[DIM], U_j[K];
-      const uint32_t j = j_n;
+      for (uint32_t c = 0; c < r.width; ++c) {
+        const uint64_t colbase = (uint64_t)r.base + c;
+        const bool active = UNIFORM ? row_active : (row_active && c < r.len);
+        double c_ij[DIM], U_j[K];
+        const uint32_t j = j_n;
 #pragma unroll
-      for (int d = 0; d < DIM; ++d)
-        c_ij[d] = c_n[d];
-#pragma unroll
-      for (int q = 0; q < K; ++q)
-        U_j[q] = U_n[q];
-      const double d_ij = d_n, alpha_j = alpha_n, s_j = s_n;
-      if (c + 1 < r.width) {
-        j_n = j_nn;
-        load_entry<DIM>(cij, colbase + 1, r.lane, c_n);
-        d_n = dij[(colbase + 1) * 64 + r.lane];
-        load_state<K>(U, j_n, U_n);
-        alpha_n = alpha[j_n];
-        s_n = prec[(size_t)j_n * 2 + 0];
-        j_nn = (c + 2 < r.width) ? ld_stream(cols + ((colbase + 2) * 64 + r.lane)) : i;
-      }
-
-      if (!active)
-        continue;
-
-      double factor = (alpha_i + alpha_j) * .5;
-      if constexpr (DG) /* hyperbolic_module.template.h:733-737 */
-        factor = fmax(factor, M.incidence[colbase * 64 + r.lane]);
-      const double d_ijH = d_ij * factor;
-
-      const double regularization = 100. * DBL_MIN;
-      const double denom = fmax(d_ij, regularization);
-      double scaled_c_ij[DIM];
-      const double inverse_denom = 1. / denom; /* dealii::Tensor / scalar multiplies by the inverse */
-#pragma unroll
-      for (int d = 0; d < DIM; ++d)
-        scaled_c_ij[d] = c_ij[d] * inverse_denom;
-
-      double f_j[K][DIM];
-      E::flux(P, U_j, f_j);
-      double flux_ij[K];
-      if constexpr (kParkFlux) {
-        /* flux_divergence() with f_i read from LDS (an opaque lane offset keeps the loop-invariant loads from being
-         * hoisted back into registers) */
-        uint32_t off = r.lane;
-        asm volatile("" : "+v"(off));
-        const double *const f_i_parked = parked + off;
-#pragma unroll
-        for (int q = 0; q < K; ++q) {
-          double s = (f_i_parked[(q * DIM + 0) * 64] + f_j[q][0]) * c_ij[0];
-#pragma unroll
-          for (int d = 1; d < DIM; ++d)
-            s += (f_i_parked[(q * DIM + d) * 64] + f_j[q][d]) * c_ij[d];
-          flux_ij[q] = -s;
-        }
-      } else {
-        E::flux_divergence(f_i, f_j, c_ij, flux_ij);
-      }
-
-      double P_ij[K];
-#pragma unroll
-      for (int q = 0; q < K; ++q) {
-        U_i_new[q] += tau * m_i_inv * flux_ij[q];
-        P_ij[q] = -flux_ij[q];
-      }
-#pragma unroll
-      for (int q = 0; q < K; ++q) {
-        const double dU = U_j[q] - U_i[q];
-        U_i_new[q] += tau * m_i_inv * d_ij * dU;
-        F_iH[q] += d_ijH * dU;
-        P_ij[q] += (d_ijH - d_ij) * dU;
-      }
-
-      /* Limiter::accumulate (limiter.h:279-327) */
-      {
-        const double rho_i = U_i[0], rho_j = U_j[0];
-        double dm_c = (U_i[1] - U_j[1]) * scaled_c_ij[0];
-#pragma unroll
-        for (int d = 1; d < DIM; ++d)
-          dm_c += (U_i[1 + d] - U_j[1 + d]) * scaled_c_ij[d];
-        const double rho_ij_bar = 0.5 * (rho_i + rho_j + dm_c) + 0.;
-        rho_min = fmin(rho_min, rho_ij_bar);
-        rho_max = fmax(rho_max, rho_ij_bar);
-        s_min = fmin(s_min, s_j);
-        rho_relaxation_numerator += 1. * (rho_i + rho_j);
-        rho_relaxation_denominator += 1.;
-        double U_avg[K];
+        for (int d = 0; d < DIM; ++d)
+          c_ij[d] = c_n[d];
 #pragma unroll
         for (int q = 0; q < K; ++q)
-          U_avg[q] = (U_i[q] + U_j[q]) * .5;
-        /* column 0 (j = i, wave-uniform): U_avg = U_i exactly and s(U_i) is the precomputed s_i = s_j (the same
-         * function on the same arguments): one power and one division less per row, the same bits */
-        const double s_interp = c == 0 ? s_j : E::specific_entropy(P, U_avg);
-        s_interp_max = fmax(s_interp_max, s_interp);
-      }
+          U_j[q] = U_n[q];
+        const double d_ij = d_n, alpha_j = alpha_n, s_j = s_n;
+        if (c + 1 < r.width) {
+          j_n = j_nn;
+          if constexpr (UNIFORM)
+            class_cij<DIM>(M, cls + c + 1, c_n);
+          else
+            load_entry<DIM>(cij, colbase + 1, r.lane, c_n);
+          d_n = dij[(colbase + 1) * 64 + r.lane];
+          load_state<K>(U, j_n, U_n);
+          alpha_n = alpha[j_n];
+          s_n = prec[(size_t)j_n * 2 + 0];
+          j_nn = (c + 2 < r.width) ? column(colbase + 2) : i;
+        }
 
+        if (!active)
+          continue;
+
+        double factor = (alpha_i + alpha_j) * .5;
+        if constexpr (DG) /* hyperbolic_module.template.h:733-737 */
+          factor = fmax(factor, M.incidence[colbase * 64 + r.lane]);
+        const double d_ijH = d_ij * factor;
+
+        const double regularization = 100. * DBL_MIN;
+        const double denom = fmax(d_ij, regularization);
+        double scaled_c_ij[DIM];
+        const double inverse_denom = 1. / denom; /* dealii::Tensor / scalar multiplies by the inverse */
 #pragma unroll
-      for (int q = 0; q < K; ++q) {
-        F_iH[q] += weight * flux_ij[q];
-        P_ij[q] += weight * flux_ij[q];
-      }
+        for (int d = 0; d < DIM; ++d)
+          scaled_c_ij[d] = c_ij[d] * inverse_denom;
 
-      if constexpr (HAS_STAGES) {
-        for (int s = 0; s < S.stages; ++s) {
-          double U_iHs[K], U_jHs[K];
-          load_state<K>(S.U[s], i, U_iHs);
-          load_state<K>(S.U[s], j, U_jHs);
-          double f_iHs[K][DIM], f_jHs[K][DIM];
-          E::flux(P, U_iHs, f_iHs);
-          E::flux(P, U_jHs, f_jHs);
-          double flux_s[K];
-          E::flux_divergence(f_iHs, f_jHs, c_ij, flux_s);
-          const double w = S.w[s];
+        double f_j[K][DIM];
+        E::flux(P, U_j, f_j);
+        double flux_ij[K];
+        if constexpr (kParkFlux) {
+          /* flux_divergence() with f_i read from LDS (an opaque lane offset keeps the loop-invariant loads from being
+           * hoisted back into registers) */
+          uint32_t off = r.lane;
+          asm volatile("" : "+v"(off));
+          const double *const f_i_parked = parked + off;
 #pragma unroll
           for (int q = 0; q < K; ++q) {
-            F_iH[q] += w * flux_s[q];
-            P_ij[q] += w * flux_s[q];
+            double s = (f_i_parked[(q * DIM + 0) * 64] + f_j[q][0]) * c_ij[0];
+#pragma unroll
+            for (int d = 1; d < DIM; ++d)
+              s += (f_i_parked[(q * DIM + d) * 64] + f_j[q][d]) * c_ij[d];
+            flux_ij[q] = -s;
+          }
+        } else {
+          E::flux_divergence(f_i, f_j, c_ij, flux_ij);
+        }
+
+        double P_ij[K];
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+          U_i_new[q] += tau * m_i_inv * flux_ij[q];
+          P_ij[q] = -flux_ij[q];
+        }
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+          const double dU = U_j[q] - U_i[q];
+          U_i_new[q] += tau * m_i_inv * d_ij * dU;
+          F_iH[q] += d_ijH * dU;
+          P_ij[q] += (d_ijH - d_ij) * dU;
+        }
+
+        /* Limiter::accumulate (limiter.h:279-327) */
+        {
+          const double rho_i = U_i[0], rho_j = U_j[0];
+          double dm_c = (U_i[1] - U_j[1]) * scaled_c_ij[0];
+#pragma unroll
+          for (int d = 1; d < DIM; ++d)
+            dm_c += (U_i[1 + d] - U_j[1 + d]) * scaled_c_ij[d];
+          const double rho_ij_bar = 0.5 * (rho_i + rho_j + dm_c) + 0.;
+          rho_min = fmin(rho_min, rho_ij_bar);
+          rho_max = fmax(rho_max, rho_ij_bar);
+          s_min = fmin(s_min, s_j);
+          rho_relaxation_numerator += 1. * (rho_i + rho_j);
+          rho_relaxation_denominator += 1.;
+          double U_avg[K];
+#pragma unroll
+          for (int q = 0; q < K; ++q)
+            U_avg[q] = (U_i[q] + U_j[q]) * .5;
+          /* column 0 (j = i, wave-uniform): U_avg = U_i exactly and s(U_i) is the precomputed s_i = s_j (the same
+           * function on the same arguments): one power and one division less per row, the same bits */
+          const double s_interp = c == 0 ? s_j : E::specific_entropy(P, U_avg);
+          s_interp_max = fmax(s_interp_max, s_interp);
+        }
+
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+          F_iH[q] += weight * flux_ij[q];
+          P_ij[q] += weight * flux_ij[q];
+        }
+
+        if constexpr (HAS_STAGES) {
+          for (int s = 0; s < S.stages; ++s) {
+            double U_iHs[K], U_jHs[K];
+            load_state<K>(S.U[s], i, U_iHs);
+            load_state<K>(S.U[s], j, U_jHs);
+            double f_iHs[K][DIM], f_jHs[K][DIM];
+            E::flux(P, U_iHs, f_iHs);
+            E::flux(P, U_jHs, f_jHs);
+            double flux_s[K];
+            E::flux_divergence(f_iHs, f_jHs, c_ij, flux_s);
+            const double w = S.w[s];
+#pragma unroll
+            for (int q = 0; q < K; ++q) {
+              F_iH[q] += w * flux_s[q];
+              P_ij[q] += w * flux_s[q];
+            }
           }
         }
-      }
 
-      if constexpr (STORE_P)
-        store_entry<K>(pij, colbase, r.lane, P_ij);
-    }
+        if constexpr (STORE_P)
+          store_entry<K>(pij, colbase, r.lane, P_ij);
+      }
+    };
+    dispatch_uniform<kClasses>(cls, column_loop);
 
     if (!row_active)
       return;

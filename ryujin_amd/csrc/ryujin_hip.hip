@@ -397,6 +397,9 @@ struct ryujin_hip_ctx {
   DeviceBuffer<uint32_t> d_slice_off, d_cols, d_idx_t, d_lower_mask;
   DeviceBuffer<TileDesc> d_tiles; /* the tile map (host_layout.hpp); empty with debug_tile_map < 0 */
   DeviceBuffer<uint64_t> d_chain_loads; /* ... and the lanes of its chained tiles that fetch their node themselves */
+  /* the stencil classes (host_layout.hpp); empty where no slice is uniform, in 3-D and with debug_stencil_classes < 0 */
+  DeviceBuffer<uint32_t> d_slice_class;
+  DeviceBuffer<uint64_t> d_class_table;
   DeviceBuffer<uint16_t> d_row_len;
   DeviceBuffer<double> d_cij, d_mij, d_mi, d_mi_inv;
   bool dg = false; /* discontinuous ansatz */
@@ -835,6 +838,13 @@ void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params
     d_tiles.upload(L.tiles);
     d_chain_loads.upload(L.chain_loads);
   }
+  if (p.debug_stencil_classes >= 0 && stencil_classes_pay(dim)) {
+    L.build_stencil_classes(o, dim);
+    if (L.n_uniform_slices != 0) {
+      d_slice_class.upload(L.slice_class);
+      d_class_table.upload(L.class_table);
+    }
+  }
   {
     /* bit c of lower_mask[row] <=> column c of the row lies below the diagonal (cols < row) */
     std::vector<uint32_t> lower_mask(L.rows_padded, 0u);
@@ -930,6 +940,8 @@ void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params
   mesh.idx_t = d_idx_t.ptr;
   mesh.tiles = d_tiles.n != 0 ? d_tiles.ptr : nullptr;
   mesh.chain_loads = d_chain_loads.n != 0 ? d_chain_loads.ptr : nullptr;
+  mesh.slice_class = d_slice_class.n != 0 ? d_slice_class.ptr : nullptr;
+  mesh.class_table = d_class_table.n != 0 ? reinterpret_cast<const StencilClassEntry *>(d_class_table.ptr) : nullptr;
   mesh.tail_queue_columns = std::max<uint32_t>(1u, std::min<uint32_t>(63u, L.max_row_len - 1u));
   /* stacked blocks (row_context(), kernels_euler.hpp): debug_band_stride < 0 off, > 0 that many slices, 0 from the
    * mesh, in 2-D: C2 (G = 47) -1.1 % per update, every sweep a little; in 3-D stacking lattice planes (G = 365 on the C4
@@ -2658,6 +2670,7 @@ void ryujin_hip_default_params(ryujin_hip_params *p, int equation, int dim)
   p->debug_tile_map = 0;
   p->debug_band_stride = 0;
   p->debug_xcd_chunk = 0;
+  p->debug_stencil_classes = 0;
   /* the profiling scripts wrap bench.py, which takes the defaults: let them select a mapping without a flag */
   if (const char *e = std::getenv("RYUJIN_XCD_CHUNK"))
     p->debug_xcd_chunk = std::atoi(e);
@@ -3235,6 +3248,24 @@ int ryujin_hip_chain_info(ryujin_hip_ctx *ctx, unsigned long long *n_chained_til
       *n_chained_tiles = ctx->d_tiles.n == 0 ? 0ull : (masks ? ctx->L.n_chained_tiles : ctx->L.n_end_lane_tiles);
     if (n_chained_entries)
       *n_chained_entries = ctx->d_tiles.n == 0 ? 0ull : (masks ? ctx->L.n_chained_entries : 63ull * ctx->L.n_end_lane_tiles);
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_stencil_class_info(ryujin_hip_ctx *ctx, unsigned long long *n_uniform_slices,
+                                  unsigned long long *n_classes, double *uniform_entry_fraction)
+{
+  return guarded([&]() {
+    if (!ctx)
+      throw HipError(RYUJIN_ERR_ARG, "null context");
+    const bool table = ctx->d_slice_class.n != 0;
+    const uint64_t n_tiles = ctx->L.slice_off[ctx->L.n_slices];
+    if (n_uniform_slices)
+      *n_uniform_slices = table ? ctx->L.n_uniform_slices : 0ull;
+    if (n_classes)
+      *n_classes = table ? ctx->L.n_stencil_classes() : 0ull;
+    if (uniform_entry_fraction)
+      *uniform_entry_fraction = table && n_tiles != 0 ? (double)ctx->L.n_uniform_tiles / (double)n_tiles : 0.;
     return RYUJIN_OK;
   });
 }

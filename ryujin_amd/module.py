@@ -582,6 +582,14 @@ class HyperbolicModule:
                     n_chained_tiles=ch.value, chained_tile_fraction=(ch.value / n.value if n.value else 0.0),
                     chained_entry_fraction=(ce.value / (64.0 * n.value) if n.value else 0.0))
 
+    def stencil_class_info(self) -> dict:
+        """uniform slices (64 rows with the same c_ij, m_ij and column offsets, column by column) whose c_ij and
+        column indices steps 2 and 4 take from the class table, the classes in it and the fraction of the matrix entries in such slices; all
+        0 where there is no table (ryujin_hip_stencil_class_info; device backend only)"""
+        n, k, f = C.c_ulonglong(0), C.c_ulonglong(0), C.c_double(0.0)
+        self._check(self._lib.ryujin_hip_stencil_class_info(self._ctx, C.byref(n), C.byref(k), C.byref(f)))
+        return dict(n_uniform_slices=n.value, n_classes=k.value, uniform_entry_fraction=f.value)
+
     PLAN_STEP2 = ("alpha_then_dij", "dij_alpha_sc", "records", "dij_alpha")
     PLAN_STEP5 = ("none", "stage0_per_tile", "stage0_per_slice", "stage0_groups", "recompute", "pij_lij")
     PLAN_STEP6 = ("none", "per_slice", "cached", "high_order")
