@@ -39,6 +39,7 @@
 #endif
 
 #include "host_layout.hpp"
+#include "host_context.hpp"
 #include "step_plan.hpp"
 #include "rank_reduce.hpp"
 #include "kernels_euler.hpp"
@@ -57,15 +58,6 @@ using namespace ryujin_hip;
 namespace
 {
   thread_local std::string g_error;
-
-  struct HipError : std::runtime_error {
-    int status;
-    HipError(int status, const std::string &what)
-        : std::runtime_error(what)
-        , status(status)
-    {
-    }
-  };
 
 #define HIP_CHECK(expr)                                                                        \
   do {                                                                                         \
@@ -345,7 +337,7 @@ struct ryujin_hip_comm {
 
 struct ryujin_hip_ctx {
   ryujin_hip_params params{};
-  int dim = 0, K = 0, KP = 0, NB = 3, NPREC = 2;
+  int dim = 0, K = 0, KP = 0, NB = 3, NPREC = 2, RS = 0; /* system_shape() */
   int device = 0;
   ryujin_hip_comm *comm = nullptr;
   hipStream_t stream = nullptr;      /* compute */
@@ -364,7 +356,6 @@ struct ryujin_hip_ctx {
   uint32_t resident_waves_step5 = kResidentWavesStep5, resident_waves_step6 = kResidentWavesStep6;
   bool interior_reads_ghosts = false; /* asymmetric stencil: every sweep joins the exchanges (no overlap) */
   uint32_t n_export_slices = 0;
-  uint32_t bounds_stride = 0; /* SoA stride of the limiter bounds: covers the ghost range (dG reads bounds_j) */
 
   SellLayout L;
   DeviceMesh mesh{};
@@ -405,24 +396,22 @@ struct ryujin_hip_ctx {
   bool dg = false; /* discontinuous ansatz */
   DeviceBuffer<double> d_incidence, d_minv, d_bounds_combined;
 
-  /* boundary data */
-  uint32_t n_bdry = 0, n_groups = 0;
-  std::vector<uint32_t> bdry_perm; /* sorted entry -> original entry */
+  /* boundary data: the boundary map grouped by DoF (host_context.hpp) and its device copies */
+  BoundaryTables bdry;
   DeviceBuffer<uint32_t> d_grp_start, d_b_i, d_bc_first;
   DeviceBuffer<unsigned long long> d_bc_mask; /* BcFold: boundary rows of every slice */
   DeviceBuffer<double> d_b_normal, d_dirichlet;
   DeviceBuffer<uint8_t> d_b_id;
-  bool have_dirichlet = false, needs_dirichlet = false;
-  /* ryujin_hip_state_download_prepared: the distinct boundary_map rows, packed on the device, scattered on the host */
-  std::vector<uint32_t> h_bc_rows;
+  bool have_dirichlet = false;
+  /* ryujin_hip_state_download_prepared: the distinct boundary_map rows (bdry.rows), packed on the device, scattered on
+   * the host */
   DeviceBuffer<uint32_t> d_bc_rows;
   DeviceBuffer<double> d_bc_pack;
   double *h_bc_pack = nullptr; /* pinned */
   /* ryujin_hip_host_register: caller-owned arrays pinned in place */
   std::vector<const void *> registered_host;
 
-  /* coupling boundary pairs */
-  uint32_t n_pairs = 0;
+  /* coupling boundary pairs (d_p_pos.n of them) */
   DeviceBuffer<uint32_t> d_p_i, d_p_j, d_p_pos;
   DeviceBuffer<double> d_p_cji;
 
@@ -488,7 +477,7 @@ struct ryujin_hip_ctx {
   bool want_tau_early = false;
   double *h_dirichlet_stage[kMaxRkStages] = {}; /* pinned staging, one per RK stage */
   /* InitialValues (ryujin_hip_initial_values_*, kernels_initial_values.hpp): the configured analytic state, the
-   * node positions and the boundary_map positions in the grouped order of d_b_i (bdry_perm applied once) */
+   * node positions and the boundary_map positions in the grouped order of d_b_i (bdry.permute applied once) */
   bool iv_configured = false;
   InitialValuesParams iv{};
   DeviceBuffer<double> d_iv_positions, d_iv_b_positions;
@@ -517,11 +506,8 @@ struct ryujin_hip_ctx {
   };
   std::vector<std::unique_ptr<State>> states;
 
-  /* exchange pattern */
-  int n_nbr = 0;
-  std::vector<int> nbr_rank;
-  std::vector<uint32_t> send_off, recv_off, row_send_off;
-  std::vector<uint64_t> row_recv_off; /* offsets into the ghost CSR region */
+  /* exchange pattern (host_context.hpp) */
+  ExchangeTables exch;
   DeviceBuffer<uint32_t> d_send_idx, d_row_send_pos;
   DeviceBuffer<double> d_send_buf;
 
@@ -725,55 +711,25 @@ struct ryujin_hip_ctx {
   }
 };
 
+/* Check, derive, create, upload: the host tables come from host_context.hpp, one call each; nothing touches the device
+ * before every argument has passed. */
 void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params &p,
                             ryujin_hip_comm *c, int dev)
 {
+  check_create_arguments(o, p, c != nullptr);
   params = p;
   comm = c;
   device = dev;
   dim = p.dim;
-  if (p.equation != RYUJIN_EQ_EULER && p.equation != RYUJIN_EQ_SHALLOW_WATER &&
-      p.equation != RYUJIN_EQ_EULER_AEOS && p.equation != RYUJIN_EQ_SCALAR_CONSERVATION)
-    throw HipError(RYUJIN_ERR_UNSUPPORTED, "unknown equation");
-  if (p.equation == RYUJIN_EQ_SCALAR_CONSERVATION) {
-    if (p.sc_flux < RYUJIN_FLUX_BURGERS || p.sc_flux > RYUJIN_FLUX_FUNCTION)
-      throw HipError(RYUJIN_ERR_UNSUPPORTED, "unknown flux");
-    if (p.sc_flux == RYUJIN_FLUX_KPP && p.dim == 3)
-      throw HipError(RYUJIN_ERR_UNSUPPORTED, "KPP is only defined in (1 or) 2 space dimensions");
-    if (p.sc_random_entropies != 0) /* std::random_device in riemann_solver.template.h:93-107 */
-      throw HipError(RYUJIN_ERR_UNSUPPORTED,
-                     "scalar conservation: random entropies are not reproducible in the reference");
-    for (uint32_t b = 0; b < o.n_bdry; ++b)
-      if (o.b_id[b] == RYUJIN_BC_SLIP || o.b_id[b] == RYUJIN_BC_NO_SLIP || o.b_id[b] == RYUJIN_BC_DYNAMIC)
-        throw HipError(RYUJIN_ERR_UNSUPPORTED, "slip, no-slip and dynamic boundary conditions are "
-                                               "unavailable for scalar conservation equations");
-  }
-  if (p.equation == RYUJIN_EQ_EULER_AEOS) {
-    if (p.eos < RYUJIN_EOS_POLYTROPIC_GAS || p.eos > RYUJIN_EOS_JONES_WILKINS_LEE)
-      throw HipError(RYUJIN_ERR_UNSUPPORTED, "unknown equation of state");
-    for (uint32_t b = 0; b < o.n_bdry; ++b)
-      if (o.b_id[b] == RYUJIN_BC_DYNAMIC) /* __builtin_trap() in euler_aeos/hyperbolic_system.h:1337 */
-        throw HipError(RYUJIN_ERR_UNSUPPORTED,
-                       "euler aeos: dynamic boundary conditions are not implemented in the reference");
-  }
-  if (p.equation == RYUJIN_EQ_SHALLOW_WATER && p.dim == 3)
-    throw HipError(RYUJIN_ERR_UNSUPPORTED, "the shallow water equations are defined for dim 1 and 2");
-  if (dim < 1 || dim > 3)
-    throw HipError(RYUJIN_ERR_ARG, "dim must be 1, 2 or 3");
-  if (p.limiter_iterations < 0 || p.limiter_iterations > 2)
-    throw HipError(RYUJIN_ERR_ARG, "The number of limiter iterations must be between [0,2]");
-  if (p.debug_pij_storage > 2)
-    throw HipError(RYUJIN_ERR_ARG, "debug_pij_storage must be < 0, 0, 1 or 2 (per-tile P_ij in 3-D was retired)");
-  K = p.equation == RYUJIN_EQ_SHALLOW_WATER ? dim + 1 : dim + 2;
-  NB = p.equation == RYUJIN_EQ_EULER ? 3 : (p.equation == RYUJIN_EQ_EULER_AEOS ? 4 : 5);
-  NPREC = p.equation == RYUJIN_EQ_EULER_AEOS ? 4 : 2;
-  if (p.equation == RYUJIN_EQ_SCALAR_CONSERVATION) {
-    K = 1;
-    NB = 2;
-    NPREC = 2 * dim;
-  }
-  KP = (K + 1) / 2 * 2;
+  const SystemShape shape = system_shape(p.equation, dim);
+  K = shape.K;
+  KP = shape.KP;
+  NB = shape.NB;
+  NPREC = shape.NPREC;
+  RS = shape.RS;
+  dg = o.discontinuous_ansatz != 0;
 
+  /* ---- streams and events -------------------------------------------------- */
   HIP_CHECK(hipSetDevice(device));
   HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
   HIP_CHECK(hipStreamCreateWithFlags(&comm_stream, hipStreamNonBlocking));
@@ -790,6 +746,7 @@ void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params
     HIP_CHECK(hipEventCreate(&e));
   HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&h_scalars), sizeof(DeviceScalars)));
 
+  /* ---- parameter blocks ---------------------------------------------------- */
   eparams = make_euler_params(p);
   aeosparams = make_aeos_params(p);
 
@@ -806,12 +763,10 @@ void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params
   if (p.equation == RYUJIN_EQ_SCALAR_CONSERVATION && p.sc_flux == RYUJIN_FLUX_FUNCTION) {
     /* the default expression of flux_function.h:32, in every direction (as "burgers"), until
      * ryujin_hip_flux_configure_function replaces it */
-    if (!(p.sc_derivative_approximation_delta > 0.) || !std::isfinite(p.sc_derivative_approximation_delta))
-      throw HipError(RYUJIN_ERR_ARG, "flux: derivative approximation delta must be positive and finite");
     static const char *const defaults[3] = {"0.5*u*u", "0.5*u*u; 0.5*u*u", "0.5*u*u; 0.5*u*u; 0.5*u*u"};
     auto program = std::make_unique<FluxProgram>();
     std::string error;
-    if (const int status = flux_compile(defaults[p.dim >= 1 && p.dim <= 3 ? p.dim - 1 : 0], p.dim, *program, error))
+    if (const int status = flux_compile(defaults[dim - 1], dim, *program, error))
       throw HipError(status, error);
     d_flux_function.upload(program.get(), 1);
     flux_n_instructions = program->n_instructions;
@@ -845,95 +800,42 @@ void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params
       d_class_table.upload(L.class_table);
     }
   }
-  {
-    /* bit c of lower_mask[row] <=> column c of the row lies below the diagonal (cols < row) */
-    std::vector<uint32_t> lower_mask(L.rows_padded, 0u);
-    if (L.max_row_len <= 32)
-      parallel_chunks(L.n_owned, [&](const uint64_t i0, const uint64_t i1) {
-        for (uint32_t i = (uint32_t)i0; i < (uint32_t)i1; ++i)
-          for (uint32_t c = 1; c < L.row_len[i]; ++c)
-            if (L.cols[L.pos(i, c)] < i)
-              lower_mask[i] |= 1u << c;
-      });
-    d_lower_mask.upload(lower_mask);
-  }
+  d_lower_mask.upload(lower_mask(L));
   {
     const auto cij = L.scatter(o, o.cij, (uint32_t)dim);
     d_cij.upload(cij);
-    const auto mij = L.scatter(o, o.mij, 1);
-    d_mij.upload(mij);
-    dg = o.discontinuous_ansatz != 0;
+    d_mij.upload(L.scatter(o, o.mij, 1));
     if (dg) {
-      /* Scalar conservation: refused. The branch is written (k_low_order_sc<DIM, HAS_STAGES, true>,
-       * k_bounds_combine_minmax<2, 0b10>, k_pij_lij<E, true>), but the reference's own scalar Riemann solver cannot
-       * run on a dG stencil: the entries between DoFs of face-neighbour cells that do not lie on the shared face have
-       * c_ij = 0 exactly, n_ij = c_ij / |c_ij| is 0/0, and |f_i.n - f_j.n| / max(|u_i - u_j|, 2 delta) -- taken
-       * through std::max, which returns its first argument when the comparison with a NaN fails
-       * (scalar_conservation/riemann_solver.template.h:63,95-96) -- stays NaN: d_ij = 0 * NaN
-       * (tests/test_dg_q1.py::test_scalar_conservation_on_a_dg_stencil_is_nan_in_the_reference_formulas). */
-      if (p.equation == RYUJIN_EQ_SCALAR_CONSERVATION)
-        throw HipError(RYUJIN_ERR_UNSUPPORTED,
-                       "discontinuous ansatz with scalar conservation equations: the reference's Riemann solver is 0/0 "
-                       "on the structural zeros of a dG stencil");
-      if (!o.incidence || !o.mass_matrix_inverse)
-        throw HipError(RYUJIN_ERR_ARG, "discontinuous ansatz without incidence / inverse mass matrix");
       d_incidence.upload(L.scatter(o, o.incidence, 1));
       d_minv.upload(L.scatter(o, o.mass_matrix_inverse, 1));
     }
-
-    /* coupling boundary pairs: position of (i,col_idx) and the value of c_ji */
-    n_pairs = o.n_pairs;
-    std::vector<uint32_t> p_pos(n_pairs);
-    std::vector<double> p_cji((size_t)n_pairs * dim);
-    for (uint32_t q = 0; q < n_pairs; ++q) {
-      const uint64_t pos = L.pos(o.p_i[q], o.p_col[q]);
-      if (L.cols[pos] != o.p_j[q])
-        throw HipError(RYUJIN_ERR_ARG, "coupling_boundary_pairs do not match the sparsity pattern");
-      p_pos[q] = (uint32_t)pos;
-      const uint64_t pos_t = L.idx_t[pos];
-      for (int d = 0; d < dim; ++d)
-        p_cji[(size_t)q * dim + d] = cij[L.comp_pos(pos_t, (uint32_t)dim, (uint32_t)d)];
-    }
-    d_p_i.upload(o.p_i, n_pairs);
-    d_p_j.upload(o.p_j, n_pairs);
-    d_p_pos.upload(p_pos);
-    d_p_cji.upload(p_cji);
+    const PairTables pairs = build_pair_tables(o, L, cij, dim);
+    d_p_i.upload(o.p_i, o.n_pairs);
+    d_p_j.upload(o.p_j, o.n_pairs);
+    d_p_pos.upload(pairs.pos);
+    d_p_cji.upload(pairs.cji);
   }
   d_mi.upload(o.mi, o.n_relevant);
   d_mi_inv.upload(o.mi_inv, o.n_relevant);
 
+  /* ---- boundary map, grouped by DoF ---------------------------------------- */
+  bdry = build_boundary_tables(o, L, dim);
+  d_bc_mask.upload(bdry.bc_mask);
+  d_bc_first.upload(bdry.bc_first);
+  d_grp_start.upload(bdry.grp_start);
+  d_b_i.upload(bdry.b_i);
+  d_b_normal.upload(bdry.b_normal);
+  d_b_id.upload(bdry.b_id);
+  d_dirichlet.alloc((size_t)bdry.n_bdry * K);
+
+  /* ---- the mesh as the kernels see it -------------------------------------- */
+  const MeshKnobs knobs = mesh_knobs(p, L, dim, RYUJIN_XCD_CHUNK_3D, kWavesPerBlock);
   mesh.n_owned = L.n_owned;
   mesh.n_relevant = L.n_relevant;
   mesh.n_slices = L.n_slices;
-  bounds_stride = (std::max<uint32_t>(L.rows_padded, L.n_relevant) + 63u) / 64u * 64u;
-  mesh.bounds_stride = bounds_stride;
+  mesh.bounds_stride = knobs.bounds_stride;
   mesh.slice_begin = 0;
   mesh.slice_end = L.n_slices;
-  /* rows [0, n_export) are the ones other ranks hold as ghosts (offline_data.template.h:213-249) */
-  n_export_slices = std::min<uint32_t>(L.n_slices, (o.n_export + kWave - 1) / kWave);
-  /* The overlap of the exchanges with the interior rows rests on: only export rows couple to ghost columns
-   * (true for a symmetric stencil: if i sees the ghost j, the owner of j sees i). Checked, not assumed. */
-  if (L.n_owned > n_export_slices * kWave) {
-    const uint32_t first = n_export_slices * kWave;
-    std::atomic<bool> found{false};
-    parallel_chunks(L.n_owned - first, [&](const uint64_t i0, const uint64_t i1) {
-      for (uint32_t i = first + (uint32_t)i0; i < first + (uint32_t)i1 && !found.load(std::memory_order_relaxed); ++i)
-        for (uint32_t c = 0; c < L.row_len[i]; ++c)
-          if (L.cols[L.pos(i, c)] >= L.n_owned) {
-            found.store(true, std::memory_order_relaxed);
-            break;
-          }
-    });
-    interior_reads_ghosts = found.load();
-  }
-  /* test hooks (ryujin_hip_params::debug_*; tests/test_gpu_parity.py runs the partitioned cases through both
-   * branches of each): force the fallback choreography / move the mesh size below which boundary conditions
-   * ride on the pre-pass / small meshes run the kernels of the large ones */
-  interior_reads_ghosts = interior_reads_ghosts || p.debug_join_exchanges != 0;
-  if (p.debug_bc_fold_max_slices != 0)
-    bc_fold_max_slices = p.debug_bc_fold_max_slices < 0 ? 0u : (uint32_t)p.debug_bc_fold_max_slices;
-  if (p.debug_no_small_mesh_split != 0)
-    resident_waves_step5 = resident_waves_step6 = 0;
   mesh.slice_off = d_slice_off.ptr;
   mesh.row_len = d_row_len.ptr;
   mesh.cols = d_cols.ptr;
@@ -942,26 +844,9 @@ void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params
   mesh.chain_loads = d_chain_loads.n != 0 ? d_chain_loads.ptr : nullptr;
   mesh.slice_class = d_slice_class.n != 0 ? d_slice_class.ptr : nullptr;
   mesh.class_table = d_class_table.n != 0 ? reinterpret_cast<const StencilClassEntry *>(d_class_table.ptr) : nullptr;
-  mesh.tail_queue_columns = std::max<uint32_t>(1u, std::min<uint32_t>(63u, L.max_row_len - 1u));
-  /* stacked blocks (row_context(), kernels_euler.hpp): debug_band_stride < 0 off, > 0 that many slices, 0 from the
-   * mesh, in 2-D: C2 (G = 47) -1.1 % per update, every sweep a little; in 3-D stacking lattice planes (G = 365 on the C4
-   * share) LOSES 1.7 % and stacking lattice rows (G = 2) is noise -- the re-fetches of neighbour data across XCDs that
-   * the counters show are not what limits the sweeps (profiles/r05p_ab_band_2d.log, r05p_ab_band_3d.log) */
-  mesh.band_stride = 1;
-  if (p.debug_band_stride > 0)
-    mesh.band_stride = (uint32_t)p.debug_band_stride;
-  else if (p.debug_band_stride == 0 && dim == 2) {
-    const uint32_t stride = L.lattice_stride(dim);
-    const uint32_t G = (stride + kWave / 2) / kWave;
-    if (G >= 2 && (uint64_t)G * kWavesPerBlock * 4 <= L.n_slices)
-      mesh.band_stride = G;
-  }
-  /* XCD-local block ranges (row_context()): debug_xcd_chunk < 0 off, > 0 that many blocks per XCD and chunk */
-  mesh.xcd_chunk = 0;
-  if (p.debug_xcd_chunk > 0)
-    mesh.xcd_chunk = (uint32_t)p.debug_xcd_chunk;
-  else if (p.debug_xcd_chunk == 0 && dim == 3)
-    mesh.xcd_chunk = RYUJIN_XCD_CHUNK_3D;
+  mesh.tail_queue_columns = knobs.tail_queue_columns;
+  mesh.band_stride = knobs.band_stride;
+  mesh.xcd_chunk = knobs.xcd_chunk;
   mesh.cij = d_cij.ptr;
   mesh.mij = d_mij.ptr;
   mesh.incidence = dg ? d_incidence.ptr : nullptr;
@@ -970,60 +855,24 @@ void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params
   mesh.mi_inv = d_mi_inv.ptr;
   mesh.measure_of_omega_inverse = 1. / o.measure_of_omega;
 
-  /* ---- boundary map: group entries by DoF, keep the original order inside a group ---- */
-  n_bdry = o.n_bdry;
-  bdry_perm.resize(n_bdry);
-  std::iota(bdry_perm.begin(), bdry_perm.end(), 0u);
-  std::stable_sort(bdry_perm.begin(), bdry_perm.end(),
-                   [&](uint32_t a, uint32_t b) { return o.b_i[a] < o.b_i[b]; });
-  {
-    std::vector<uint32_t> b_i(n_bdry), grp_start;
-    std::vector<double> b_normal((size_t)n_bdry * dim);
-    std::vector<uint8_t> b_id(n_bdry);
-    for (uint32_t e = 0; e < n_bdry; ++e) {
-      const uint32_t src = bdry_perm[e];
-      b_i[e] = o.b_i[src];
-      if (b_i[e] >= o.n_owned)
-        throw HipError(RYUJIN_ERR_ARG, "boundary_map entry refers to a non-owned DoF");
-      b_id[e] = o.b_id[src];
-      /* ids whose boundary condition reads the Dirichlet state (hyperbolic_system.h:1099-1159) */
-      if (b_id[e] == RYUJIN_BC_DIRICHLET || b_id[e] == RYUJIN_BC_DYNAMIC ||
-          b_id[e] == RYUJIN_BC_DIRICHLET_MOMENTUM)
-        needs_dirichlet = true;
-      for (int d = 0; d < dim; ++d)
-        b_normal[(size_t)e * dim + d] = o.b_normal[(size_t)src * dim + d];
-      if (e == 0 || b_i[e] != b_i[e - 1])
-        grp_start.push_back(e);
-    }
-    n_groups = (uint32_t)grp_start.size();
-    h_bc_rows.clear();
-    for (const uint32_t e : grp_start)
-      h_bc_rows.push_back(b_i[e]);
-    /* which rows of a slice are boundary DoFs, and the group of the first one (BcFold) */
-    std::vector<unsigned long long> bc_mask(L.n_slices, 0ull);
-    std::vector<uint32_t> bc_first(L.n_slices, 0u);
-    for (uint32_t g = n_groups; g-- > 0;) {
-      const uint32_t row = b_i[grp_start[g]];
-      bc_mask[row / kWave] |= 1ull << (row % kWave);
-      bc_first[row / kWave] = g; /* descending loop: the smallest group of the slice wins */
-    }
-    d_bc_mask.upload(bc_mask);
-    d_bc_first.upload(bc_first);
-    grp_start.push_back(n_bdry);
-    d_grp_start.upload(grp_start);
-    d_b_i.upload(b_i);
-    d_b_normal.upload(b_normal);
-    d_b_id.upload(b_id);
-    d_dirichlet.alloc((size_t)n_bdry * K);
-  }
+  /* ---- the choreography of the ghost exchange ------------------------------ */
+  n_export_slices = ryujin_hip::n_export_slices(o, L);
+  /* test hooks (ryujin_hip_params::debug_*; tests/test_gpu_parity.py runs the partitioned cases through both
+   * branches of each): force the fallback choreography / move the mesh size below which boundary conditions
+   * ride on the pre-pass / small meshes run the kernels of the large ones */
+  interior_reads_ghosts = interior_rows_read_ghosts(L, n_export_slices) || p.debug_join_exchanges != 0;
+  if (p.debug_bc_fold_max_slices != 0)
+    bc_fold_max_slices = p.debug_bc_fold_max_slices < 0 ? 0u : (uint32_t)p.debug_bc_fold_max_slices;
+  if (p.debug_no_small_mesh_split != 0)
+    resident_waves_step5 = resident_waves_step6 = 0;
 
   /* ---- module-owned storage (prepare(): hyperbolic_module.template.h:52-86) ---- */
   d_alpha.alloc(L.n_relevant);
   if (params.equation == RYUJIN_EQ_EULER_AEOS)
     d_gamma.alloc(L.n_relevant);
-  d_bounds.alloc((size_t)NB * bounds_stride);
+  d_bounds.alloc((size_t)NB * mesh.bounds_stride);
   if (dg)
-    d_bounds_combined.alloc((size_t)NB * bounds_stride);
+    d_bounds_combined.alloc((size_t)NB * mesh.bounds_stride);
   d_r.alloc((size_t)L.n_relevant * KP);
   d_dij.alloc(L.nnz_total);
   d_lij.alloc(L.nnz_total);
@@ -1032,25 +881,11 @@ void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params
   d_scalars.alloc(1);
 
   /* ---- exchange pattern ---- */
-  n_nbr = o.n_nbr;
-  if (n_nbr > 0 && !comm)
-    throw HipError(RYUJIN_ERR_COMM, "offline data has neighbour ranks but no communicator was given");
-  if (n_nbr > 0) {
-    nbr_rank.assign(o.nbr_rank, o.nbr_rank + n_nbr);
-    send_off.assign(o.send_off, o.send_off + n_nbr + 1);
-    recv_off.assign(o.recv_off, o.recv_off + n_nbr + 1);
-    row_send_off.assign(o.row_send_off, o.row_send_off + n_nbr + 1);
-    d_send_idx.upload(o.send_idx, send_off[n_nbr]);
-    std::vector<uint32_t> row_send_pos(row_send_off[n_nbr]);
-    for (uint32_t e = 0; e < row_send_off[n_nbr]; ++e)
-      row_send_pos[e] = (uint32_t)L.pos(o.row_send_row[e], o.row_send_col[e]);
-    d_row_send_pos.upload(row_send_pos);
-    row_recv_off.resize((size_t)n_nbr + 1);
-    for (int q = 0; q <= n_nbr; ++q)
-      row_recv_off[q] = L.ghost_ptr[recv_off[q] - L.n_owned];
-    const size_t buf =
-        std::max<size_t>((size_t)send_off[n_nbr] * std::max(KP, NPREC), row_send_off[n_nbr]);
-    d_send_buf.alloc(buf);
+  exch = build_exchange_tables(o, L, KP, NPREC);
+  if (exch.n_nbr > 0) {
+    d_send_idx.upload(o.send_idx, exch.send_off[exch.n_nbr]);
+    d_row_send_pos.upload(exch.row_send_pos);
+    d_send_buf.alloc(exch.send_buffer_doubles);
   }
   HIP_CHECK(hipStreamSynchronize(stream));
 }
@@ -1146,7 +981,7 @@ void ryujin_hip_ctx::sweep(F &&launch)
     StepBegin &b;
     ~Consume() { b = StepBegin{}; }
   } consume{pending_begin};
-  if (n_nbr == 0) {
+  if (exch.n_nbr == 0) {
     run(0, L.n_slices, stream);
     return;
   }
@@ -1169,8 +1004,8 @@ void ryujin_hip_ctx::local_before_pack()
   const unsigned long x = local_exchanges;
   if (x == 0)
     return;
-  for (int q = 0; q < n_nbr; ++q) {
-    const int peer = g.loopback ? comm->rank : nbr_rank[q];
+  for (int q = 0; q < exch.n_nbr; ++q) {
+    const int peer = g.loopback ? comm->rank : exch.nbr_rank[q];
     g.await(g.pulled, peer, x);
     HIP_CHECK(hipStreamWaitEvent(comm_stream,
                                  g.ev_pulled[(size_t)peer * LocalGroup::kRing + (x - 1) % LocalGroup::kRing], 0));
@@ -1187,16 +1022,16 @@ void ryujin_hip_ctx::local_exchange(double *base, const std::vector<size_t> &sen
   const unsigned long x = local_exchanges;
   const size_t slot = x % LocalGroup::kRing;
   const int me = comm->rank;
-  for (int q = 0; q < n_nbr; ++q)
-    g.mail[me][nbr_rank[q]] = d_send_buf.ptr + send_offset[q];
+  for (int q = 0; q < exch.n_nbr; ++q)
+    g.mail[me][exch.nbr_rank[q]] = d_send_buf.ptr + send_offset[q];
   HIP_CHECK(hipEventRecord(g.ev_packed[(size_t)me * LocalGroup::kRing + slot], comm_stream));
   g.publish(g.packed, me, x + 1);
-  for (int q = 0; q < n_nbr; ++q) {
-    const int peer = g.loopback ? me : nbr_rank[q];
+  for (int q = 0; q < exch.n_nbr; ++q) {
+    const int peer = g.loopback ? me : exch.nbr_rank[q];
     g.await(g.packed, peer, x + 1);
     HIP_CHECK(hipStreamWaitEvent(comm_stream, g.ev_packed[(size_t)peer * LocalGroup::kRing + slot], 0));
     /* loopback: what the neighbour on the other side would have received from me */
-    const double *src = g.loopback ? g.mail[me][nbr_rank[n_nbr - 1 - q]] : g.mail[nbr_rank[q]][me];
+    const double *src = g.loopback ? g.mail[me][exch.nbr_rank[exch.n_nbr - 1 - q]] : g.mail[exch.nbr_rank[q]][me];
     if (recv_count[q])
       HIP_CHECK(hipMemcpyAsync(base + recv_offset[q], src, recv_count[q] * sizeof(double),
                                hipMemcpyDeviceToDevice, comm_stream));
@@ -1285,32 +1120,32 @@ bool ryujin_hip_ctx::reduce_over_ranks(double *dev, std::initializer_list<RankRe
 
 void ryujin_hip_ctx::exchange_vector(double *v, int stride, bool after_split_sweep)
 {
-  if (n_nbr == 0)
+  if (exch.n_nbr == 0)
     return;
   begin_exchange(after_split_sweep);
   if (comm->local)
     local_before_pack();
-  const uint32_t n_send = send_off[n_nbr];
+  const uint32_t n_send = exch.send_off[exch.n_nbr];
   hipLaunchKernelGGL(k_pack_vector, dim3(grid_for((size_t)n_send * stride)), dim3(kBlock), 0, comm_stream,
                      n_send, d_send_idx.ptr, stride, v, d_send_buf.ptr);
   if (comm->local) {
-    std::vector<size_t> off(n_nbr), dst(n_nbr), rcnt(n_nbr);
-    for (int q = 0; q < n_nbr; ++q) {
-      off[q] = (size_t)send_off[q] * stride;
-      dst[q] = (size_t)recv_off[q] * stride;
-      rcnt[q] = (size_t)(recv_off[q + 1] - recv_off[q]) * stride;
+    std::vector<size_t> off(exch.n_nbr), dst(exch.n_nbr), rcnt(exch.n_nbr);
+    for (int q = 0; q < exch.n_nbr; ++q) {
+      off[q] = (size_t)exch.send_off[q] * stride;
+      dst[q] = (size_t)exch.recv_off[q] * stride;
+      rcnt[q] = (size_t)(exch.recv_off[q + 1] - exch.recv_off[q]) * stride;
     }
     local_exchange(v, off, dst, rcnt);
     end_exchange();
     return;
   }
   NCCL_CHECK(ncclGroupStart());
-  for (int q = 0; q < n_nbr; ++q) {
-    NCCL_CHECK(ncclSend(d_send_buf.ptr + (size_t)send_off[q] * stride,
-                        (size_t)(send_off[q + 1] - send_off[q]) * stride, ncclDouble, nbr_rank[q],
+  for (int q = 0; q < exch.n_nbr; ++q) {
+    NCCL_CHECK(ncclSend(d_send_buf.ptr + (size_t)exch.send_off[q] * stride,
+                        (size_t)(exch.send_off[q + 1] - exch.send_off[q]) * stride, ncclDouble, exch.nbr_rank[q],
                         comm->comm, comm_stream));
-    NCCL_CHECK(ncclRecv(v + (size_t)recv_off[q] * stride,
-                        (size_t)(recv_off[q + 1] - recv_off[q]) * stride, ncclDouble, nbr_rank[q],
+    NCCL_CHECK(ncclRecv(v + (size_t)exch.recv_off[q] * stride,
+                        (size_t)(exch.recv_off[q + 1] - exch.recv_off[q]) * stride, ncclDouble, exch.nbr_rank[q],
                         comm->comm, comm_stream));
   }
   NCCL_CHECK(ncclGroupEnd());
@@ -1319,31 +1154,31 @@ void ryujin_hip_ctx::exchange_vector(double *v, int stride, bool after_split_swe
 
 void ryujin_hip_ctx::exchange_matrix(double *m, bool after_split_sweep)
 {
-  if (n_nbr == 0)
+  if (exch.n_nbr == 0)
     return;
   begin_exchange(after_split_sweep);
   if (comm->local)
     local_before_pack();
-  const uint32_t n_send = row_send_off[n_nbr];
+  const uint32_t n_send = exch.row_send_off[exch.n_nbr];
   hipLaunchKernelGGL(k_pack_matrix, dim3(grid_for(n_send)), dim3(kBlock), 0, comm_stream, n_send,
                      d_row_send_pos.ptr, m, d_send_buf.ptr);
   if (comm->local) {
-    std::vector<size_t> off(n_nbr), dst(n_nbr), rcnt(n_nbr);
-    for (int q = 0; q < n_nbr; ++q) {
-      off[q] = row_send_off[q];
-      dst[q] = L.nnz_sell + row_recv_off[q];
-      rcnt[q] = row_recv_off[q + 1] - row_recv_off[q];
+    std::vector<size_t> off(exch.n_nbr), dst(exch.n_nbr), rcnt(exch.n_nbr);
+    for (int q = 0; q < exch.n_nbr; ++q) {
+      off[q] = exch.row_send_off[q];
+      dst[q] = L.nnz_sell + exch.row_recv_off[q];
+      rcnt[q] = exch.row_recv_off[q + 1] - exch.row_recv_off[q];
     }
     local_exchange(m, off, dst, rcnt);
     end_exchange();
     return;
   }
   NCCL_CHECK(ncclGroupStart());
-  for (int q = 0; q < n_nbr; ++q) {
-    NCCL_CHECK(ncclSend(d_send_buf.ptr + row_send_off[q], row_send_off[q + 1] - row_send_off[q],
-                        ncclDouble, nbr_rank[q], comm->comm, comm_stream));
-    NCCL_CHECK(ncclRecv(m + L.nnz_sell + row_recv_off[q], row_recv_off[q + 1] - row_recv_off[q],
-                        ncclDouble, nbr_rank[q], comm->comm, comm_stream));
+  for (int q = 0; q < exch.n_nbr; ++q) {
+    NCCL_CHECK(ncclSend(d_send_buf.ptr + exch.row_send_off[q], exch.row_send_off[q + 1] - exch.row_send_off[q],
+                        ncclDouble, exch.nbr_rank[q], comm->comm, comm_stream));
+    NCCL_CHECK(ncclRecv(m + L.nnz_sell + exch.row_recv_off[q], exch.row_recv_off[q + 1] - exch.row_recv_off[q],
+                        ncclDouble, exch.nbr_rank[q], comm->comm, comm_stream));
   }
   NCCL_CHECK(ncclGroupEnd());
   end_exchange();
@@ -1389,15 +1224,15 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStag
   const auto &eparams = eq_params<E>(); /* shadows the member: the equation's parameter block */
   State &s = state(h);
   const dim3 block(kBlock);
-  if (iv_stage.on && n_bdry && needs_dirichlet) {
+  if (iv_stage.on && bdry.n_bdry && bdry.needs_dirichlet) {
     /* initial_state(position, t + c tau) of every boundary_map entry, evaluated where the data is read: behind
      * every kernel of the previous stage that read the buffer (compute stream order; the export part of the previous
      * pre-pass may have applied boundary conditions on comm_stream) and behind the step-4 kernel of the first stage,
      * which left tau_rk. Nothing on the host waits for tau. */
     if (iv.state == kIvFunction) {
       join_export();
-      hipLaunchKernelGGL(k_initial_values_function_dirichlet<E>, dim3(grid_for(n_bdry, kInitialValuesBlock)),
-                         dim3(kInitialValuesBlock), 0, stream, iv, d_iv_function.ptr, n_bdry, d_iv_b_positions.ptr,
+      hipLaunchKernelGGL(k_initial_values_function_dirichlet<E>, dim3(grid_for(bdry.n_bdry, kInitialValuesBlock)),
+                         dim3(kInitialValuesBlock), 0, stream, iv, d_iv_function.ptr, bdry.n_bdry, d_iv_b_positions.ptr,
                          d_b_id.ptr, iv_stage.t, iv_stage.c, d_scalars.ptr, d_dirichlet.ptr);
       HIP_CHECK(hipGetLastError());
       have_dirichlet = true;
@@ -1405,13 +1240,13 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStag
       throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: scalar conservation has the function state only");
     } else {
       join_export();
-      hipLaunchKernelGGL(k_initial_values_dirichlet<E>, dim3(grid_for(n_bdry, kInitialValuesBlock)),
-                         dim3(kInitialValuesBlock), 0, stream, iv, n_bdry, d_iv_b_positions.ptr, d_b_id.ptr,
+      hipLaunchKernelGGL(k_initial_values_dirichlet<E>, dim3(grid_for(bdry.n_bdry, kInitialValuesBlock)),
+                         dim3(kInitialValuesBlock), 0, stream, iv, bdry.n_bdry, d_iv_b_positions.ptr, d_b_id.ptr,
                          iv_stage.t, iv_stage.c, d_scalars.ptr, d_dirichlet.ptr);
       HIP_CHECK(hipGetLastError());
       have_dirichlet = true;
     }
-  } else if (dirichlet && n_bdry) {
+  } else if (dirichlet && bdry.n_bdry) {
     /* permute into the grouped order, then upload */
     if (deferred) {
       /* inside a device-resident RK step: a pinned staging buffer per stage, no host synchronisation (a buffer
@@ -1419,23 +1254,21 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStag
        * copy is ordered on the compute stream behind every kernel of the previous stage that read the data. */
       double *&buf = h_dirichlet_stage[rk_stage];
       if (!buf)
-        HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&buf), (size_t)n_bdry * K * sizeof(double)));
-      for (uint32_t e = 0; e < n_bdry; ++e)
-        std::memcpy(&buf[(size_t)e * K], &dirichlet[(size_t)bdry_perm[e] * K], sizeof(double) * K);
+        HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&buf), (size_t)bdry.n_bdry * K * sizeof(double)));
+      bdry.permute(dirichlet, K, buf);
       join_export(); /* the export part of the previous pre-pass may have applied boundary conditions */
-      HIP_CHECK(hipMemcpyAsync(d_dirichlet.ptr, buf, (size_t)n_bdry * K * sizeof(double), hipMemcpyHostToDevice,
+      HIP_CHECK(hipMemcpyAsync(d_dirichlet.ptr, buf, (size_t)bdry.n_bdry * K * sizeof(double), hipMemcpyHostToDevice,
                                stream));
     } else {
-      std::vector<double> tmp((size_t)n_bdry * K);
-      for (uint32_t e = 0; e < n_bdry; ++e)
-        std::memcpy(&tmp[(size_t)e * K], &dirichlet[(size_t)bdry_perm[e] * K], sizeof(double) * K);
+      std::vector<double> tmp((size_t)bdry.n_bdry * K);
+      bdry.permute(dirichlet, K, tmp.data());
       HIP_CHECK(hipMemcpyAsync(d_dirichlet.ptr, tmp.data(), tmp.size() * sizeof(double),
                                hipMemcpyHostToDevice, stream));
       HIP_CHECK(hipStreamSynchronize(stream)); /* tmp goes out of scope */
     }
     have_dirichlet = true;
   }
-  if (needs_dirichlet && !have_dirichlet)
+  if (bdry.needs_dirichlet && !have_dirichlet)
     throw HipError(RYUJIN_ERR_ARG, "prepare_state_vector: the boundary map holds dirichlet / dynamic / "
                                    "dirichlet_momentum ids but no Dirichlet data was ever passed");
   /* Boundary conditions (:102-146). Small meshes: applied by the first pre-pass sweep itself (apply_bc_row; a
@@ -1444,7 +1277,7 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStag
    * comm_stream, the interior part never writes them. Large meshes: a launch of its own in front of the sweep
    * (the streaming pre-pass kernel keeps its occupancy); it writes export rows from the compute stream and
    * therefore joins whatever comm_stream still holds for them. */
-  const BcFold bc{n_groups ? d_bc_mask.ptr : nullptr, d_bc_first.ptr, d_grp_start.ptr, d_b_normal.ptr,
+  const BcFold bc{bdry.n_groups ? d_bc_mask.ptr : nullptr, d_bc_first.ptr, d_grp_start.ptr, d_b_normal.ptr,
                   d_b_id.ptr,   d_dirichlet.ptr};
   const bool fold_bc = L.n_slices <= bc_fold_max_slices;
   /* the step that wrote this vector left its precomputed values and Riemann records behind (FusedPrecompute):
@@ -1453,18 +1286,18 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStag
   if constexpr (E::kFusablePrecompute)
     have_records = s.precomputed && !fold_bc;
   s.precomputed = false;
-  if (!fold_bc && n_groups) {
+  if (!fold_bc && bdry.n_groups) {
     if (exchange_after_exp)
       wait_comm();
     else
       join_export();
     if constexpr (E::kFusablePrecompute) {
       if (have_records)
-        hipLaunchKernelGGL(k_apply_bc_records<E>, dim3(grid_for(n_groups)), block, 0, stream, eparams, n_groups,
+        hipLaunchKernelGGL(k_apply_bc_records<E>, dim3(grid_for(bdry.n_groups)), block, 0, stream, eparams, bdry.n_groups,
                            d_b_i.ptr, d_row_len.ptr, bc, s.U.ptr, s.prec.ptr, s.rrec.ptr);
     }
     if (!have_records)
-      hipLaunchKernelGGL(k_apply_bc<E>, dim3(grid_for(n_groups)), block, 0, stream, eparams, n_groups, d_b_i.ptr,
+      hipLaunchKernelGGL(k_apply_bc<E>, dim3(grid_for(bdry.n_groups)), block, 0, stream, eparams, bdry.n_groups, d_b_i.ptr,
                          bc, s.U.ptr);
   }
   /* U.update_ghost_values(), :148, is enqueued BEHIND the export part of the first pre-pass sweep, which
@@ -1473,21 +1306,19 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStag
   if constexpr (std::is_same<typename E::Params, EulerAeosParams>::value) {
     /* n_precomputation_cycles = 2 (euler_aeos/hyperbolic_system.h:433), ghost update after each */
     sweep([&](const DeviceMesh &mm, dim3 grid) {
-      if (fold_bc)
-        hipLaunchKernelGGL((k_precompute_aeos0<E::DIMENSION, true>), grid, block, 0, launch_stream, eparams, mm, bc, s.U.ptr,
-                         s.prec.ptr, s.rrec.ptr, d_gamma.ptr);
-      else
-        hipLaunchKernelGGL((k_precompute_aeos0<E::DIMENSION, false>), grid, block, 0, launch_stream, eparams, mm, bc, s.U.ptr,
-                         s.prec.ptr, s.rrec.ptr, d_gamma.ptr);
+      with_bool(fold_bc, [&](auto fold) {
+        hipLaunchKernelGGL((k_precompute_aeos0<E::DIMENSION, decltype(fold)::value>), grid, block, 0, launch_stream,
+                           eparams, mm, bc, s.U.ptr, s.prec.ptr, s.rrec.ptr, d_gamma.ptr);
+      });
     });
     exchange_vector(s.U.ptr, KP, true);
     exchange_vector(s.prec.ptr, 4, true);
     if (L.n_relevant > L.n_owned) {
       /* Riemann records of the ghost rows from the exchanged (U_j, p_j): on comm_stream behind the two exchanges */
       hipLaunchKernelGGL(k_ghost_records_aeos<E::DIMENSION>, dim3(grid_for(L.n_relevant - L.n_owned)), block, 0,
-                         n_nbr ? comm_stream : stream, eparams, L.n_owned, L.n_relevant, s.U.ptr, s.prec.ptr,
+                         exch.n_nbr ? comm_stream : stream, eparams, L.n_owned, L.n_relevant, s.U.ptr, s.prec.ptr,
                          s.rrec.ptr, d_gamma.ptr);
-      if (n_nbr) {
+      if (exch.n_nbr) {
         comm_pending = true;
         exchange_after_exp = true;
       }
@@ -1502,18 +1333,15 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStag
       if (eparams.flux == RYUJIN_FLUX_FUNCTION) {
         /* the interpreter: a kernel of its own, one wave per block and slice */
         const dim3 slices(mm.slice_end - mm.slice_begin), wave(kFluxFunctionBlock);
-        if (fold_bc)
-          hipLaunchKernelGGL((k_precompute_sc_function<E::DIMENSION, true>), slices, wave, 0, launch_stream, eparams, mm,
-                             bc, d_flux_function.ptr, s.U.ptr, s.prec.ptr);
-        else
-          hipLaunchKernelGGL((k_precompute_sc_function<E::DIMENSION, false>), slices, wave, 0, launch_stream, eparams,
-                             mm, bc, d_flux_function.ptr, s.U.ptr, s.prec.ptr);
-      } else if (fold_bc)
-        hipLaunchKernelGGL((k_precompute_sc<E::DIMENSION, true>), grid, block, 0, launch_stream, eparams, mm, bc, s.U.ptr,
-                         s.prec.ptr);
-      else
-        hipLaunchKernelGGL((k_precompute_sc<E::DIMENSION, false>), grid, block, 0, launch_stream, eparams, mm, bc, s.U.ptr,
-                         s.prec.ptr);
+        with_bool(fold_bc, [&](auto fold) {
+          hipLaunchKernelGGL((k_precompute_sc_function<E::DIMENSION, decltype(fold)::value>), slices, wave, 0,
+                             launch_stream, eparams, mm, bc, d_flux_function.ptr, s.U.ptr, s.prec.ptr);
+        });
+      } else
+        with_bool(fold_bc, [&](auto fold) {
+          hipLaunchKernelGGL((k_precompute_sc<E::DIMENSION, decltype(fold)::value>), grid, block, 0, launch_stream,
+                             eparams, mm, bc, s.U.ptr, s.prec.ptr);
+        });
     });
     exchange_vector(s.U.ptr, KP, true);
     exchange_vector(s.prec.ptr, E::NPREC, true);
@@ -1528,23 +1356,21 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStag
       /* the owned rows are complete. Their producers: the last sweep of the step (its export part sits on
        * comm_stream, in front of this exchange in stream order) and, for boundary rows, the kernel above on the
        * compute stream -- with boundary DoFs the exchange is ordered behind the compute stream as well */
-      exchange_vector(s.U.ptr, KP, n_groups == 0);
+      exchange_vector(s.U.ptr, KP, bdry.n_groups == 0);
     } else {
       sweep([&](const DeviceMesh &mm, dim3 grid) {
-        if (fold_bc)
-          hipLaunchKernelGGL((k_precompute_records<E, true>), grid, block, 0, launch_stream, eparams, mm, bc,
-                             s.U.ptr, s.prec.ptr, s.rrec.ptr);
-        else
-          hipLaunchKernelGGL((k_precompute_records<E, false>), grid, block, 0, launch_stream, eparams, mm, bc,
-                             s.U.ptr, s.prec.ptr, s.rrec.ptr);
+        with_bool(fold_bc, [&](auto fold) {
+          hipLaunchKernelGGL((k_precompute_records<E, decltype(fold)::value>), grid, block, 0, launch_stream, eparams,
+                             mm, bc, s.U.ptr, s.prec.ptr, s.rrec.ptr);
+        });
       });
       exchange_vector(s.U.ptr, KP, true);
     }
     if (L.n_relevant > L.n_owned) {
       hipLaunchKernelGGL(k_ghost_precompute_records<E>, dim3(grid_for(L.n_relevant - L.n_owned)), block, 0,
-                         n_nbr ? comm_stream : stream, eparams, L.n_owned, L.n_relevant, s.U.ptr, s.prec.ptr,
+                         exch.n_nbr ? comm_stream : stream, eparams, L.n_owned, L.n_relevant, s.U.ptr, s.prec.ptr,
                          s.rrec.ptr);
-      if (n_nbr) { /* work on comm_stream behind the latest export part, as an exchange (not counted as one) */
+      if (exch.n_nbr) { /* work on comm_stream behind the latest export part, as an exchange (not counted as one) */
         comm_pending = true;
         exchange_after_exp = true;
       }
@@ -1652,7 +1478,7 @@ void ryujin_hip_ctx::step3_diagonal_tau(const StepPlan &plan, const State &old)
   constexpr int DIM = E::DIMENSION;
   const auto &eparams = eq_params<E>();
   const dim3 block(kBlock);
-  if (n_pairs) {
+  if (const uint32_t n_pairs = (uint32_t)d_p_pos.n) {
     join_export(); /* boundary pairs may sit in export rows, whose d_ij the export part wrote on comm_stream
                     * (and may point to ghost columns: the U exchange precedes that export part in stream order) */
     if constexpr (is_aeos_v<E>)
@@ -1778,7 +1604,7 @@ void ryujin_hip_ctx::step4_low_order(const StepPlan &plan, const StepArgs<E::DIM
     /* the bounds are extended over the stencil in step 5: their ghost range has to be current
      * (hyperbolic_module.template.h:601-613); SoA, one scalar vector per bound */
     for (int b = 0; b < NB; ++b)
-      exchange_vector(d_bounds.ptr + (size_t)b * bounds_stride, 1, true);
+      exchange_vector(d_bounds.ptr + (size_t)b * mesh.bounds_stride, 1, true);
   }
 }
 
@@ -2176,7 +2002,7 @@ int ryujin_hip_ctx::time_step(int scheme, int h_state, int n_tmp, const int *h_t
      * t + c_s tau) per stage (time_integrator.template.h:279-510: SSPRK22 t, t+tau; SSPRK33 t, t+tau, t+tau/2;
      * ERK stage s at t + s tau) through the caller's function. tau is known on the host as soon as step 3 of
      * the first stage has run; the first stage's remaining sweeps are already enqueued behind it. */
-    const bool time_dependent = dirichlet_fn != nullptr && n_bdry > 0 && needs_dirichlet;
+    const bool time_dependent = dirichlet_fn != nullptr && bdry.n_bdry > 0 && bdry.needs_dirichlet;
     std::vector<double> stage_data;
     double tau_first = 0.;
     auto stage_coefficient = [&](int st) -> double {
@@ -2188,7 +2014,7 @@ int ryujin_hip_ctx::time_step(int scheme, int h_state, int n_tmp, const int *h_t
       if (!time_dependent)
         return st == 0 ? dirichlet : nullptr;
       const double c = stage_coefficient(st);
-      stage_data.assign((size_t)n_bdry * K, 0.);
+      stage_data.assign((size_t)bdry.n_bdry * K, 0.);
       dirichlet_fn(dirichlet_user, t + c * tau_first, stage_data.data());
       return stage_data.data();
     };
@@ -2600,6 +2426,54 @@ namespace
     default: return f(EqTag<Euler<3>>{});
     }
   }
+
+  /* system_shape() (host_context.hpp) against the Descriptions of the device headers */
+  template <typename E>
+  constexpr bool shape_matches(const int equation)
+  {
+    const SystemShape s = system_shape(equation, E::DIMENSION);
+    bool ok = s.K == E::K && s.KP == StatePad<E::K>::KP && s.NB == E::NB;
+    if constexpr (is_scalar_v<E>)
+      ok = ok && s.NPREC == E::NPREC && s.RS == 0;
+    else
+      ok = ok && s.RS == E::RS;
+    if constexpr (is_aeos_v<E>)
+      ok = ok && s.NPREC == E::NPREC;
+    return ok;
+  }
+  static_assert(shape_matches<Euler<1>>(RYUJIN_EQ_EULER) && shape_matches<Euler<2>>(RYUJIN_EQ_EULER) &&
+                    shape_matches<Euler<3>>(RYUJIN_EQ_EULER),
+                "system_shape(): Euler");
+  static_assert(shape_matches<EulerAeos<1>>(RYUJIN_EQ_EULER_AEOS) && shape_matches<EulerAeos<2>>(RYUJIN_EQ_EULER_AEOS) &&
+                    shape_matches<EulerAeos<3>>(RYUJIN_EQ_EULER_AEOS),
+                "system_shape(): EulerAEOS");
+  static_assert(shape_matches<ShallowWater<1>>(RYUJIN_EQ_SHALLOW_WATER) &&
+                    shape_matches<ShallowWater<2>>(RYUJIN_EQ_SHALLOW_WATER),
+                "system_shape(): shallow water");
+  static_assert(shape_matches<ScalarConservation<1>>(RYUJIN_EQ_SCALAR_CONSERVATION) &&
+                    shape_matches<ScalarConservation<2>>(RYUJIN_EQ_SCALAR_CONSERVATION) &&
+                    shape_matches<ScalarConservation<3>>(RYUJIN_EQ_SCALAR_CONSERVATION),
+                "system_shape(): scalar conservation");
+
+  /* n rows from row `first` on between an AoS host array of stride K and the device array of stride KP */
+  template <bool kUpload>
+  void transfer_rows(const ryujin_hip_ctx &ctx, double *dev, std::conditional_t<kUpload, const double, double> *host,
+                     const size_t first, const size_t n)
+  {
+    const size_t K = ctx.K, KP = ctx.KP;
+    dev += first * KP;
+    host += first * K;
+    std::vector<double> tmp(K == KP ? 0 : n * KP, 0.);
+    if constexpr (kUpload) {
+      for (size_t i = 0; i < n && K != KP; ++i)
+        std::memcpy(&tmp[i * KP], &host[i * K], sizeof(double) * K);
+      HIP_CHECK(hipMemcpy(dev, K == KP ? host : tmp.data(), n * KP * sizeof(double), hipMemcpyHostToDevice));
+    } else {
+      HIP_CHECK(hipMemcpy(K == KP ? host : tmp.data(), dev, n * KP * sizeof(double), hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < n && K != KP; ++i)
+        std::memcpy(&host[i * K], &tmp[i * KP], sizeof(double) * K);
+    }
+  }
 } // namespace
 
 extern "C" {
@@ -2795,10 +2669,10 @@ int ryujin_hip_exchange_info(ryujin_hip_ctx *ctx, int *n_nbr, int *nbr_rank, int
     if (!ctx)
       throw HipError(RYUJIN_ERR_ARG, "null context");
     if (n_nbr)
-      *n_nbr = ctx->n_nbr;
+      *n_nbr = ctx->exch.n_nbr;
     if (nbr_rank)
-      for (int q = 0; q < ctx->n_nbr && q < max_nbr; ++q)
-        nbr_rank[q] = ctx->nbr_rank[q];
+      for (int q = 0; q < ctx->exch.n_nbr && q < max_nbr; ++q)
+        nbr_rank[q] = ctx->exch.nbr_rank[q];
     if (n_exchanges)
       *n_exchanges = ctx->n_exchanges;
     if (n_allreduces)
@@ -2839,12 +2713,8 @@ int ryujin_hip_state_alloc(ryujin_hip_ctx *ctx, int *handle)
       h = (int)ctx->states.size() - 1;
       ctx->states[h]->U.alloc((size_t)ctx->L.n_relevant * ctx->KP);
       ctx->states[h]->prec.alloc((size_t)ctx->L.n_relevant * ctx->NPREC);
-      if (ctx->params.equation == RYUJIN_EQ_EULER) /* Euler<dim>::RS: the combined node record in 3-D */
-        ctx->states[h]->rrec.alloc((size_t)ctx->L.n_relevant * (ctx->dim == 3 ? Euler<3>::RS : ctx->dim == 2 ? Euler<2>::RS : Euler<1>::RS));
-      else if (ctx->params.equation == RYUJIN_EQ_EULER_AEOS)
-        ctx->states[h]->rrec.alloc((size_t)ctx->L.n_relevant * ((6 + ctx->dim + 1) / 2 * 2));
-      else if (ctx->params.equation == RYUJIN_EQ_SHALLOW_WATER)
-        ctx->states[h]->rrec.alloc((size_t)ctx->L.n_relevant * ((2 + ctx->dim + 1) / 2 * 2));
+      if (ctx->RS != 0) /* E::RS; scalar conservation keeps no node records */
+        ctx->states[h]->rrec.alloc((size_t)ctx->L.n_relevant * ctx->RS);
     }
     ctx->states[h]->used = true;
     ctx->states[h]->precomputed = false;
@@ -2865,18 +2735,9 @@ int ryujin_hip_state_upload(ryujin_hip_ctx *ctx, int handle, const double *U_aos
 {
   return guarded_ctx(ctx, [&]() {
     auto &s = ctx->state(handle);
-    const size_t n = ctx->L.n_relevant;
-    const int K = ctx->K, KP = ctx->KP;
     ctx->finish();
     s.precomputed = false;
-    if (K == KP) {
-      HIP_CHECK(hipMemcpy(s.U.ptr, U_aos, n * K * sizeof(double), hipMemcpyHostToDevice));
-    } else {
-      std::vector<double> tmp(n * KP, 0.);
-      for (size_t i = 0; i < n; ++i)
-        std::memcpy(&tmp[i * KP], &U_aos[i * K], sizeof(double) * K);
-      HIP_CHECK(hipMemcpy(s.U.ptr, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
+    transfer_rows<true>(*ctx, s.U.ptr, U_aos, 0, ctx->L.n_relevant);
     return RYUJIN_OK;
   });
 }
@@ -2885,17 +2746,8 @@ int ryujin_hip_state_download(ryujin_hip_ctx *ctx, int handle, double *U_aos)
 {
   return guarded_ctx(ctx, [&]() {
     auto &s = ctx->state(handle);
-    const size_t n = ctx->L.n_relevant;
-    const int K = ctx->K, KP = ctx->KP;
     ctx->finish();
-    if (K == KP) {
-      HIP_CHECK(hipMemcpy(U_aos, s.U.ptr, n * K * sizeof(double), hipMemcpyDeviceToHost));
-    } else {
-      std::vector<double> tmp(n * KP);
-      HIP_CHECK(hipMemcpy(tmp.data(), s.U.ptr, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
-      for (size_t i = 0; i < n; ++i)
-        std::memcpy(&U_aos[i * K], &tmp[i * KP], sizeof(double) * K);
-    }
+    transfer_rows<false>(*ctx, s.U.ptr, U_aos, 0, ctx->L.n_relevant);
     return RYUJIN_OK;
   });
 }
@@ -2951,17 +2803,8 @@ int ryujin_hip_state_download_owned(ryujin_hip_ctx *ctx, int handle, double *U_a
 {
   return guarded_ctx(ctx, [&]() {
     auto &s = ctx->state(handle);
-    const size_t n = ctx->L.n_owned;
-    const int K = ctx->K, KP = ctx->KP;
     ctx->finish();
-    if (K == KP) {
-      HIP_CHECK(hipMemcpy(U_aos, s.U.ptr, n * K * sizeof(double), hipMemcpyDeviceToHost));
-    } else {
-      std::vector<double> tmp(n * KP);
-      HIP_CHECK(hipMemcpy(tmp.data(), s.U.ptr, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
-      for (size_t i = 0; i < n; ++i)
-        std::memcpy(&U_aos[i * K], &tmp[i * KP], sizeof(double) * K);
-    }
+    transfer_rows<false>(*ctx, s.U.ptr, U_aos, 0, ctx->L.n_owned);
     return RYUJIN_OK;
   });
 }
@@ -2971,13 +2814,13 @@ int ryujin_hip_state_download_prepared(ryujin_hip_ctx *ctx, int handle, double *
   return guarded_ctx(ctx, [&]() {
     auto &s = ctx->state(handle);
     const int K = ctx->K, KP = ctx->KP;
-    const uint32_t n_rows = (uint32_t)ctx->h_bc_rows.size();
+    const uint32_t n_rows = (uint32_t)ctx->bdry.rows.size();
     /* boundary rows inside export slices get their boundary conditions from the export part of the pre-pass, on
      * comm_stream (fold_bc): the pack kernel below reads them, so the compute stream joins comm_stream FIRST */
     ctx->wait_comm();
     if (n_rows != 0) {
       if (ctx->d_bc_rows.n == 0) {
-        ctx->d_bc_rows.upload(ctx->h_bc_rows);
+        ctx->d_bc_rows.upload(ctx->bdry.rows);
         ctx->d_bc_pack.alloc((size_t)n_rows * KP);
         HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_bc_pack), (size_t)n_rows * KP * sizeof(double)));
       }
@@ -2990,20 +2833,11 @@ int ryujin_hip_state_download_prepared(ryujin_hip_ctx *ctx, int handle, double *
       HIP_CHECK(hipMemcpy(ctx->h_bc_pack, ctx->d_bc_pack.ptr, (size_t)n_rows * KP * sizeof(double),
                           hipMemcpyDeviceToHost));
       for (uint32_t q = 0; q < n_rows; ++q)
-        std::memcpy(&U_aos[(size_t)ctx->h_bc_rows[q] * K], &ctx->h_bc_pack[(size_t)q * KP], sizeof(double) * K);
+        std::memcpy(&U_aos[(size_t)ctx->bdry.rows[q] * K], &ctx->h_bc_pack[(size_t)q * KP], sizeof(double) * K);
     }
     /* the ghost range [n_owned, n_relevant) */
-    const size_t first = ctx->L.n_owned, n = ctx->L.n_relevant - ctx->L.n_owned;
-    if (n != 0) {
-      if (K == KP) {
-        HIP_CHECK(hipMemcpy(U_aos + first * K, s.U.ptr + first * K, n * K * sizeof(double), hipMemcpyDeviceToHost));
-      } else {
-        std::vector<double> tmp(n * KP);
-        HIP_CHECK(hipMemcpy(tmp.data(), s.U.ptr + first * KP, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; ++i)
-          std::memcpy(&U_aos[(first + i) * K], &tmp[i * KP], sizeof(double) * K);
-      }
-    }
+    if (ctx->L.n_relevant != ctx->L.n_owned)
+      transfer_rows<false>(*ctx, s.U.ptr, U_aos, ctx->L.n_owned, ctx->L.n_relevant - ctx->L.n_owned);
     return RYUJIN_OK;
   });
 }
@@ -3367,12 +3201,12 @@ int ryujin_hip_debug_fetch(ryujin_hip_ctx *ctx, int what, double *out, size_t n_
     case 3: {
       if (n_doubles < (size_t)L.n_owned * ctx->NB)
         throw HipError(RYUJIN_ERR_ARG, "output buffer too small");
-      std::vector<double> tmp((size_t)ctx->NB * ctx->bounds_stride);
+      std::vector<double> tmp((size_t)ctx->NB * ctx->mesh.bounds_stride);
       HIP_CHECK(hipMemcpy(tmp.data(), ctx->d_bounds.ptr, tmp.size() * sizeof(double),
                           hipMemcpyDeviceToHost));
       for (uint32_t i = 0; i < L.n_owned; ++i)
         for (int b = 0; b < ctx->NB; ++b)
-          out[(size_t)i * ctx->NB + b] = tmp[(size_t)b * ctx->bounds_stride + i];
+          out[(size_t)i * ctx->NB + b] = tmp[(size_t)b * ctx->mesh.bounds_stride + i];
       break;
     }
     case 4: {
@@ -4022,10 +3856,8 @@ namespace
   {
     const size_t dim = (size_t)ctx->dim;
     ctx->d_iv_positions.upload(positions, (size_t)ctx->L.n_relevant * dim);
-    std::vector<double> grouped((size_t)ctx->n_bdry * dim);
-    for (uint32_t e = 0; e < ctx->n_bdry; ++e)
-      for (size_t d = 0; d < dim; ++d)
-        grouped[(size_t)e * dim + d] = b_positions[(size_t)ctx->bdry_perm[e] * dim + d];
+    std::vector<double> grouped((size_t)ctx->bdry.n_bdry * dim);
+    ctx->bdry.permute(b_positions, ctx->dim, grouped.data());
     ctx->d_iv_b_positions.upload(grouped);
   }
 
@@ -4169,7 +4001,7 @@ int ryujin_hip_initial_values_configure(ryujin_hip_ctx *ctx, const ryujin_hip_in
     if (ctx->params.equation == RYUJIN_EQ_SCALAR_CONSERVATION)
       throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: scalar conservation is not offered");
     const InitialValuesParams P = make_initial_values_params(*ctx, *initial_values);
-    if ((!positions && ctx->L.n_relevant > 0) || (!b_positions && ctx->n_bdry > 0))
+    if ((!positions && ctx->L.n_relevant > 0) || (!b_positions && ctx->bdry.n_bdry > 0))
       throw HipError(RYUJIN_ERR_ARG, "initial values: positions missing");
     ctx->finish();
     ctx->iv_configured = false;
@@ -4210,7 +4042,7 @@ int ryujin_hip_initial_values_configure_function(ryujin_hip_ctx *ctx, int n_expr
     P.state = kIvFunction;
     P.c[0] = ctx->params.gamma; /* Euler: from_primitive_state */
     set_initial_values_frame(P, ctx->dim, direction, position);
-    if ((!positions && ctx->L.n_relevant > 0) || (!b_positions && ctx->n_bdry > 0))
+    if ((!positions && ctx->L.n_relevant > 0) || (!b_positions && ctx->bdry.n_bdry > 0))
       throw HipError(RYUJIN_ERR_ARG, "initial values: positions missing");
     ctx->finish();
     ctx->iv_configured = false;

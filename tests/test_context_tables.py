@@ -1,0 +1,347 @@
+"""The host tables of a context on the CPU (ryujin_amd/csrc/host_context.hpp): what ryujin_hip_ctx::create() derives from
+the offline data, the parameters and the device layout -- the component counts, the boundary map grouped by DoF, the
+coupling pairs, lower_mask, the export slices, the launch knobs of the mesh, the exchange tables -- and every refusal it
+makes without a device. The checker (tests/cpp/context_tables.cc) prints the tables of an OfflineData dump; the expected
+values are formed here with numpy from the same offline arrays and from the SELL-64 addressing written out below, never
+from the checker's own output. Host logic only: no GPU, no HIP runtime; the checker is a stand-alone program built with
+the address and undefined-behaviour sanitizers."""
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import helpers_row_width_cases as row_width_cases
+from ryujin_amd import _build, capi, offline
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "tests", "cpp", "context_tables")
+WAVE = 64
+XCD_CHUNK_3D, WAVES_PER_BLOCK = 8, 4   # RYUJIN_XCD_CHUNK_3D, kWavesPerBlock (ryujin_hip.hip)
+ARG, COMM, UNSUPPORTED = capi.RYUJIN_ERR_ARG, capi.RYUJIN_ERR_COMM, capi.RYUJIN_ERR_UNSUPPORTED
+
+
+def _line(*bc):
+    return offline.MeshSpec(1, (500,), (0.0,), (1.0,), bc)
+
+
+MESHES = {
+    "step": lambda: offline.SyntheticOffline(offline.mach3_step_2d(60)),
+    "step_0of3": lambda: offline.SyntheticOffline(offline.mach3_step_2d(60, n_ranks=3, rank=0)),
+    "step_1of3": lambda: offline.SyntheticOffline(offline.mach3_step_2d(60, n_ranks=3, rank=1)),
+    "step_2of3": lambda: offline.SyntheticOffline(offline.mach3_step_2d(60, n_ranks=3, rank=2)),
+    "line": lambda: offline.SyntheticOffline(_line(capi.BC_DIRICHLET, capi.BC_DO_NOTHING)),
+    "line_dynamic": lambda: offline.SyntheticOffline(_line(capi.BC_DO_NOTHING, capi.BC_DYNAMIC)),
+    "line_momentum": lambda: offline.SyntheticOffline(_line(capi.BC_DIRICHLET_MOMENTUM, capi.BC_DO_NOTHING)),
+    "box": lambda: offline.SyntheticOffline(offline.box_3d(20)),
+    "wide": row_width_cases._lattice(row_width_cases.PLANE, 33),   # rows of 33 entries: no lower_mask
+    "flat": lambda: offline.SyntheticOffline(offline.rectangle_2d(200, ny=12)),   # 13 lattice rows of 201 nodes
+}
+TABLE_MESHES = ["step", "step_0of3", "step_1of3", "line", "box", "wide"]
+
+
+@pytest.fixture(scope="module")
+def checker():
+    synth = _build.build_synth()
+    src = os.path.join(ROOT, "tests", "cpp", "context_tables.cc")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", "-fsanitize=address,undefined",
+                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "ryujin_amd", "csrc"), src, synth,
+                    "-Wl,-rpath," + os.path.dirname(synth), "-o", BIN], check=True)
+    return BIN
+
+
+@pytest.fixture(scope="module")
+def meshes(tmp_path_factory):
+    """name -> (offline data, path of its dump); built on first use"""
+    directory, built = tmp_path_factory.mktemp("context_tables"), {}
+
+    def get(name):
+        if name not in built:
+            off = MESHES[name]()
+            path = str(directory / (name + ".offline"))
+            assert capi.load_synth().ryujin_offline_write(path.encode(), off.c, off.dim, 0, None, None) == 0
+            built[name] = (off, path)
+        return built[name]
+    return get
+
+
+def _run(checker, *source, **edits):
+    out = subprocess.run([checker, *map(str, source), *(f"{k}={v}" for k, v in edits.items())], capture_output=True,
+                         text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "runtime error" not in out.stderr, out.stderr  # (the undefined-behaviour sanitizer reports and goes on)
+    return json.loads(out.stdout)
+
+
+# ------------------------------------------------------------------ the expected tables
+
+class Expected:
+    """The offline arrays as plain CSR and the SELL-64 addressing of host_layout.hpp, written out: entry (row, c) of an
+    owned row at (slice_off[row / 64] + c) * 64 + row % 64, slice_off the running sum of the widest row of every 64;
+    the ghost rows as CSR behind them."""
+
+    def __init__(self, off):
+        o = off.c.contents
+        assert o.simd_length <= 1 or o.n_internal == 0, "plain CSR expected"
+        self.o, self.dim = o, off.dim
+        self.n_owned, self.n_relevant, self.n_export = o.n_owned, o.n_relevant, o.n_export
+        self.rs = capi.np_from_ptr(o.row_starts, o.n_relevant + 1, np.uint64).astype(np.int64)
+        nnz = int(self.rs[-1])
+        self.cols = capi.np_from_ptr(o.columns, nnz, np.uint32).astype(np.int64)
+        self.cij = capi.np_from_ptr(o.cij, nnz * off.dim, np.float64).reshape(nnz, off.dim)
+        widths = np.diff(self.rs)
+        self.rows = np.repeat(np.arange(o.n_relevant), widths)
+        self.c = np.arange(nnz) - np.repeat(self.rs[:-1], widths)
+        self.n_slices = -(-o.n_owned // WAVE)
+        self.rows_padded = self.n_slices * WAVE
+        padded = np.zeros(self.rows_padded, dtype=np.int64)
+        padded[: o.n_owned] = widths[: o.n_owned]
+        self.max_row_len = int(padded.max())
+        self.slice_off = np.concatenate([[0], np.cumsum(padded.reshape(-1, WAVE).max(axis=1))])
+        self.nnz_sell = int(self.slice_off[-1]) * WAVE
+        self.ghost_ptr = np.concatenate([[0], np.cumsum(widths[o.n_owned:])])
+        self.b_i = capi.np_from_ptr(o.b_i, o.n_bdry, np.uint32).astype(np.int64)
+        self.b_id = capi.np_from_ptr(o.b_id, o.n_bdry, np.uint8)
+        self.b_normal = capi.np_from_ptr(o.b_normal, o.n_bdry * off.dim, np.float64).reshape(o.n_bdry, off.dim)
+
+    def pos(self, row, c):
+        row, c = np.asarray(row, dtype=np.int64), np.asarray(c, dtype=np.int64)
+        assert (row < self.n_owned).all()
+        return (self.slice_off[row // WAVE] + c) * WAVE + row % WAVE
+
+    def array(self, pointer, n, dtype=np.uint32):
+        return capi.np_from_ptr(pointer, n, dtype).astype(np.int64)
+
+
+def _bits(values):
+    return np.ascontiguousarray(values, dtype=np.float64).reshape(-1).view(np.uint64)
+
+
+@pytest.fixture(scope="module")
+def tables(checker, meshes, tmp_path_factory):
+    """name -> (Expected, the checker's tables, the random arrays it permuted); one checker run per mesh"""
+    directory, done = tmp_path_factory.mktemp("permute"), {}
+
+    def get(name):
+        if name not in done:
+            off, path = meshes(name)
+            e = Expected(off)
+            rng = np.random.default_rng(7)
+            K = off.dim + 2   # Euler
+            by_K, by_dim = rng.uniform(-1.0, 1.0, (e.o.n_bdry, K)), rng.uniform(-1.0, 1.0, (e.o.n_bdry, off.dim))
+            data = str(directory / (name + ".bin"))
+            np.concatenate([by_K.reshape(-1), by_dim.reshape(-1)]).tofile(data)
+            done[name] = (e, _run(checker, "file", path, permute=data), (by_K, by_dim))
+        return done[name]
+    return get
+
+
+# ------------------------------------------------------------------ the tables, mesh by mesh
+
+@pytest.mark.parametrize("name", TABLE_MESHES)
+def test_boundary_permutation_and_groups(tables, name):
+    e, r, (by_K, by_dim) = tables(name)
+    perm = np.argsort(e.b_i, kind="stable")
+    assert r["status"] == 0 and r["n_bdry"] == len(perm)
+    assert np.array_equal(r["perm"], perm)
+    assert np.array_equal(r["b_i"], e.b_i[perm]) and np.array_equal(r["b_id"], e.b_id[perm])
+    assert np.array_equal(np.array(r["b_normal"], dtype=np.uint64), _bits(e.b_normal[perm]))
+    # permute(): a random [n_bdry][K] and a random [n_bdry][dim] array
+    assert np.array_equal(np.array(r["permuted_K"], dtype=np.uint64), _bits(by_K[perm]))
+    assert np.array_equal(np.array(r["permuted_dim"], dtype=np.uint64), _bits(by_dim[perm]))
+    # groups: the first indices of the distinct sorted b_i, then n_bdry
+    ordered = e.b_i[perm]
+    first = np.flatnonzero(np.concatenate([[True], ordered[1:] != ordered[:-1]])) if len(ordered) else np.zeros(0, int)
+    rows = ordered[first]
+    assert r["n_groups"] == len(first)
+    assert np.array_equal(r["grp_start"], np.concatenate([first, [len(perm)]]))
+    assert np.array_equal(r["rows"], rows)
+    mask = np.zeros(e.n_slices, dtype=np.uint64)
+    np.bitwise_or.at(mask, rows // WAVE, np.uint64(1) << (rows % WAVE).astype(np.uint64))
+    assert np.array_equal(np.array(r["bc_mask"], dtype=np.uint64), mask)
+    bc_first = np.zeros(e.n_slices, dtype=np.int64)
+    for g in range(len(rows) - 1, -1, -1):   # (ascending rows: the smallest group of a slice is written last)
+        bc_first[rows[g] // WAVE] = g
+    assert np.array_equal(r["bc_first"], bc_first)
+    assert all(bc_first[s] == np.flatnonzero(rows // WAVE == s).min() for s in np.unique(rows // WAVE))
+    if name in ("step", "box"):
+        assert len(perm) > len(first) > 0, "DoFs with several boundary entries"
+    if name == "line":
+        assert np.array_equal(np.diff(r["grp_start"]), [1, 1]), "groups of one entry"
+
+
+@pytest.mark.parametrize("name, needs", [("step", True), ("line", True), ("line_dynamic", True), ("line_momentum", True),
+                                         ("box", False), ("wide", False)])
+def test_needs_dirichlet(checker, meshes, name, needs):
+    off, path = meshes(name)
+    ids = set(capi.np_from_ptr(off.c.contents.b_id, off.n_bdry, np.uint8).tolist())
+    assert needs == bool(ids & {capi.BC_DIRICHLET, capi.BC_DYNAMIC, capi.BC_DIRICHLET_MOMENTUM})
+    assert _run(checker, "file", path, arrays=0)["needs_dirichlet"] == int(needs)
+
+
+@pytest.mark.parametrize("name", TABLE_MESHES)
+def test_coupling_pairs(tables, name):
+    e, r, _ = tables(name)
+    p_i, p_col, p_j = (e.array(p, e.o.n_pairs) for p in (e.o.p_i, e.o.p_col, e.o.p_j))
+    if name == "step":
+        assert len(p_i) > 0
+    # pos decodes to row p_i, and the column index there is p_j
+    pos = np.array(r["pair_pos"], dtype=np.int64)
+    assert np.array_equal(pos % WAVE, p_i % WAVE)
+    assert np.array_equal(pos // WAVE - e.slice_off[p_i // WAVE], p_col)
+    assert np.array_equal(e.cols[e.rs[p_i] + p_col], p_j)
+    # c_ji: the entry of row p_j whose column is p_i, found in the CSR arrays
+    transposed = np.array([e.rs[j] + np.flatnonzero(e.cols[e.rs[j]: e.rs[j + 1]] == i)[0] for i, j in zip(p_i, p_j)],
+                          dtype=np.int64)
+    assert np.array_equal(np.array(r["pair_cji"], dtype=np.uint64), _bits(e.cij[transposed]))
+
+
+@pytest.mark.parametrize("name", TABLE_MESHES)
+def test_lower_mask(tables, name):
+    e, r, _ = tables(name)
+    assert (r["n_slices"], r["rows_padded"], r["max_row_len"], r["nnz_sell"]) == \
+        (e.n_slices, e.rows_padded, e.max_row_len, e.nnz_sell)
+    mask = np.zeros(e.rows_padded, dtype=np.int64)
+    if e.max_row_len <= 32:
+        below = (e.rows < e.n_owned) & (e.c >= 1) & (e.cols < e.rows)
+        np.add.at(mask, e.rows[below], 1 << e.c[below])
+        assert mask[: e.n_owned].any()
+    else:
+        assert name == "wide"
+    assert np.array_equal(r["lower_mask"], mask)
+
+
+@pytest.mark.parametrize("name", TABLE_MESHES + ["step_2of3"])
+def test_export_slices(checker, meshes, name):
+    off, path = meshes(name)
+    e, r = Expected(off), _run(checker, "file", path, arrays=0)
+    assert r["n_export_slices"] == min(e.n_slices, -(-e.n_export // WAVE))
+    assert r["interior_rows_read_ghosts"] == 0   # on every rank of the partition: only export rows see ghost columns
+    if name == "step_1of3":
+        with_ghost = e.rows[(e.rows < e.n_owned) & (e.cols >= e.n_owned)]
+        lowered = int(with_ghost.min()) // WAVE * WAVE   # the slice of the first such row is an interior slice now
+        assert lowered < e.n_export
+        r = _run(checker, "file", path, arrays=0, n_export=lowered)
+        assert r["n_export_slices"] == lowered // WAVE and r["interior_rows_read_ghosts"] == 1
+
+
+@pytest.mark.parametrize("name, n_nbr", [("step", 0), ("step_0of3", 1), ("step_1of3", 2)])
+def test_exchange_tables(tables, name, n_nbr):
+    e, r, _ = tables(name)
+    assert r["n_nbr"] == e.o.n_nbr == n_nbr
+    if n_nbr == 0:
+        assert r["send_buffer_doubles"] == 0 and r["row_send_pos"] == [] and r["row_recv_off"] == []
+        return
+    send_off, recv_off, row_send_off = (e.array(p, n_nbr + 1) for p in (e.o.send_off, e.o.recv_off, e.o.row_send_off))
+    for key, want in (("nbr_rank", e.array(e.o.nbr_rank, n_nbr, np.int32)), ("send_off", send_off),
+                      ("recv_off", recv_off), ("row_send_off", row_send_off)):
+        assert np.array_equal(r[key], want), key
+    row, col = (e.array(p, row_send_off[-1]) for p in (e.o.row_send_row, e.o.row_send_col))
+    assert len(row) > 0 and np.array_equal(r["row_send_pos"], e.pos(row, col))
+    assert (recv_off[0], recv_off[-1]) == (e.n_owned, e.n_relevant)
+    assert np.array_equal(r["row_recv_off"], e.ghost_ptr[recv_off - e.n_owned])
+    K = e.dim + 2   # Euler: KP = 4 state components per row, 2 precomputed values
+    assert r["send_buffer_doubles"] == max(send_off[-1] * max((K + 1) // 2 * 2, 2), row_send_off[-1])
+
+
+@pytest.mark.parametrize("name", TABLE_MESHES)
+def test_bounds_stride_and_tail_queue(tables, name):
+    e, r, _ = tables(name)
+    least = max(e.rows_padded, e.n_relevant)
+    assert r["bounds_stride"] % WAVE == 0 and least <= r["bounds_stride"] < least + WAVE
+    assert r["tail_queue_columns"] == max(1, min(63, e.max_row_len - 1))
+
+
+@pytest.mark.parametrize("name, chunks", [("step", (0, 0, 5)), ("box", (0, XCD_CHUNK_3D, 5))])
+def test_xcd_chunk(checker, meshes, name, chunks):
+    """debug_xcd_chunk -1 / 0 / 5: off, the library's choice (3-D only), that many"""
+    path = meshes(name)[1]
+    assert tuple(_run(checker, "file", path, arrays=0, debug_xcd_chunk=v)["xcd_chunk"] for v in (-1, 0, 5)) == chunks
+
+
+def test_band_stride(checker, meshes):
+    """debug_band_stride -1 / 3 / 0: off, that many, from the mesh -- G = the lattice stride in slices, taken where the
+    mesh has at least G * kWavesPerBlock * 4 slices, in 2-D only."""
+    path = meshes("step")[1]   # lattice rows of 181 nodes: G = 3, 145 slices and more
+    assert [_run(checker, "file", path, arrays=0, debug_band_stride=v)["band_stride"] for v in (-1, 3, 0)] == [1, 3, 3]
+    r = _run(checker, "file", meshes("flat")[1], arrays=0)   # lattice rows of 201 nodes: G = 3, but 41 slices
+    assert r["n_slices"] == 41 < 3 * WAVES_PER_BLOCK * 4 and r["band_stride"] == 1
+    assert _run(checker, "file", meshes("box")[1], arrays=0)["band_stride"] == 1   # 3-D
+    assert _run(checker, "file", meshes("line")[1], arrays=0)["band_stride"] == 1
+
+
+def test_band_stride_of_the_bench_mesh(checker):
+    """mach3_step_2d(995): lattice rows of 2986 nodes, G = 47 (the figure the knob was measured with)"""
+    assert _run(checker, "mach3", 995, 1, 0, arrays=0)["band_stride"] == 47
+
+
+def test_system_shape(checker):
+    """(equation, dim, K, KP, NB, NPREC, RS) of the eleven Description / dimension pairs"""
+    assert _run(checker, "shape") == [
+        [capi.EQ_EULER, 1, 3, 4, 3, 2, 8], [capi.EQ_EULER, 2, 4, 4, 3, 2, 8], [capi.EQ_EULER, 3, 5, 6, 3, 2, 12],
+        [capi.EQ_SHALLOW_WATER, 1, 2, 2, 5, 2, 4], [capi.EQ_SHALLOW_WATER, 2, 3, 4, 5, 2, 4],
+        [capi.EQ_EULER_AEOS, 1, 3, 4, 4, 4, 8], [capi.EQ_EULER_AEOS, 2, 4, 4, 4, 4, 8],
+        [capi.EQ_EULER_AEOS, 3, 5, 6, 4, 4, 10],
+        [capi.EQ_SCALAR_CONSERVATION, 1, 1, 2, 2, 2, 0], [capi.EQ_SCALAR_CONSERVATION, 2, 1, 2, 2, 4, 0],
+        [capi.EQ_SCALAR_CONSERVATION, 3, 1, 2, 2, 6, 0]]
+
+
+# ------------------------------------------------------------------ refusals
+
+SCALAR = dict(equation=capi.EQ_SCALAR_CONSERVATION)
+CHECK, PAIRS, BOUNDARY = "check_create_arguments", "build_pair_tables", "build_boundary_tables"
+# (mesh, edits of the parameters / the offline data, status, part of the message, who refuses)
+REFUSALS = [
+    ("step", dict(equation=9), UNSUPPORTED, "unknown equation", CHECK),
+    ("line", dict(SCALAR, sc_flux=9), UNSUPPORTED, "unknown flux", CHECK),
+    ("line", dict(SCALAR, sc_flux=-1), UNSUPPORTED, "unknown flux", CHECK),
+    ("line", dict(SCALAR, sc_flux=capi.FLUX_KPP, dim=3), UNSUPPORTED, "KPP is only defined", CHECK),
+    ("line", dict(SCALAR, sc_random_entropies=1), UNSUPPORTED, "random entropies", CHECK),
+    ("step", SCALAR, UNSUPPORTED, "slip, no-slip and dynamic boundary conditions", CHECK),
+    ("line", dict(SCALAR, b_id0=capi.BC_NO_SLIP), UNSUPPORTED, "slip, no-slip and dynamic boundary conditions", CHECK),
+    ("line_dynamic", SCALAR, UNSUPPORTED, "slip, no-slip and dynamic boundary conditions", CHECK),
+    ("step", dict(equation=capi.EQ_EULER_AEOS, eos=9), UNSUPPORTED, "unknown equation of state", CHECK),
+    ("line_dynamic", dict(equation=capi.EQ_EULER_AEOS), UNSUPPORTED, "euler aeos: dynamic boundary conditions", CHECK),
+    ("box", dict(equation=capi.EQ_SHALLOW_WATER), UNSUPPORTED, "shallow water equations are defined for dim 1 and 2",
+     CHECK),
+    ("step", dict(dim=0), ARG, "dim must be 1, 2 or 3", CHECK),
+    ("step", dict(dim=4), ARG, "dim must be 1, 2 or 3", CHECK),
+    ("step", dict(limiter_iterations=5), ARG, "limiter iterations must be between [0,2]", CHECK),
+    ("step", dict(limiter_iterations=-1), ARG, "limiter iterations must be between [0,2]", CHECK),
+    ("step", dict(debug_pij_storage=3), ARG, "debug_pij_storage must be", CHECK),
+    ("line", dict(SCALAR, sc_flux=capi.FLUX_FUNCTION, sc_delta=0), ARG, "derivative approximation delta", CHECK),
+    ("line", dict(SCALAR, sc_flux=capi.FLUX_FUNCTION, sc_delta="nan"), ARG, "derivative approximation delta", CHECK),
+    ("line", dict(SCALAR, sc_flux=capi.FLUX_FUNCTION, sc_delta="inf"), ARG, "derivative approximation delta", CHECK),
+    ("line", dict(SCALAR, dg=1), UNSUPPORTED, "discontinuous ansatz with scalar conservation", CHECK),
+    ("step", dict(dg=1), ARG, "discontinuous ansatz without incidence", CHECK),
+    ("step_1of3", dict(have_comm=0), COMM, "neighbour ranks but no communicator", CHECK),
+    # precedence: the equation before dim, the flux before the limiter iterations
+    ("step", dict(equation=9, dim=7), UNSUPPORTED, "unknown equation", CHECK),
+    ("line", dict(SCALAR, sc_flux=9, limiter_iterations=5), UNSUPPORTED, "unknown flux", CHECK),
+    # the refusals that need the layout
+    ("step", dict(p_col0="other"), ARG, "coupling_boundary_pairs do not match", PAIRS),
+    ("step_1of3", dict(b_i0="ghost"), ARG, "boundary_map entry refers to a non-owned DoF", BOUNDARY),
+]
+
+
+@pytest.mark.parametrize("case", range(len(REFUSALS)))
+def test_refusals(checker, meshes, case):
+    name, edits, status, message, stage = REFUSALS[case]
+    off, path = meshes(name)
+    edits = dict(edits)
+    if edits.get("p_col0") == "other":   # another column of the same row
+        edits["p_col0"] = int(off.pairs[1][0]) % 2 + 1
+    if edits.get("b_i0") == "ghost":
+        assert off.n_relevant > off.n_owned
+        edits["b_i0"] = off.n_owned
+    r = _run(checker, "file", path, arrays=0, **edits)
+    assert r["status"] == status and message in r["message"] and r["stage"] == stage, r
+
+
+@pytest.mark.parametrize("name, edits", [("step", {}), ("step_1of3", {}), ("box", {}), ("wide", {}),
+                                         ("line", dict(SCALAR, sc_flux=capi.FLUX_FUNCTION)),
+                                         ("line", dict(equation=capi.EQ_SHALLOW_WATER)),
+                                         ("step", dict(equation=capi.EQ_EULER_AEOS, limiter_iterations=0))])
+def test_the_base_cases_are_accepted(checker, meshes, name, edits):
+    assert _run(checker, "file", meshes(name)[1], arrays=0, **edits)["status"] == 0
