@@ -61,13 +61,16 @@ enum {
  * (ryujin_hip_flux_configure_function below). Both form the gradient as (f(u + delta) - f(u - delta)) / (2 * delta). */
 enum { RYUJIN_FLUX_BURGERS = 0, RYUJIN_FLUX_KPP = 1, RYUJIN_FLUX_POLYNOMIAL = 2, RYUJIN_FLUX_FUNCTION = 3 };
 
-/* EquationOfStateLibrary (source/euler_aeos/equation_of_state_library.h): the closed-form members.
- * "sesame" (tabulated, needs EOSPAC) and "function" (muparser) are host-library bound and not offered. */
+/* EquationOfStateLibrary (source/euler_aeos/equation_of_state_library.h): the four closed-form members, and
+ * "function" (muparser in the reference): four expressions of the grammar table under "The function state" below,
+ * evaluated by the library's interpreter on the device (ryujin_hip_eos_configure_function below). "sesame"
+ * (tabulated, needs EOSPAC) is host-library bound and not offered. */
 enum {
   RYUJIN_EOS_POLYTROPIC_GAS = 0,             /* equation_of_state_polytropic_gas.h */
   RYUJIN_EOS_NOBLE_ABEL_STIFFENED_GAS = 1,   /* equation_of_state_noble_abel_stiffened_gas.h */
   RYUJIN_EOS_VAN_DER_WAALS = 2,              /* equation_of_state_van_der_waals.h */
-  RYUJIN_EOS_JONES_WILKINS_LEE = 3           /* equation_of_state_jones_wilkins_lee.h */
+  RYUJIN_EOS_JONES_WILKINS_LEE = 3,          /* equation_of_state_jones_wilkins_lee.h */
+  RYUJIN_EOS_FUNCTION = 4                    /* equation_of_state_function.h */
 };
 
 /* ryujin::Boundary (source/discretization.h:28-112) */
@@ -867,6 +870,58 @@ int ryujin_hip_flux_configure_function(ryujin_hip_ctx *ctx, const char *expressi
 int ryujin_hip_flux_function_evaluate(const char *expression, int dim, double delta, const double *u, size_t n,
                                       double *value, double *gradient);
 int ryujin_hip_flux_info(ryujin_hip_ctx *ctx, int *kind, int *n_instructions, int *step2_interpreted);
+
+/* ---- The function equation of state: EquationOfStateLibrary "function" of EulerAEOS ---- */
+/* source/euler_aeos/equation_of_state_function.h: FOUR expression strings,
+ *   which = 0   pressure                   in rho, e      default "(1.4 - 1.0) * rho * e"
+ *   which = 1   specific internal energy   in rho, p      default "p / (rho * (1.4 - 1.0))"
+ *   which = 2   temperature                in rho, e      default "e / 718."
+ *   which = 3   speed of sound             in rho, e      default "sqrt(1.4 * (1.4 - 1.0) * e)"
+ * and the three interpolation parameters of the surrogate (interpolatory covolume b, reference pressure, reference
+ * specific internal energy; default 0). The grammar is the table above with these variables: `e` and `p` are
+ * variables here, each in its own programs only, Euler's number stays `_e`; x, y, z, t and u are unknown identifiers
+ * (RYUJIN_ERR_ARG). The limits -- RYUJIN_EXPR_MAX_INSTRUCTIONS, RYUJIN_EXPR_MAX_STACK, nesting 64 -- hold per
+ * expression. ryujin_hip_last_error names the parameter ("pressure", ...) and the character, counted from 0 within
+ * that string. The reference checks no consistency between the four, and neither does the library. A context created
+ * with eos = RYUJIN_EOS_FUNCTION starts from the defaults.
+ *   eos_configure_function   valid on an EulerAEOS context created with any equation of state
+ *                            (RYUJIN_ERR_UNSUPPORTED for the other Descriptions, and for what the table refuses with
+ *                            that status); a NULL string is that function's default. RYUJIN_ERR_ARG: a parse error, a
+ *                            non-finite interpolation parameter. A refused call leaves the earlier equation of state
+ *                            in place. It waits for the stream and takes effect at the next prepare_state_vector; on
+ *                            several ranks every rank's context is configured by its own call. The surrogate
+ *                            (gamma, the Riemann records, the indicator, the bounds, the limiter) reads the three
+ *                            interpolation parameters given here.
+ *                            On the device the pressure program runs once per node in cycle 0 of the precomputation
+ *                            (a kernel of its own); everything behind the precomputed pressure is the code of the
+ *                            closed-form members. The analytic initial and Dirichlet states
+ *                            (ryujin_hip_initial_values_configure) take specific_internal_energy(rho, p) from the sie
+ *                            program: a state configured BEFORE this call is switched over by it, one configured
+ *                            afterwards sees it -- both orders give the same values. The function state
+ *                            (configure_function above) needs no equation of state.
+ *                            NOTHING in the update, or in any feature of this library, reads temperature or speed of
+ *                            sound: they are parsed and checked, and eos_function_evaluate_device is their only use
+ *                            on the device.
+ *   eos_function_evaluate    needs no context and no device: out[i] = expression(rho[i], second[i]) with the host
+ *                            interpreter, read with the variables of function `which`; expression = NULL: the
+ *                            default. n = 0 returns RYUJIN_OK and writes nothing.
+ *   eos_function_evaluate_device   program `which` of the context's configured function equation of state at n
+ *                            host points through the device interpreter (RYUJIN_ERR_ARG if the context runs a
+ *                            closed-form member).
+ *   eos_info                 what the latest prepare_state_vector ran, from host values (before the first one: what
+ *                            the next would run, precompute_interpreted = 0): kind = RYUJIN_EOS_*, n_instructions[4]
+ *                            (0 unless the function equation of state), precompute_interpreted = 1 if cycle 0 ran the
+ *                            interpreter kernel. Any of the three pointers may be NULL.
+ * ryujin_hip_debug_function with RYUJIN_DEBUG_AEOS_DIJ_2D / _RECORDS_2D forms p from a closed-form member inside its
+ * kernel: with eos = RYUJIN_EOS_FUNCTION it returns RYUJIN_ERR_UNSUPPORTED. */
+int ryujin_hip_eos_configure_function(ryujin_hip_ctx *ctx, const char *pressure, const char *specific_internal_energy,
+                                      const char *temperature, const char *speed_of_sound, double interpolation_b,
+                                      double interpolation_pinfty, double interpolation_q);
+int ryujin_hip_eos_function_evaluate(int which, const char *expression, const double *rho, const double *second,
+                                     size_t n, double *out);
+int ryujin_hip_eos_function_evaluate_device(ryujin_hip_ctx *ctx, int which, const double *rho, const double *second,
+                                            size_t n, double *out);
+int ryujin_hip_eos_info(ryujin_hip_ctx *ctx, int *kind, int *n_instructions, int *precompute_interpreted);
 
 /* ---- Error norms: analytic-solution error of a verification run, device resident -- */
 /* The norms of TimeLoop::compute_error() of the reference (source/time_loop.template.h:692-833) between the state

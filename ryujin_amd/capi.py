@@ -22,6 +22,9 @@ RYUJIN_ERR_TAU, RYUJIN_ERR_ARG, RYUJIN_ERR_HIP, RYUJIN_ERR_COMM, RYUJIN_ERR_UNSU
 EQ_EULER, EQ_SHALLOW_WATER, EQ_EULER_AEOS, EQ_SCALAR_CONSERVATION = 0, 1, 2, 3
 FLUX_BURGERS, FLUX_KPP, FLUX_POLYNOMIAL, FLUX_FUNCTION = 0, 1, 2, 3
 EOS_POLYTROPIC_GAS, EOS_NOBLE_ABEL_STIFFENED_GAS, EOS_VAN_DER_WAALS, EOS_JONES_WILKINS_LEE = 0, 1, 2, 3
+EOS_FUNCTION = 4  # four expressions (ryujin_hip_eos_configure_function)
+# the programs of the function equation of state, the `which` of eos_function_evaluate
+EOS_PRESSURE, EOS_SPECIFIC_INTERNAL_ENERGY, EOS_TEMPERATURE, EOS_SPEED_OF_SOUND = 0, 1, 2, 3
 BC_DO_NOTHING, BC_PERIODIC, BC_SLIP, BC_NO_SLIP, BC_DIRICHLET, BC_DYNAMIC, BC_DIRICHLET_MOMENTUM = range(7)
 IDV_WARN, IDV_RAISE_EXCEPTION = 0, 1
 CUT_NONE, CUT_BOX, CUT_CYLINDER = 0, 1, 2
@@ -245,6 +248,29 @@ def flux_function_evaluate(expr: str, dim: int, u, delta: float = 1e-10, gradien
     return value, grad
 
 
+def eos_function_evaluate(which: int, expr, rho, second) -> np.ndarray:
+    """[n]: function `which` (EOS_PRESSURE, ...) of the function equation of state given as the expression `expr`
+    (None: the reference's default) at (rho [n], second [n]) -- second is e, or p for the specific internal energy --
+    through the library's host interpreter (ryujin_hip_eos_function_evaluate; no device). RuntimeError with .status
+    for a refused expression."""
+    lib = load_hip()
+    rho = np.ascontiguousarray(rho, dtype=np.float64).reshape(-1)
+    second = np.ascontiguousarray(second, dtype=np.float64).reshape(-1)
+    if rho.size != second.size:
+        raise ValueError("rho and the second variable take the same number of points")
+    out = np.zeros(rho.size, dtype=np.float64)
+    rc = lib.ryujin_hip_eos_function_evaluate(int(which), None if expr is None else str(expr).encode(),
+                                              as_ptr(rho, c_double_p) if rho.size else None,
+                                              as_ptr(second, c_double_p) if rho.size else None, rho.size,
+                                              as_ptr(out, c_double_p) if rho.size else None)
+    if rc < 0:
+        error = RuntimeError(f"ryujin_hip_eos_function_evaluate failed with status {rc}: "
+                             f"{lib.ryujin_hip_last_error().decode()}")
+        error.status = rc
+        raise error
+    return out
+
+
 def component_names(equation: int, dim: int) -> tuple[tuple[str, ...], tuple[str, ...]]:
     """(View::component_names, View::primitive_component_names) of a Description
     (source/<eq>/hyperbolic_system.h)."""
@@ -369,6 +395,8 @@ HIP_SYMBOLS = [
     "ryujin_hip_initial_values_configure_function", "ryujin_hip_expression_evaluate",
     "ryujin_hip_error_norms_configure", "ryujin_hip_error_norms_compute",
     "ryujin_hip_flux_configure_function", "ryujin_hip_flux_function_evaluate", "ryujin_hip_flux_info",
+    "ryujin_hip_eos_configure_function", "ryujin_hip_eos_function_evaluate",
+    "ryujin_hip_eos_function_evaluate_device", "ryujin_hip_eos_info",
 ]
 
 
@@ -489,5 +517,12 @@ def load_hip():
         lib.ryujin_hip_flux_function_evaluate.argtypes = [C.c_char_p, C.c_int, C.c_double, c_double_p, C.c_size_t,
                                                           c_double_p, c_double_p]
         lib.ryujin_hip_flux_info.argtypes = [vp, c_int_p, c_int_p, c_int_p]
+        lib.ryujin_hip_eos_configure_function.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
+                                                          C.c_double, C.c_double, C.c_double]
+        lib.ryujin_hip_eos_function_evaluate.argtypes = [C.c_int, C.c_char_p, c_double_p, c_double_p, C.c_size_t,
+                                                         c_double_p]
+        lib.ryujin_hip_eos_function_evaluate_device.argtypes = [vp, C.c_int, c_double_p, c_double_p, C.c_size_t,
+                                                                c_double_p]
+        lib.ryujin_hip_eos_info.argtypes = [vp, c_int_p, c_int_p, c_int_p]
         _hip = lib
     return _hip

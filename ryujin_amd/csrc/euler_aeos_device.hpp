@@ -12,6 +12,7 @@
 #pragma once
 
 #include "euler_device.hpp"
+#include "expression.hpp"
 #include "ryujin_hip.h"
 
 namespace ryujin_hip
@@ -806,4 +807,40 @@ namespace ryujin_hip
       }
     }
   };
+
+  /* ================================================================ EquationOfStateLibrary "function" */
+  /* The equation of state as four expressions (expression.hpp: eos_compile), evaluated by the interpreter the function
+   * initial state and the function flux use: the programs through a const __restrict__ argument at wave-uniform
+   * indices (scalar loads), the operand stack a [slot][lane] column of LDS. Kernels of their own with one wave per
+   * block (k_precompute_aeos0_function in kernels_euler_aeos.hpp, the analytic states in kernels_initial_values.hpp):
+   * the closed-form kernels keep their registers and take no LDS. EVERY lane of a wave runs the interpreter, a lane
+   * without work on finite arguments, and stores nothing. */
+
+  constexpr int kEosFunctionBlock = 64;
+
+  constexpr int eos_function_lds_doubles(const int block)
+  {
+    return RYUJIN_EXPR_MAX_STACK * block;
+  }
+
+  template <int BLOCK>
+  struct EosLdsStack {
+    double *column; /* &lds[thread] */
+    RYUJIN_DEV double load(const int slot) const { return column[slot * BLOCK]; }
+    RYUJIN_DEV void store(const int slot, const double value) { column[slot * BLOCK] = value; }
+  };
+
+  struct EosDevicePow {
+    RYUJIN_DEV double operator()(const double a, const double b) const { return dev_pow(a, b); }
+  };
+
+  /* program `which` (EosFunction, wave-uniform) at (rho, second): second is e, or p for the specific internal energy */
+  template <int BLOCK>
+  RYUJIN_DEV double eos_function_value(const EosProgram *__restrict__ F, const int which, const double rho,
+                                       const double second, double *column)
+  {
+    EosLdsStack<BLOCK> stack{column};
+    const int begin = F->offset[which];
+    return expr_evaluate(F->code + begin, F->offset[which + 1] - begin, rho, second, 0., 0., stack, EosDevicePow{});
+  }
 } // namespace ryujin_hip

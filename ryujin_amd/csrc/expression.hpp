@@ -7,7 +7,10 @@
 // runs on the host (ryujin_hip_expression_evaluate, tests/cpp/expression_cases.cc) and on the device
 // (initial_states_device.hpp). The flux of the scalar conservation equation (FluxLibrary "function", one string in the
 // variable u with a component per direction) is its second consumer: flux_compile() and flux_evaluate_points() at the
-// end of this file, the kernels in scalar_conservation_device.hpp. Host standard library only -- no HIP, no context. Under hipcc RYUJIN_EXPR_HD makes the
+// end of this file, the kernels in scalar_conservation_device.hpp. The equation of state "function" of EulerAEOS
+// (EquationOfStateLibrary, four strings in rho and e, or rho and p) is the third: eos_compile() and
+// eos_evaluate_points() behind the flux, the kernels in kernels_euler_aeos.hpp and kernels_initial_values.hpp.
+// Host standard library only -- no HIP, no context. Under hipcc RYUJIN_EXPR_HD makes the
 // interpreter a host and device function; the parser is host code.
 //
 // The interpreter keeps the top of the operand stack in a register and everything below it behind a `Stack`
@@ -730,6 +733,104 @@ namespace ryujin_hip
       for (int d = 0; d < dim; ++d)
         gradient[i * (size_t)dim + d] = (plus[d] - stack.load(RYUJIN_EXPR_MAX_STACK + d)) / (2 * delta);
     }
+  }
+
+  /* ---- the equation of state of EulerAEOS: EquationOfStateLibrary "function" -------------------------------------- */
+
+  /* source/euler_aeos/equation_of_state_function.h: FOUR strings, pressure(rho, e), specific internal energy(rho, p),
+   * temperature(rho, e) and speed of sound(rho, e). Here `e` and `p` are variables (Euler's number stays `_e`); x, y,
+   * z, t and u are unknown identifiers. Slot 0 is rho, slot 1 the second variable. */
+  inline ExprVariables expr_variables_rho_e()
+  {
+    static const char *const names[2] = {"rho", "e"};
+    return ExprVariables{names, 2, 0};
+  }
+
+  inline ExprVariables expr_variables_rho_p()
+  {
+    static const char *const names[2] = {"rho", "p"};
+    return ExprVariables{names, 2, 0};
+  }
+
+  constexpr int kEosPrograms = 4;
+  enum EosFunction : int { kEosPressure = 0, kEosSpecificInternalEnergy = 1, kEosTemperature = 2, kEosSpeedOfSound = 3 };
+
+  inline const char *eos_function_name(const int which)
+  {
+    static const char *const names[kEosPrograms] = {"pressure", "specific internal energy", "temperature",
+                                                    "speed of sound"};
+    return names[which];
+  }
+
+  /* the reference's defaults (equation_of_state_function.h:32-53): the polytropic gas with 1.4 */
+  inline const char *eos_function_default(const int which)
+  {
+    static const char *const defaults[kEosPrograms] = {"(1.4 - 1.0) * rho * e", "p / (rho * (1.4 - 1.0))", "e / 718.",
+                                                       "sqrt(1.4 * (1.4 - 1.0) * e)"};
+    return defaults[which];
+  }
+
+  inline ExprVariables eos_function_variables(const int which)
+  {
+    return which == kEosSpecificInternalEnergy ? expr_variables_rho_p() : expr_variables_rho_e();
+  }
+
+  /* The four programs back to back, program w in code[offset[w], offset[w + 1]): a kernel runs only the one it needs,
+   * whose value is what expr_evaluate returns (no kExResult closers). The same for every lane of a wave. */
+  struct EosProgram {
+    int offset[kEosPrograms + 1];
+    int pad[3];
+    ExprInstruction code[kEosPrograms * RYUJIN_EXPR_MAX_INSTRUCTIONS];
+    int n_instructions(const int which) const { return offset[which + 1] - offset[which]; }
+  };
+
+  /* `expressions[w]` (NULL: the reference's default for that function) -> `program`; kExprOk or the refusal, whose
+   * message names the parameter and the character position within that string. The limits (instructions, operands,
+   * nesting) hold per expression. The three interpolation parameters of the surrogate must be finite. */
+  inline int eos_compile(const char *const expressions[kEosPrograms], const double interpolation_b,
+                         const double interpolation_pinfty, const double interpolation_q, EosProgram &program,
+                         std::string &error)
+  {
+    for (int w = 0; w <= kEosPrograms; ++w)
+      program.offset[w] = 0;
+    program.pad[0] = program.pad[1] = program.pad[2] = 0;
+    if (!std::isfinite(interpolation_b) || !std::isfinite(interpolation_pinfty) || !std::isfinite(interpolation_q)) {
+      error = std::string("eos: interpolatory ") +
+              (!std::isfinite(interpolation_b) ? "covolume b"
+                                               : (!std::isfinite(interpolation_pinfty)
+                                                      ? "reference pressure"
+                                                      : "reference specific internal energy")) +
+              " is not finite";
+      return kExprErrArg;
+    }
+    ExprProgram *one = new ExprProgram;
+    int status = kExprOk;
+    for (int w = 0; w < kEosPrograms; ++w) {
+      const char *text = expressions && expressions[w] ? expressions[w] : eos_function_default(w);
+      std::string message;
+      status = ExprParser(text, 1, *one, eos_function_variables(w)).compile(message);
+      if (status != kExprOk) {
+        error = std::string("eos: ") + eos_function_name(w) + ": " + message;
+        break;
+      }
+      for (int i = 0; i < one->n; ++i)
+        program.code[program.offset[w] + i] = one->code[i];
+      program.offset[w + 1] = program.offset[w] + one->n;
+    }
+    delete one;
+    return status;
+  }
+
+  /* out[i] = program `which` at (rho[i], second[i]) with the host's library; second is e, or p for the specific
+   * internal energy */
+  inline void eos_evaluate_points(const EosProgram &program, const int which, const double *rho, const double *second,
+                                  const size_t n, double *out)
+  {
+    ExprHostStack stack;
+    const ExprInstruction *code = program.code + program.offset[which];
+    const int n_instructions = program.n_instructions(which);
+    for (size_t i = 0; i < n; ++i)
+      out[i] = expr_evaluate(code, n_instructions, rho[i], second[i], 0., 0., stack, ExprHostPow{});
   }
 } // namespace ryujin_hip
 

@@ -72,7 +72,7 @@ namespace ryujin_hip
                                                  "unavailable for scalar conservation equations");
     }
     if (p.equation == RYUJIN_EQ_EULER_AEOS) {
-      if (p.eos < RYUJIN_EOS_POLYTROPIC_GAS || p.eos > RYUJIN_EOS_JONES_WILKINS_LEE)
+      if (p.eos < RYUJIN_EOS_POLYTROPIC_GAS || p.eos > RYUJIN_EOS_FUNCTION)
         throw HipError(RYUJIN_ERR_UNSUPPORTED, "unknown equation of state");
       for (uint32_t b = 0; b < o.n_bdry; ++b)
         if (o.b_id[b] == RYUJIN_BC_DYNAMIC) /* __builtin_trap() in euler_aeos/hyperbolic_system.h:1337 */

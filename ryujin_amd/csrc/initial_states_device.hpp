@@ -345,6 +345,36 @@ namespace ryujin_hip
     }
   }
 
+  /* initial_state<EulerAeos<DIM>>() on a context whose equation of state is the "function" one: from_initial_state
+   * takes specific_internal_energy(rho, p) from the sie program of the interpreter (eos_function_value), everything
+   * else is the statements above on the same operands. Every lane of the wave calls it, a lane without a point with
+   * active = false: its interpreter runs on (1, 1) and the caller stores nothing. */
+  template <int DIM, int BLOCK>
+  RYUJIN_DEV void initial_state_eos_function(const InitialValuesParams &P, const EosProgram *__restrict__ F,
+                                             const double (&x_in)[DIM], const double t, const bool active,
+                                             double *column, double (&U)[DIM + 2])
+  {
+    double x[DIM];
+    iv_transform_point<DIM>(P, x_in, x);
+    const IvPrimitive s = iv_euler_primitive<DIM>(P, x, t);
+    const double sie = eos_function_value<BLOCK>(F, kEosSpecificInternalEnergy, active ? s.rho : 1.,
+                                                 active ? s.p : 1., column);
+    double m[DIM];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      m[d] = 0.;
+    m[0] = s.rho * s.v1;
+    if constexpr (DIM >= 2)
+      m[1] = s.rho * s.v2;
+    const double E_total = s.rho * sie + 0.5 * s.rho * (s.v1 * s.v1 + s.v2 * s.v2);
+    iv_transform_vector<DIM>(P, m);
+    U[0] = s.rho;
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      U[1 + d] = m[d];
+    U[1 + DIM] = E_total;
+  }
+
   /* ---- configuration = function: one expression in (x, t) per primitive component -------------------------- */
 
   constexpr int kIvMaxExpressions = 5; /* Euler, dim = 3: density, three velocities, pressure */

@@ -40,6 +40,61 @@ namespace ryujin_hip
     gamma[i] = rr[2]; /* once more as a dense vector: cycle 1 gathers it over the stencil */
   }
 
+  /* cycle 0 with the "function" equation of state: p_i from the pressure program of the interpreter
+   * (eos_function_value, euler_aeos_device.hpp), everything behind it the statements of k_precompute_aeos0 on the same
+   * operands. One wave per block and slice; a lane without a row runs the interpreter on the state (1, 0, 1). */
+  template <int DIM, bool WITH_BC>
+  __global__ void __launch_bounds__(kEosFunctionBlock)
+  k_precompute_aeos0_function(const EulerAeosParams P, const DeviceMesh M, const BcFold B,
+                              const EosProgram *__restrict__ F, double *U, double *__restrict__ prec,
+                              double *__restrict__ rec, double *__restrict__ gamma)
+  {
+    using E = EulerAeos<DIM>;
+    constexpr int K = E::K, RS = E::RS;
+    __shared__ double lds[eos_function_lds_doubles(kEosFunctionBlock)];
+    const uint32_t i = (M.slice_begin + blockIdx.x) * 64 + threadIdx.x;
+    bool active = i < M.n_owned && i < M.slice_end * 64;
+    if (active) {
+      if constexpr (WITH_BC)
+        apply_bc_row<E>(P, B, i, U);
+      active = M.row_len[i] != 1;
+    }
+    double U_i[K], rr[RS];
+    if (active) {
+      load_state<K>(U, i, U_i);
+    } else {
+#pragma unroll
+      for (int q = 0; q < K; ++q)
+        U_i[q] = q == 0 || q == K - 1 ? 1. : 0.;
+    }
+    const double rho_i = U_i[0];
+    const double e_i = E::internal_energy(U_i) / rho_i;
+    const double p_i = eos_function_value<kEosFunctionBlock>(F, kEosPressure, rho_i, e_i, lds + threadIdx.x);
+    if (!active)
+      return;
+    const typename E::Prec prec_i{p_i, E::surrogate_gamma(P, U_i, p_i), 0., 0.};
+    E::store_prec(prec, i, prec_i);
+    E::riemann_record(P, U_i, prec_i.p, rr);
+#pragma unroll
+    for (int g = 0; g < RS; ++g)
+      rec[(size_t)i * RS + g] = rr[g];
+    gamma[i] = rr[2];
+  }
+
+  /* ryujin_hip_eos_function_evaluate_device: program `which` at n points */
+  __global__ void __launch_bounds__(kEosFunctionBlock)
+  k_eos_function_points(const EosProgram *__restrict__ F, const int which, const uint32_t n,
+                        const double *__restrict__ rho, const double *__restrict__ second, double *__restrict__ out)
+  {
+    __shared__ double lds[eos_function_lds_doubles(kEosFunctionBlock)];
+    const uint32_t i = blockIdx.x * (uint32_t)kEosFunctionBlock + threadIdx.x;
+    const bool active = i < n;
+    const double value = eos_function_value<kEosFunctionBlock>(F, which, active ? rho[i] : 1., active ? second[i] : 1.,
+                                                               lds + threadIdx.x);
+    if (active)
+      out[i] = value;
+  }
+
   /* Riemann records of the ghost rows, from the exchanged ghost states and pressures (functions of (U_j, p_j)
    * alone): behind the exchange of the precomputed values of cycle 0, on the stream of the exchange */
   template <int DIM>

@@ -151,4 +151,67 @@ namespace ryujin_hip
     for (int q = 0; q < K; ++q)
       dirichlet[(size_t)e * K + q] = U[q];
   }
+
+  /* k_initial_values_points and k_initial_values_dirichlet for the analytic EulerAEOS states on a context with the
+   * "function" equation of state (initial_state_eos_function): the sie program through the interpreter, kernels of
+   * their own for the reasons above */
+  template <int DIM>
+  __global__ __launch_bounds__(kInitialValuesBlock) void k_initial_values_eos_function_points(
+      const InitialValuesParams P, const EosProgram *__restrict__ program, const uint32_t n,
+      const double *__restrict__ positions, const double t, const int stride, double *__restrict__ out)
+  {
+    constexpr int K = DIM + 2;
+    __shared__ double lds[eos_function_lds_doubles(kInitialValuesBlock)];
+    const uint32_t i = blockIdx.x * (uint32_t)kInitialValuesBlock + threadIdx.x;
+    const bool active = i < n;
+    double x[DIM];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      x[d] = active ? positions[(size_t)i * DIM + d] : 0.;
+    double U[K];
+    initial_state_eos_function<DIM, kInitialValuesBlock>(P, program, x, t, active, lds + threadIdx.x, U);
+    if (!active)
+      return;
+#pragma unroll
+    for (int q = 0; q < K; ++q)
+      out[(size_t)i * stride + q] = U[q];
+    for (int q = K; q < stride; ++q) /* the pad lane of an odd state, as state_upload leaves it */
+      out[(size_t)i * stride + q] = 0.;
+  }
+
+  template <int DIM>
+  __global__ __launch_bounds__(kInitialValuesBlock) void k_initial_values_eos_function_dirichlet(
+      const InitialValuesParams P, const EosProgram *__restrict__ program, const uint32_t n_bdry,
+      const double *__restrict__ b_positions, const uint8_t *__restrict__ b_id, const double t, const double c,
+      const DeviceScalars *__restrict__ scalars, double *__restrict__ dirichlet)
+  {
+    constexpr int K = DIM + 2;
+    __shared__ double lds[eos_function_lds_doubles(kInitialValuesBlock)];
+    const uint32_t e = blockIdx.x * (uint32_t)kInitialValuesBlock + threadIdx.x;
+    bool active = e < n_bdry;
+    if (active) {
+      const int id = b_id[e];
+      active = id == RYUJIN_BC_DIRICHLET || id == RYUJIN_BC_DYNAMIC || id == RYUJIN_BC_DIRICHLET_MOMENTUM;
+    }
+    double time = t;
+    if (c != 0.) {
+      /* as k_initial_values_dirichlet */
+      double tau = scalars->tau_rk;
+      if (!(tau > 0.) || isinf(tau))
+        tau = 0.;
+      const double increment = c * tau;
+      time = t + increment;
+    }
+    double x[DIM];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      x[d] = active ? b_positions[(size_t)e * DIM + d] : 0.;
+    double U[K];
+    initial_state_eos_function<DIM, kInitialValuesBlock>(P, program, x, time, active, lds + threadIdx.x, U);
+    if (!active)
+      return;
+#pragma unroll
+    for (int q = 0; q < K; ++q)
+      dirichlet[(size_t)e * K + q] = U[q];
+  }
 } // namespace ryujin_hip

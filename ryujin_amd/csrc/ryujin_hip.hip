@@ -369,6 +369,12 @@ struct ryujin_hip_ctx {
   int flux_n_instructions = 0;
   int last_flux_kind = -1, last_flux_n_instructions = 0, last_step2_interpreted = 0;
   bool flux_interpreted_pairs() const { return scparams.flux == RYUJIN_FLUX_FUNCTION && scparams.use_averaged_entropy; }
+  /* RYUJIN_EOS_FUNCTION (ryujin_hip_eos_configure_function): the four programs of the equation of state, and what
+   * the latest prepare_state_vector ran (ryujin_hip_eos_info; host values) */
+  DeviceBuffer<EosProgram> d_eos_function;
+  int eos_n_instructions[kEosPrograms] = {0, 0, 0, 0};
+  int last_eos_kind = -1, last_eos_n_instructions[kEosPrograms] = {0, 0, 0, 0}, last_precompute_interpreted = 0;
+  void set_eos_function(const EosProgram &program, double b, double pinf, double q);
   DeviceBuffer<double> d_Z; /* initial_precomputed (bathymetry), shallow water only */
 
   template <typename E>
@@ -773,6 +779,16 @@ void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params
   }
   scparams.evc_factor = p.indicator_evc_factor;
   scparams.lim_relaxation_factor = p.limiter_relaxation_factor;
+
+  if (p.equation == RYUJIN_EQ_EULER_AEOS && p.eos == RYUJIN_EOS_FUNCTION) {
+    /* the defaults of equation_of_state_function.h:32-53 (the polytropic gas with 1.4, interpolation parameters 0),
+     * until ryujin_hip_eos_configure_function replaces them */
+    auto program = std::make_unique<EosProgram>();
+    std::string error;
+    if (const int status = eos_compile(nullptr, 0., 0., 0., *program, error))
+      throw HipError(status, error);
+    set_eos_function(*program, 0., 0., 0.);
+  }
 
   swparams = make_sw_params(p);
   if (p.equation == RYUJIN_EQ_SHALLOW_WATER) {
@@ -1184,6 +1200,22 @@ void ryujin_hip_ctx::exchange_matrix(double *m, bool after_split_sweep)
   end_exchange();
 }
 
+/* the caller has waited for the streams: nothing enqueued may still read the earlier programs */
+void ryujin_hip_ctx::set_eos_function(const EosProgram &program, const double b, const double pinf, const double q)
+{
+  d_eos_function.upload(&program, 1);
+  for (int w = 0; w < kEosPrograms; ++w)
+    eos_n_instructions[w] = program.n_instructions(w);
+  aeosparams.eos = RYUJIN_EOS_FUNCTION;
+  aeosparams.b = b;
+  aeosparams.pinf = pinf;
+  aeosparams.q = q;
+  iv.eos = RYUJIN_EOS_FUNCTION; /* an analytic state configured earlier goes through the sie program from now on */
+  for (auto &s : states)
+    if (s)
+      s->precomputed = false;
+}
+
 template <typename E>
 void ryujin_hip_ctx::store_pij_for_debug()
 {
@@ -1211,6 +1243,11 @@ void ryujin_hip_ctx::initial_values_points(const double *d_points, size_t n, dou
                        d_out);
   } else if constexpr (is_scalar_v<E>) {
     throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: scalar conservation has the function state only");
+  } else if (std::is_same<typename E::Params, EulerAeosParams>::value && aeosparams.eos == RYUJIN_EOS_FUNCTION) {
+    /* the analytic state through the sie program of the function equation of state */
+    hipLaunchKernelGGL(k_initial_values_eos_function_points<E::DIMENSION>, dim3(grid_for(n, kInitialValuesBlock)),
+                       dim3(kInitialValuesBlock), 0, stream, iv, d_eos_function.ptr, (uint32_t)n, d_points, t, stride,
+                       d_out);
   } else {
     hipLaunchKernelGGL(k_initial_values_points<E>, dim3(grid_for(n, kInitialValuesBlock)), dim3(kInitialValuesBlock),
                        0, stream, iv, (uint32_t)n, d_points, t, stride, d_out);
@@ -1238,6 +1275,14 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStag
       have_dirichlet = true;
     } else if constexpr (is_scalar_v<E>) {
       throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: scalar conservation has the function state only");
+    } else if (std::is_same<typename E::Params, EulerAeosParams>::value && aeosparams.eos == RYUJIN_EOS_FUNCTION) {
+      join_export();
+      hipLaunchKernelGGL(k_initial_values_eos_function_dirichlet<E::DIMENSION>,
+                         dim3(grid_for(bdry.n_bdry, kInitialValuesBlock)), dim3(kInitialValuesBlock), 0, stream, iv,
+                         d_eos_function.ptr, bdry.n_bdry, d_iv_b_positions.ptr, d_b_id.ptr, iv_stage.t, iv_stage.c,
+                         d_scalars.ptr, d_dirichlet.ptr);
+      HIP_CHECK(hipGetLastError());
+      have_dirichlet = true;
     } else {
       join_export();
       hipLaunchKernelGGL(k_initial_values_dirichlet<E>, dim3(grid_for(bdry.n_bdry, kInitialValuesBlock)),
@@ -1305,11 +1350,25 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStag
    * exchange of U hides behind the interior parts of the pre-pass and of step 2 */
   if constexpr (std::is_same<typename E::Params, EulerAeosParams>::value) {
     /* n_precomputation_cycles = 2 (euler_aeos/hyperbolic_system.h:433), ghost update after each */
+    const bool eos_function = eparams.eos == RYUJIN_EOS_FUNCTION;
+    last_eos_kind = eparams.eos;
+    last_precompute_interpreted = eos_function;
+    for (int w = 0; w < kEosPrograms; ++w)
+      last_eos_n_instructions[w] = eos_function ? eos_n_instructions[w] : 0;
     sweep([&](const DeviceMesh &mm, dim3 grid) {
-      with_bool(fold_bc, [&](auto fold) {
-        hipLaunchKernelGGL((k_precompute_aeos0<E::DIMENSION, decltype(fold)::value>), grid, block, 0, launch_stream,
-                           eparams, mm, bc, s.U.ptr, s.prec.ptr, s.rrec.ptr, d_gamma.ptr);
-      });
+      if (eos_function) {
+        /* the interpreter: a kernel of its own, one wave per block and slice */
+        const dim3 slices(mm.slice_end - mm.slice_begin), wave(kEosFunctionBlock);
+        with_bool(fold_bc, [&](auto fold) {
+          hipLaunchKernelGGL((k_precompute_aeos0_function<E::DIMENSION, decltype(fold)::value>), slices, wave, 0,
+                             launch_stream, eparams, mm, bc, d_eos_function.ptr, s.U.ptr, s.prec.ptr, s.rrec.ptr,
+                             d_gamma.ptr);
+        });
+      } else
+        with_bool(fold_bc, [&](auto fold) {
+          hipLaunchKernelGGL((k_precompute_aeos0<E::DIMENSION, decltype(fold)::value>), grid, block, 0, launch_stream,
+                             eparams, mm, bc, s.U.ptr, s.prec.ptr, s.rrec.ptr, d_gamma.ptr);
+        });
     });
     exchange_vector(s.U.ptr, KP, true);
     exchange_vector(s.prec.ptr, 4, true);
@@ -3469,6 +3528,11 @@ int ryujin_hip_debug_function(int device, const ryujin_hip_params *params, int w
     case RYUJIN_DEBUG_SW_DIJ_RECORDS_2D: n_in = 8; n_out = 1; break;
     default: throw HipError(RYUJIN_ERR_ARG, "unknown debug function");
     }
+    /* these two form p from the closed-form equation of state inside the kernel; the programs of the function one
+     * belong to a context */
+    if ((which == RYUJIN_DEBUG_AEOS_DIJ_2D || which == RYUJIN_DEBUG_AEOS_DIJ_RECORDS_2D) &&
+        params->eos == RYUJIN_EOS_FUNCTION)
+      throw HipError(RYUJIN_ERR_UNSUPPORTED, "debug function: not offered with the function equation of state");
     HIP_CHECK(hipSetDevice(device));
     DeviceBuffer<double> din, dout;
     din.upload(in, n * n_in);
@@ -3890,7 +3954,8 @@ namespace
 
     const ryujin_hip_params &hp = ctx.params;
     if (eq == RYUJIN_EQ_EULER_AEOS) {
-      P.eos = hp.eos;
+      P.eos = ctx.aeosparams.eos; /* RYUJIN_EOS_FUNCTION after ryujin_hip_eos_configure_function: the kernels of the
+                                   * sie program run, no closed-form switch is reached with it */
       P.eos_gamma = hp.gamma;
       P.eos_b = hp.eos_covolume_b;
       P.eos_q = hp.eos_q;
@@ -4128,6 +4193,93 @@ int ryujin_hip_flux_info(ryujin_hip_ctx *ctx, int *kind, int *n_instructions, in
                             : (ctx->scparams.flux == RYUJIN_FLUX_FUNCTION ? ctx->flux_n_instructions : 0);
     if (step2_interpreted)
       *step2_interpreted = ran ? ctx->last_step2_interpreted : 0;
+    return RYUJIN_OK;
+  });
+}
+
+/* ---- EquationOfStateLibrary "function" of EulerAEOS ---- */
+
+int ryujin_hip_eos_configure_function(ryujin_hip_ctx *ctx, const char *pressure, const char *specific_internal_energy,
+                                      const char *temperature, const char *speed_of_sound, double interpolation_b,
+                                      double interpolation_pinfty, double interpolation_q)
+{
+  return guarded_ctx(ctx, [&]() {
+    if (ctx->params.equation != RYUJIN_EQ_EULER_AEOS)
+      throw HipError(RYUJIN_ERR_UNSUPPORTED, "eos: only EulerAEOS takes an equation of state");
+    /* everything that can be refused comes first: a refused call leaves the earlier equation of state in place */
+    const char *const expressions[kEosPrograms] = {pressure, specific_internal_energy, temperature, speed_of_sound};
+    auto program = std::make_unique<EosProgram>();
+    std::string error;
+    if (const int status =
+            eos_compile(expressions, interpolation_b, interpolation_pinfty, interpolation_q, *program, error))
+      throw HipError(status, error);
+    ctx->finish();
+    ctx->set_eos_function(*program, interpolation_b, interpolation_pinfty, interpolation_q);
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_eos_function_evaluate(int which, const char *expression, const double *rho, const double *second,
+                                     size_t n, double *out)
+{
+  return guarded([&]() {
+    if (which < 0 || which >= kEosPrograms)
+      throw HipError(RYUJIN_ERR_ARG, "eos_function_evaluate: which outside 0 .. 3");
+    if (n > 0 && (!rho || !second || !out))
+      throw HipError(RYUJIN_ERR_ARG, "eos_function_evaluate: null argument");
+    const char *expressions[kEosPrograms] = {nullptr, nullptr, nullptr, nullptr};
+    expressions[which] = expression; /* NULL: the default */
+    auto program = std::make_unique<EosProgram>();
+    std::string error;
+    if (const int status = eos_compile(expressions, 0., 0., 0., *program, error))
+      throw HipError(status, error);
+    eos_evaluate_points(*program, which, rho, second, n, out);
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_eos_function_evaluate_device(ryujin_hip_ctx *ctx, int which, const double *rho, const double *second,
+                                            size_t n, double *out)
+{
+  return guarded_ctx(ctx, [&]() {
+    if (ctx->params.equation != RYUJIN_EQ_EULER_AEOS)
+      throw HipError(RYUJIN_ERR_UNSUPPORTED, "eos: only EulerAEOS takes an equation of state");
+    if (ctx->aeosparams.eos != RYUJIN_EOS_FUNCTION)
+      throw HipError(RYUJIN_ERR_ARG, "eos: the function equation of state is not configured");
+    if (which < 0 || which >= kEosPrograms)
+      throw HipError(RYUJIN_ERR_ARG, "eos_function_evaluate_device: which outside 0 .. 3");
+    if (n == 0)
+      return RYUJIN_OK;
+    if (!rho || !second || !out || n > 0x7fffffffull)
+      throw HipError(RYUJIN_ERR_ARG, "eos_function_evaluate_device: bad argument");
+    DeviceBuffer<double> d_in, d_out;
+    d_in.alloc(2 * n, false);
+    d_out.alloc(n, false);
+    HIP_CHECK(hipMemcpyAsync(d_in.ptr, rho, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(d_in.ptr + n, second, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_eos_function_points, dim3(grid_for(n, kEosFunctionBlock)), dim3(kEosFunctionBlock), 0,
+                       ctx->stream, ctx->d_eos_function.ptr, which, (uint32_t)n, d_in.ptr, d_in.ptr + n, d_out.ptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, d_out.ptr, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_eos_info(ryujin_hip_ctx *ctx, int *kind, int *n_instructions, int *precompute_interpreted)
+{
+  return guarded_ctx(ctx, [&]() {
+    if (ctx->params.equation != RYUJIN_EQ_EULER_AEOS)
+      throw HipError(RYUJIN_ERR_UNSUPPORTED, "eos: only EulerAEOS takes an equation of state");
+    const bool ran = ctx->last_eos_kind >= 0;
+    const bool function = ctx->aeosparams.eos == RYUJIN_EOS_FUNCTION;
+    if (kind)
+      *kind = ran ? ctx->last_eos_kind : ctx->aeosparams.eos;
+    if (n_instructions)
+      for (int w = 0; w < kEosPrograms; ++w)
+        n_instructions[w] = ran ? ctx->last_eos_n_instructions[w] : (function ? ctx->eos_n_instructions[w] : 0);
+    if (precompute_interpreted)
+      *precompute_interpreted = ran ? ctx->last_precompute_interpreted : 0;
     return RYUJIN_OK;
   });
 }

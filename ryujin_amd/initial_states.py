@@ -99,9 +99,16 @@ def sw_circular_dam_break(positions, h_inner=2.5, h_outer=0.5, radius=2.5):
 
 def aeos_specific_internal_energy(params, rho, p):
     """EquationOfState::specific_internal_energy(rho, p) of the closed-form equations of state
-    (source/euler_aeos/equation_of_state_*.h), vectorised; `params` is a capi.Params."""
+    (source/euler_aeos/equation_of_state_*.h), vectorised; `params` is a capi.Params. With eos = capi.EOS_FUNCTION
+    the "specific internal energy" expression -- the Python attribute `eos_function_sie` of `params`, None or absent:
+    the reference's default -- goes through the library's host interpreter (capi.eos_function_evaluate)."""
     rho = np.asarray(rho, dtype=np.float64)
     p = np.asarray(p, dtype=np.float64)
+    if params.eos == capi.EOS_FUNCTION:
+        rho_b, p_b = np.broadcast_arrays(rho, p)
+        e = capi.eos_function_evaluate(capi.EOS_SPECIFIC_INTERNAL_ENERGY, getattr(params, "eos_function_sie", None),
+                                       rho_b, p_b)
+        return e.reshape(rho_b.shape)
     g = params.gamma
     if params.eos == capi.EOS_POLYTROPIC_GAS:
         return p / (rho * (g - 1.0))

@@ -320,6 +320,44 @@ class HyperbolicModule:
         self._check(self._f("flux_info")(self._ctx, C.byref(kind), C.byref(n), C.byref(interpreted)))
         return dict(kind=kind.value, n_instructions=n.value, step2_interpreted=interpreted.value)
 
+    # ------------------------------------------------- EquationOfStateLibrary "function" (device backend only)
+    def eos_configure_function(self, pressure=None, specific_internal_energy=None, temperature=None,
+                               speed_of_sound=None, interpolation_b: float = 0.0, interpolation_pinfty: float = 0.0,
+                               interpolation_q: float = 0.0) -> None:
+        """Switch an EulerAEOS module to the expression-defined equation of state "function"
+        (ryujin_hip_eos_configure_function): pressure(rho, e), specific internal energy(rho, p), temperature(rho, e)
+        and speed of sound(rho, e) as strings (None: the reference's default), and the three interpolation parameters
+        of the surrogate. The grammar is tabulated in include/ryujin_hip.h. Takes effect at the next
+        prepare_state_vector, and for an analytic initial state configured before or after this call; a refused call
+        (RuntimeError) leaves the earlier equation of state in place."""
+        texts = [None if e is None else str(e).encode()
+                 for e in (pressure, specific_internal_energy, temperature, speed_of_sound)]
+        self._check(self._f("eos_configure_function")(self._ctx, *texts, float(interpolation_b),
+                                                      float(interpolation_pinfty), float(interpolation_q)))
+
+    def eos_function_evaluate_device(self, which: int, rho, second) -> np.ndarray:
+        """[n]: program `which` (capi.EOS_PRESSURE, ...) of the configured function equation of state at (rho [n],
+        second [n]) through the device interpreter (ryujin_hip_eos_function_evaluate_device)"""
+        rho = np.ascontiguousarray(rho, dtype=np.float64).reshape(-1)
+        second = np.ascontiguousarray(second, dtype=np.float64).reshape(-1)
+        if rho.size != second.size:
+            raise ValueError("rho and the second variable take the same number of points")
+        out = np.zeros(rho.size, dtype=np.float64)
+        self._check(self._f("eos_function_evaluate_device")(
+            self._ctx, int(which), capi.as_ptr(rho, capi.c_double_p) if rho.size else None,
+            capi.as_ptr(second, capi.c_double_p) if rho.size else None, rho.size,
+            capi.as_ptr(out, capi.c_double_p) if rho.size else None))
+        return out
+
+    def eos_info(self) -> dict:
+        """What the latest prepare_state_vector ran (ryujin_hip_eos_info): kind (capi.EOS_*), n_instructions of the
+        four programs of the function equation of state, precompute_interpreted -- whether cycle 0 of the
+        precomputation ran the interpreter kernel."""
+        kind, interpreted = C.c_int(0), C.c_int(0)
+        n = (C.c_int * 4)()
+        self._check(self._f("eos_info")(self._ctx, C.byref(kind), n, C.byref(interpreted)))
+        return dict(kind=kind.value, n_instructions=tuple(n), precompute_interpreted=interpreted.value)
+
     def integrals(self, state: StateVector) -> np.ndarray:
         """sum_i m_i U_i over the owned DoFs of all ranks, computed on the device with a fixed
         summation order (ryujin_hip_state_integrals; device backend only)."""
