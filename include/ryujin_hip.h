@@ -969,6 +969,91 @@ int ryujin_hip_error_norms_configure(ryujin_hip_ctx *ctx, uint32_t n_cells, int 
 int ryujin_hip_error_norms_compute(ryujin_hip_ctx *ctx, int h_state, int h_analytic, int n_components,
                                    const int *components, int normalize, double out[3], double *detail);
 
+/* ---- VTUOutput: selected fields and level-set cell output, device resident ---- */
+/* VTUOutput::schedule_output() of the reference (source/vtu_output.template.h:80-205) up to the writer: the values of
+ * "vtu output quantities" at the nodes that go into a file -- all locally relevant nodes (output_full, :142-154) or
+ * the nodes of the cells a level set of "manifolds" cuts (output_levelsets, :156-201) -- formed and gathered on the
+ * device, so that one output moves [n_quantities][n_nodes] values over PCIe instead of the state vector. The file
+ * itself (VTK XML) is written by the caller (ryujin_amd/vtu_output.py).
+ *
+ * NAMES (source/selected_components_extractor.h:77-88, in this search order; ryujin_amd/csrc/output_selection.hpp):
+ *   1 View::component_names            the conserved state, read from U
+ *   2 View::primitive_component_names  to_primitive_state(U) as the Postprocessor block above forms it; a name that is
+ *                                      both ("rho", "h", "u") is the conserved component
+ *   3 View::precomputed_names          Euler "s", "eta_h"; EulerAEOS "p", "surrogate_gamma",
+ *                                      "surrogate_specific_entropy", "surrogate_harten_entropy"; shallow water "eta_m",
+ *                                      "h_star"; scalar conservation "f[_d]", "df[_d]": what
+ *                                      ryujin_hip_state_download_precomputed returns
+ *   4 View::initial_precomputed_names  shallow water "bathymetry" (the context's initial_precomputed); the other
+ *                                      Descriptions have none, so the name is unknown there
+ *   5 "alpha"                          ryujin_hip_get_alpha
+ *   6 the postprocessed fields, which the reference always appends (:119-123), by the names of
+ *     Postprocessor::component_names() (source/postprocessor.template.h:74-97) -- "schlieren_rho", "vorticity_v_1" --
+ *     for the quantities ryujin_hip_postprocess_configure holds WHEN output_configure IS CALLED; the normalised values
+ *     of ryujin_hip_postprocess_download(raw = 0)
+ * An unknown name is RYUJIN_ERR_ARG with the message of SelectedComponentsExtractor::check (:38-43):
+ *   Invalid component name: "<name>" is not a valid conserved/primitive/precomputed/initial component name.
+ *
+ * MANIFOLDS (:162-165): level-set expressions of the grammar table under "The function state" above in the variables
+ * x [y [z]] -- FunctionParser<dim>(expression) has no time, so `t` is an unknown identifier here (RYUJIN_ERR_ARG). The
+ * limits RYUJIN_EXPR_MAX_INSTRUCTIONS, RYUJIN_EXPR_MAX_STACK and nesting 64 hold per manifold; a refused manifold is
+ * reported as "manifold <index>: ... at character <position>" (counted from 0 within that string). A cell is selected
+ * if for SOME manifold one of its vertices has f >= -100 eps and one has f <= +100 eps, eps = DBL_EPSILON (:171-187; a
+ * NaN is neither). The level sets are evaluated at the nodes by the device interpreter: the arithmetic subset gives
+ * the bits of ryujin_hip_expression_evaluate, a library function differs from the host's by its few ulp (see the
+ * table), which can move a cell in or out only where a vertex value lies that close to +-100 eps.
+ *
+ *   output_configure  names [n_quantities]; positions [n_relevant * dim] of this rank's nodes, ghost rows included;
+ *                     the cells of this rank as ryujin_hip_error_norms_configure takes them (cell_dofs
+ *                     [n_cells][dofs_per_cell], indices < n_relevant, every cell on exactly ONE rank; the vertex order
+ *                     is the caller's and is kept); manifolds [n_manifolds], 0 for the full output only. Everything
+ *                     is copied. All that depends on the mesh and the manifolds alone is done HERE, once: the level
+ *                     sets at the nodes, the selected cells (ascending cell index), their nodes (ascending local
+ *                     index), the map to the new node numbers and the cells' connectivity in it. The lists are formed
+ *                     by an order-preserving compaction (ballots inside a block, block offsets from a scan in a launch
+ *                     of its own: no block waits for another) and are equal to numpy.flatnonzero of the flags. A second
+ *                     configure replaces the first, a refused one leaves the previous configuration in place. A rank
+ *                     with n_cells == 0, or none of whose cells is cut, is legal: the counts are 0.
+ *   output_info       the counts of the configure-time selection; either pointer may be NULL
+ *   output_selection  cell_ids [n_selected_cells] (positions in the caller's cell list), node_ids [n_selected_nodes]
+ *                     (local indices) and connectivity [n_selected_cells][dofs_per_cell] in the NEW numbering, i.e.
+ *                     indices into node_ids. Any pointer may be NULL.
+ *   output_levelset_values   out [n_relevant] = manifold `manifold` at the nodes as the device evaluated it (tests)
+ *   output_extract    out [n_quantities][n_nodes], n_nodes = n_relevant (levelsets == 0) or n_selected_nodes, as
+ *                     double (RYUJIN_OUT_FLOAT64) or float (RYUJIN_OUT_FLOAT32, what deal.II's writer stores: ONE IEEE
+ *                     conversion of the same device value, round to nearest, overflow to inf). One sweep over the
+ *                     output nodes forms all quantities: U is read once per node, to_primitive_state evaluated once.
+ *                     COLLECTIVE over the ranks of the context's communicator: it exchanges the ghost range of the
+ *                     state vector as ryujin_hip_postprocess_compute does (when a conserved or primitive name is
+ *                     requested) and, where the rank has ghost rows, fills the ghost range of alpha and of the
+ *                     postprocessed fields through the context's vector exchange; a rank without output nodes takes
+ *                     part in the exchanges and launches nothing else. It returns the values, so it waits for the
+ *                     stream. The precomputed names need a state vector that prepare_state_vector has run on -- the
+ *                     caller's duty, as for a step; the values are those of ryujin_hip_state_download_precomputed,
+ *                     ghost rows as that call returns them. What the context can tell: RYUJIN_ERR_ARG for a vector whose
+ *                     storage no prepare_state_vector (and no update that leaves the precomputed values behind) has
+ *                     touched since ryujin_hip_state_alloc; it cannot tell whether U was changed since (an upload, a
+ *                     sadd), nor which storage a Runge-Kutta step's swap of the handles left behind the handle.
+ *                     The postprocessed names need a ryujin_hip_postprocess_compute since the latest
+ *                     ryujin_hip_postprocess_configure, and that configuration to be the one output_configure saw.
+ * RYUJIN_ERR_ARG: n_quantities outside [1, RYUJIN_OUT_MAX_QUANTITIES], n_manifolds outside
+ * [0, RYUJIN_OUT_MAX_MANIFOLDS], an unknown name, a refused manifold (RYUJIN_ERR_UNSUPPORTED for what the table
+ * refuses with that status), a cell index >= n_relevant, NULL arrays with non-zero counts, any other entry before
+ * output_configure, levelsets != 0 with no manifold configured, an unknown precision, manifold or handle.
+ * RYUJIN_ERR_UNSUPPORTED: dofs_per_cell other than 2^dim (patches of higher-order elements, patch_order > 0 at
+ * :137-138, are not subdivided). ryujin_hip_offline carries no affine constraints, so
+ * AffineConstraints::distribute (:112) has no counterpart here. */
+#define RYUJIN_OUT_MAX_QUANTITIES 32
+#define RYUJIN_OUT_MAX_MANIFOLDS 8
+enum { RYUJIN_OUT_FLOAT32 = 0, RYUJIN_OUT_FLOAT64 = 1 };
+int ryujin_hip_output_configure(ryujin_hip_ctx *ctx, int n_quantities, const char *const *names,
+                                const double *positions, uint32_t n_cells, int dofs_per_cell,
+                                const uint32_t *cell_dofs, int n_manifolds, const char *const *manifolds);
+int ryujin_hip_output_info(ryujin_hip_ctx *ctx, uint32_t *n_selected_cells, uint32_t *n_selected_nodes);
+int ryujin_hip_output_selection(ryujin_hip_ctx *ctx, uint32_t *cell_ids, uint32_t *node_ids, uint32_t *connectivity);
+int ryujin_hip_output_levelset_values(ryujin_hip_ctx *ctx, int manifold, double *out);
+int ryujin_hip_output_extract(ryujin_hip_ctx *ctx, int h_state, int levelsets, int precision, void *out);
+
 #ifdef __cplusplus
 }
 #endif

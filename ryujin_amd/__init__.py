@@ -7,6 +7,7 @@ offline.py wraps the synthetic OfflineData generator.
 from . import capi  # noqa: F401
 from .module import HyperbolicModule, Restart, StateVector, TauError, TimeIntegrator  # noqa: F401
 from .offline import MeshSpec, SyntheticOffline  # noqa: F401
+from .vtu_output import VTUOutput  # noqa: F401
 
 __all__ = ["capi", "HyperbolicModule", "Restart", "StateVector", "TauError", "TimeIntegrator",
-           "MeshSpec", "SyntheticOffline"]
+           "MeshSpec", "SyntheticOffline", "VTUOutput"]

@@ -106,6 +106,8 @@ Q_INSTANTANEOUS, Q_TIME_AVERAGED, Q_SPACE_AVERAGED = 1, 2, 4
 Q_MAX_MANIFOLDS = 16
 Q_NONE_YET = 3
 EN_MAX_DOFS_PER_CELL, EN_MAX_POINTS, EN_MAX_COMPONENTS = 27, 64, 5
+OUT_MAX_QUANTITIES, OUT_MAX_MANIFOLDS = 32, 8
+OUT_FLOAT32, OUT_FLOAT64 = 0, 1
 
 
 class PostprocessQuantity(C.Structure):
@@ -287,6 +289,21 @@ def component_names(equation: int, dim: int) -> tuple[tuple[str, ...], tuple[str
     raise ValueError(f"unknown equation {equation}")
 
 
+def output_names(equation: int, dim: int) -> dict:
+    """The name tables of "vtu output quantities" (source/<eq>/hyperbolic_system.h): conserved, primitive, precomputed
+    and initial_precomputed names of a Description, as ryujin_amd/csrc/output_selection.hpp holds them."""
+    conserved, primitive = component_names(equation, dim)
+
+    def vec(name: str) -> tuple[str, ...]:
+        return (name,) if dim == 1 else tuple(f"{name}_{d + 1}" for d in range(dim))
+    precomputed = {EQ_EULER: ("s", "eta_h"),
+                   EQ_EULER_AEOS: ("p", "surrogate_gamma", "surrogate_specific_entropy", "surrogate_harten_entropy"),
+                   EQ_SHALLOW_WATER: ("eta_m", "h_star"),
+                   EQ_SCALAR_CONSERVATION: (*vec("f"), *vec("df"))}[equation]
+    initial = ("bathymetry",) if equation == EQ_SHALLOW_WATER else ()
+    return dict(conserved=conserved, primitive=primitive, precomputed=precomputed, initial_precomputed=initial)
+
+
 def resolve_component(equation: int, dim: int, name: str) -> tuple[int, int]:
     """(is_primitive, index) of a component name: the conserved names first, the primitive names second, as
     Postprocessor::prepare() (source/postprocessor.template.h:73-93); ValueError for an unknown name."""
@@ -397,6 +414,8 @@ HIP_SYMBOLS = [
     "ryujin_hip_flux_configure_function", "ryujin_hip_flux_function_evaluate", "ryujin_hip_flux_info",
     "ryujin_hip_eos_configure_function", "ryujin_hip_eos_function_evaluate",
     "ryujin_hip_eos_function_evaluate_device", "ryujin_hip_eos_info",
+    "ryujin_hip_output_configure", "ryujin_hip_output_info", "ryujin_hip_output_selection",
+    "ryujin_hip_output_levelset_values", "ryujin_hip_output_extract",
 ]
 
 
@@ -524,5 +543,11 @@ def load_hip():
         lib.ryujin_hip_eos_function_evaluate_device.argtypes = [vp, C.c_int, c_double_p, c_double_p, C.c_size_t,
                                                                 c_double_p]
         lib.ryujin_hip_eos_info.argtypes = [vp, c_int_p, c_int_p, c_int_p]
+        lib.ryujin_hip_output_configure.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), c_double_p, C.c_uint32, C.c_int,
+                                                    c_u32_p, C.c_int, C.POINTER(C.c_char_p)]
+        lib.ryujin_hip_output_info.argtypes = [vp, c_u32_p, c_u32_p]
+        lib.ryujin_hip_output_selection.argtypes = [vp, c_u32_p, c_u32_p, c_u32_p]
+        lib.ryujin_hip_output_levelset_values.argtypes = [vp, C.c_int, c_double_p]
+        lib.ryujin_hip_output_extract.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_void_p]
         _hip = lib
     return _hip

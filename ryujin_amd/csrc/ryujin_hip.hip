@@ -52,6 +52,7 @@
 #include "kernels_quantities.hpp"
 #include "kernels_initial_values.hpp"
 #include "kernels_error_norms.hpp"
+#include "kernels_output.hpp"
 
 using namespace ryujin_hip;
 
@@ -474,6 +475,23 @@ struct ryujin_hip_ctx {
   };
   std::unique_ptr<ErrorNorms> error_norms;
   void error_norms_compute(int h_state, int h_analytic, const ErrorNormsDesc &D, double *host_result);
+  /* VTUOutput (ryujin_hip_output_*, kernels_output.hpp): the requested quantities and everything the level sets select
+   * on this rank's cells -- computed once, in configure */
+  struct Output {
+    OutputDesc desc{}; /* kinds and indices; the columns are filled in per output */
+    bool needs_precomputed = false, needs_postprocessed = false;
+    int n_postprocess = 0, pp_kind[kPostprocessMaxQuantities] = {}, pp_select[kPostprocessMaxQuantities] = {};
+    int n_manifolds = 0, dofs_per_cell = 0;
+    uint32_t n_cells = 0, n_selected_cells = 0, n_selected_nodes = 0;
+    DeviceBuffer<double> d_levelsets;                          /* [n_manifolds][n_relevant] */
+    DeviceBuffer<uint32_t> d_cell_ids, d_node_ids, d_connectivity; /* the selection */
+    DeviceBuffer<double> d_columns;                            /* [columns][n_relevant]: alpha and postprocessed, ghosts exchanged */
+    DeviceBuffer<OutputDesc> d_desc;
+    DeviceBuffer<unsigned char> d_out; /* the values of one output, grown on demand */
+  };
+  std::unique_ptr<Output> output;
+  template <typename E>
+  void output_extract(Output &o, int h, bool levelsets, bool float64, void *host_out);
   /* time-dependent Dirichlet data inside a device-resident RK step (ryujin_hip_time_step_fn): the tau of the
    * first stage is copied to the host as soon as it exists (behind step 3 of the first stage), the later stages'
    * boundary data is evaluated at t + c_s tau while the rest of the first stage runs */
@@ -509,6 +527,8 @@ struct ryujin_hip_ctx {
     /* prec and rrec of the owned rows belong to the U stored here, before boundary conditions (left behind by the
      * last sweep of the step that wrote U: FusedPrecompute); cleared by whatever else writes U */
     bool precomputed = false;
+    /* some prepare_state_vector has run on this storage since it was handed out (ryujin_hip_output_extract) */
+    bool prepared = false;
   };
   std::vector<std::unique_ptr<State>> states;
 
@@ -1260,6 +1280,7 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStag
 {
   const auto &eparams = eq_params<E>(); /* shadows the member: the equation's parameter block */
   State &s = state(h);
+  s.prepared = true;
   const dim3 block(kBlock);
   if (iv_stage.on && bdry.n_bdry && bdry.needs_dirichlet) {
     /* initial_state(position, t + c tau) of every boundary_map entry, evaluated where the data is read: behind
@@ -2777,6 +2798,7 @@ int ryujin_hip_state_alloc(ryujin_hip_ctx *ctx, int *handle)
     }
     ctx->states[h]->used = true;
     ctx->states[h]->precomputed = false;
+    ctx->states[h]->prepared = false;
     *handle = h;
     return RYUJIN_OK;
   });
@@ -4462,6 +4484,324 @@ int ryujin_hip_error_norms_compute(ryujin_hip_ctx *ctx, int h_state, int h_analy
     if (detail)
       for (int q = 0; q < 6 * n_components; ++q)
         detail[q] = host[3 + q];
+    return RYUJIN_OK;
+  });
+}
+
+} /* extern "C" */
+
+/* ---- VTUOutput: selected fields and level-set cell output ------------------------------------------------- */
+
+/* One output (source/vtu_output.template.h:98-123, selected_components_extractor.h:91-123): the ghost range of the
+ * state vector and of the per-node columns (alpha, the postprocessed fields) exchanged, then ONE sweep over the output
+ * nodes. Every rank makes the exchanges, whatever it selected; a rank without output nodes launches nothing else. */
+template <typename E>
+void ryujin_hip_ctx::output_extract(Output &o, int h, bool levelsets, bool float64, void *host_out)
+{
+  State &s = state(h);
+  OutputDesc D = o.desc;
+  wait_comm();
+  if (D.any_state) {
+    exchange_vector(s.U.ptr, KP, false);
+    wait_comm();
+  }
+  /* alpha and the postprocessed fields: where this rank has ghost rows, a copy of the owned values whose ghost range
+   * the context's vector exchange fills with the owners' */
+  const size_t n_relevant = L.n_relevant, n_owned = L.n_owned;
+  size_t column = 0;
+  for (int q = 0; q < D.n; ++q) {
+    if (D.kind[q] != kOutAlpha && D.kind[q] != kOutPostprocessed)
+      continue;
+    const double *source = D.kind[q] == kOutAlpha ? d_alpha.ptr : d_pp_normalised.ptr + (size_t)D.index[q] * n_owned;
+    if (exch.n_nbr == 0) {
+      D.column[q] = source;
+      continue;
+    }
+    double *copy = o.d_columns.ptr + column++ * n_relevant;
+    HIP_CHECK(hipMemcpyAsync(copy, source, n_owned * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    exchange_vector(copy, 1, false);
+    wait_comm();
+    D.column[q] = copy;
+  }
+
+  const uint32_t n_nodes = levelsets ? o.n_selected_nodes : L.n_relevant;
+  if (n_nodes == 0)
+    return;
+  const size_t bytes = (size_t)D.n * n_nodes * (float64 ? sizeof(double) : sizeof(float));
+  if (o.d_out.n < bytes)
+    o.d_out.alloc(bytes, false);
+  HIP_CHECK(hipMemcpyAsync(o.d_desc.ptr, &D, sizeof(OutputDesc), hipMemcpyHostToDevice, stream));
+  const uint32_t *node_ids = levelsets ? o.d_node_ids.ptr : nullptr;
+  const dim3 grid(grid_for(n_nodes)), block(kBlock);
+  if (float64)
+    hipLaunchKernelGGL((k_output_extract<E, double>), grid, block, 0, stream, eq_params<E>(), o.d_desc.ptr, n_nodes,
+                       node_ids, s.U.ptr, s.prec.ptr, d_Z.ptr, reinterpret_cast<double *>(o.d_out.ptr));
+  else
+    hipLaunchKernelGGL((k_output_extract<E, float>), grid, block, 0, stream, eq_params<E>(), o.d_desc.ptr, n_nodes,
+                       node_ids, s.U.ptr, s.prec.ptr, d_Z.ptr, reinterpret_cast<float *>(o.d_out.ptr));
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(host_out, o.d_out.ptr, bytes, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+namespace
+{
+  /* flags [n] -> the ascending list of the set ones (and, unless NULL, the map item -> position): count, scan in a
+   * launch of its own, the total to the host (the list is allocated from it), compaction. n > 0. */
+  uint32_t compact_flags(ryujin_hip_ctx *ctx, const uint32_t n, const uint8_t *flags, DeviceBuffer<uint32_t> &scan,
+                         DeviceBuffer<uint32_t> &list, uint32_t *map)
+  {
+    const uint32_t n_blocks = (uint32_t)output_compaction_blocks(n, kBlock);
+    scan.alloc(2 * (size_t)n_blocks + 1, false); /* counts [n_blocks], offsets [n_blocks + 1] */
+    uint32_t *counts = scan.ptr, *offsets = scan.ptr + n_blocks;
+    hipLaunchKernelGGL(k_output_count, dim3(n_blocks), dim3(kBlock), 0, ctx->stream, n, flags, counts);
+    HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_output_scan, dim3(1), dim3(kBlock), 0, ctx->stream, n_blocks, counts, offsets);
+    HIP_CHECK(hipGetLastError());
+    uint32_t total = 0;
+    HIP_CHECK(hipMemcpyAsync(&total, offsets + n_blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (total > n)
+      throw HipError(RYUJIN_ERR_HIP, "output: the compaction counted more items than there are");
+    list.alloc(total, false);
+    hipLaunchKernelGGL(k_output_compact, dim3(n_blocks), dim3(kBlock), 0, ctx->stream, n, flags, offsets, list.ptr, map);
+    HIP_CHECK(hipGetLastError());
+    return total;
+  }
+
+  ryujin_hip_ctx::Output &require_output(ryujin_hip_ctx *ctx, const char *what)
+  {
+    if (!ctx->output)
+      throw HipError(RYUJIN_ERR_ARG, std::string(what) + " before output_configure");
+    return *ctx->output;
+  }
+} // namespace
+
+extern "C" {
+
+int ryujin_hip_output_configure(ryujin_hip_ctx *ctx, int n_quantities, const char *const *names,
+                                const double *positions, uint32_t n_cells, int dofs_per_cell,
+                                const uint32_t *cell_dofs, int n_manifolds, const char *const *manifolds)
+{
+  return guarded_ctx(ctx, [&]() {
+    static_assert(RYUJIN_OUT_MAX_QUANTITIES == kOutputMaxQuantities && RYUJIN_OUT_MAX_MANIFOLDS == kOutputMaxManifolds,
+                  "header and kernels agree");
+    static_assert(kOutEqEuler == RYUJIN_EQ_EULER && kOutEqShallowWater == RYUJIN_EQ_SHALLOW_WATER &&
+                      kOutEqEulerAeos == RYUJIN_EQ_EULER_AEOS &&
+                      kOutEqScalarConservation == RYUJIN_EQ_SCALAR_CONSERVATION &&
+                      kOutPpSchlieren == RYUJIN_PP_SCHLIEREN && kOutPpVorticity == RYUJIN_PP_VORTICITY,
+                  "output_selection.hpp and the header agree");
+    /* everything that can be refused comes first: a refused call leaves the previous configuration in place */
+    if (n_quantities < 1 || n_quantities > kOutputMaxQuantities || !names)
+      throw HipError(RYUJIN_ERR_ARG, "output_configure: n_quantities must be in [1, " +
+                                         std::to_string(kOutputMaxQuantities) + "] and names given");
+    if (n_manifolds < 0 || n_manifolds > kOutputMaxManifolds || (n_manifolds > 0 && !manifolds))
+      throw HipError(RYUJIN_ERR_ARG, "output_configure: n_manifolds must be in [0, " +
+                                         std::to_string(kOutputMaxManifolds) + "] and manifolds given");
+    const int dim = ctx->dim;
+    if (dofs_per_cell != (1 << dim))
+      throw HipError(RYUJIN_ERR_UNSUPPORTED, "output_configure: dofs_per_cell " + std::to_string(dofs_per_cell) +
+                                                 " is not 2^dim: patches of higher-order elements are not subdivided");
+    const uint32_t n_relevant = ctx->L.n_relevant;
+    if ((!positions && n_relevant > 0) || (!cell_dofs && n_cells > 0))
+      throw HipError(RYUJIN_ERR_ARG, "output_configure: null positions or cell_dofs with a non-zero count");
+
+    auto o = std::make_unique<ryujin_hip_ctx::Output>();
+    OutputNames tables;
+    if (!output_names(ctx->params.equation, dim, tables))
+      throw HipError(RYUJIN_ERR_ARG, "output_configure: no name tables for this Description");
+    std::vector<OutputPostprocessQuantity> pp;
+    if (ctx->pp_configured)
+      for (int q = 0; q < ctx->pp_desc.n; ++q) {
+        const int select = ctx->pp_desc.select[q];
+        pp.push_back(OutputPostprocessQuantity{ctx->pp_desc.kind[q], select >= ctx->K ? 1 : 0, select % ctx->K});
+        o->pp_kind[q] = ctx->pp_desc.kind[q];
+        o->pp_select[q] = select;
+      }
+    o->n_postprocess = (int)pp.size();
+    const std::vector<std::string> pp_names = output_postprocess_names(tables, pp.data(), (int)pp.size());
+    OutputDesc &D = o->desc;
+    D.n = n_quantities;
+    D.n_precomputed = ctx->NPREC;
+    D.n_initial_precomputed = 1; /* the bathymetry: d_Z holds one double per node */
+    size_t n_columns = 0;
+    for (int q = 0; q < n_quantities; ++q) {
+      if (!names[q])
+        throw HipError(RYUJIN_ERR_ARG, "output_configure: name " + std::to_string(q) + " is null");
+      OutputResolved r{};
+      std::string error;
+      if (!output_resolve(tables, pp_names, names[q], r, error))
+        throw HipError(RYUJIN_ERR_ARG, error);
+      if ((r.kind == kOutPrecomputed && r.index >= ctx->NPREC) || (r.kind == kOutInitialPrecomputed && r.index >= 1) ||
+          ((r.kind == kOutConserved || r.kind == kOutPrimitive) && r.index >= ctx->K))
+        throw HipError(RYUJIN_ERR_ARG, "output_configure: \"" + std::string(names[q]) + "\" is outside the arrays of the context");
+      D.kind[q] = r.kind;
+      D.index[q] = r.index;
+      D.any_state = D.any_state || r.kind == kOutConserved || r.kind == kOutPrimitive;
+      D.any_primitive = D.any_primitive || r.kind == kOutPrimitive;
+      o->needs_precomputed = o->needs_precomputed || r.kind == kOutPrecomputed;
+      o->needs_postprocessed = o->needs_postprocessed || r.kind == kOutPostprocessed;
+      n_columns += (r.kind == kOutAlpha || r.kind == kOutPostprocessed) ? 1 : 0;
+    }
+    auto program = std::make_unique<OutputManifoldProgram>();
+    program->n = 0;
+    program->n_manifolds = n_manifolds;
+    {
+      static const char *const xyz[3] = {"x", "y", "z"}; /* FunctionParser<dim>(expression): no time */
+      const ExprVariables variables{xyz, 3, 3};
+      auto one = std::make_unique<ExprProgram>();
+      for (int m = 0; m < n_manifolds; ++m) {
+        std::string error;
+        if (const int status = expr_compile(manifolds[m], dim, *one, error, variables))
+          throw HipError(status, "output_configure: manifold " + std::to_string(m) + ": " + error);
+        std::copy(one->code, one->code + one->n, program->code + program->n);
+        program->n += one->n;
+        program->code[program->n++] = ExprInstruction{kExResult, m, 0.};
+      }
+    }
+    const size_t n = n_cells, dpc = (size_t)dofs_per_cell;
+    for (size_t e = 0; e < n * dpc; ++e)
+      if (cell_dofs[e] >= n_relevant)
+        throw HipError(RYUJIN_ERR_ARG, "output_configure: index " + std::to_string(cell_dofs[e]) + " of cell " +
+                                           std::to_string(e / dpc) + " is not below n_relevant = " +
+                                           std::to_string(n_relevant));
+
+    /* the selection, on the device; nothing of the context changes before it is complete */
+    o->n_manifolds = n_manifolds;
+    o->dofs_per_cell = dofs_per_cell;
+    o->n_cells = n_cells;
+    o->d_desc.alloc(1, false);
+    if (ctx->exch.n_nbr > 0)
+      o->d_columns.alloc(n_columns * n_relevant);
+    if (n_manifolds > 0 && n_relevant > 0) {
+      DeviceBuffer<double> d_positions;
+      DeviceBuffer<OutputManifoldProgram> d_program;
+      d_positions.upload(positions, (size_t)n_relevant * dim);
+      d_program.upload(program.get(), 1);
+      o->d_levelsets.alloc((size_t)n_manifolds * n_relevant, false);
+      const dim3 grid(grid_for(n_relevant, kOutputLevelsetBlock)), block(kOutputLevelsetBlock);
+      if (dim == 1)
+        hipLaunchKernelGGL(k_output_levelsets<1>, grid, block, 0, ctx->stream, d_program.ptr, n_relevant,
+                           d_positions.ptr, o->d_levelsets.ptr);
+      else if (dim == 2)
+        hipLaunchKernelGGL(k_output_levelsets<2>, grid, block, 0, ctx->stream, d_program.ptr, n_relevant,
+                           d_positions.ptr, o->d_levelsets.ptr);
+      else
+        hipLaunchKernelGGL(k_output_levelsets<3>, grid, block, 0, ctx->stream, d_program.ptr, n_relevant,
+                           d_positions.ptr, o->d_levelsets.ptr);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipStreamSynchronize(ctx->stream)); /* the positions and the programs go out of scope */
+    }
+    if (n_manifolds > 0 && n_cells > 0) {
+      std::vector<uint32_t> dofs_t(n * dpc); /* transposed: lane = cell reads it coalesced */
+      for (size_t c = 0; c < n; ++c)
+        for (size_t v = 0; v < dpc; ++v)
+          dofs_t[v * n + c] = cell_dofs[c * dpc + v];
+      DeviceBuffer<uint32_t> d_cell_dofs, d_scan, d_node_map;
+      DeviceBuffer<uint8_t> d_cell_flags, d_node_flags;
+      d_cell_dofs.upload(dofs_t);
+      d_cell_flags.alloc(n, false);
+      hipLaunchKernelGGL(k_output_cell_flags, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, n_cells, dofs_per_cell,
+                         d_cell_dofs.ptr, n_manifolds, n_relevant, o->d_levelsets.ptr, d_cell_flags.ptr);
+      HIP_CHECK(hipGetLastError());
+      o->n_selected_cells = compact_flags(ctx, n_cells, d_cell_flags.ptr, d_scan, o->d_cell_ids, nullptr);
+      if (o->n_selected_cells > 0) {
+        d_node_flags.alloc(n_relevant); /* zeroed */
+        d_node_map.alloc(n_relevant, false);
+        hipLaunchKernelGGL(k_output_mark_nodes, dim3(grid_for(o->n_selected_cells)), dim3(kBlock), 0, ctx->stream,
+                           o->n_selected_cells, n_cells, dofs_per_cell, o->d_cell_ids.ptr, d_cell_dofs.ptr,
+                           d_node_flags.ptr);
+        HIP_CHECK(hipGetLastError());
+        o->n_selected_nodes = compact_flags(ctx, n_relevant, d_node_flags.ptr, d_scan, o->d_node_ids, d_node_map.ptr);
+        o->d_connectivity.alloc((size_t)o->n_selected_cells * dpc, false);
+        hipLaunchKernelGGL(k_output_connectivity, dim3(grid_for(o->n_selected_cells)), dim3(kBlock), 0, ctx->stream,
+                           o->n_selected_cells, n_cells, dofs_per_cell, o->d_cell_ids.ptr, d_cell_dofs.ptr,
+                           d_node_map.ptr, o->d_connectivity.ptr);
+        HIP_CHECK(hipGetLastError());
+      }
+      HIP_CHECK(hipStreamSynchronize(ctx->stream)); /* the scratch arrays go out of scope */
+    }
+    /* a second configure replaces the first: nothing enqueued may still read the old arrays */
+    ctx->finish();
+    ctx->output = std::move(o);
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_output_info(ryujin_hip_ctx *ctx, uint32_t *n_selected_cells, uint32_t *n_selected_nodes)
+{
+  return guarded_ctx(ctx, [&]() {
+    const ryujin_hip_ctx::Output &o = require_output(ctx, "output_info");
+    if (n_selected_cells)
+      *n_selected_cells = o.n_selected_cells;
+    if (n_selected_nodes)
+      *n_selected_nodes = o.n_selected_nodes;
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_output_selection(ryujin_hip_ctx *ctx, uint32_t *cell_ids, uint32_t *node_ids, uint32_t *connectivity)
+{
+  return guarded_ctx(ctx, [&]() {
+    const ryujin_hip_ctx::Output &o = require_output(ctx, "output_selection");
+    ctx->finish();
+    if (cell_ids && o.n_selected_cells)
+      HIP_CHECK(hipMemcpy(cell_ids, o.d_cell_ids.ptr, sizeof(uint32_t) * o.n_selected_cells, hipMemcpyDeviceToHost));
+    if (node_ids && o.n_selected_nodes)
+      HIP_CHECK(hipMemcpy(node_ids, o.d_node_ids.ptr, sizeof(uint32_t) * o.n_selected_nodes, hipMemcpyDeviceToHost));
+    if (connectivity && o.n_selected_cells)
+      HIP_CHECK(hipMemcpy(connectivity, o.d_connectivity.ptr,
+                          sizeof(uint32_t) * o.n_selected_cells * (size_t)o.dofs_per_cell, hipMemcpyDeviceToHost));
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_output_levelset_values(ryujin_hip_ctx *ctx, int manifold, double *out)
+{
+  return guarded_ctx(ctx, [&]() {
+    const ryujin_hip_ctx::Output &o = require_output(ctx, "output_levelset_values");
+    if (manifold < 0 || manifold >= o.n_manifolds)
+      throw HipError(RYUJIN_ERR_ARG, "output_levelset_values: unknown manifold " + std::to_string(manifold));
+    const size_t n = ctx->L.n_relevant;
+    if (n == 0)
+      return RYUJIN_OK;
+    if (!out)
+      throw HipError(RYUJIN_ERR_ARG, "output_levelset_values: null argument");
+    ctx->finish();
+    HIP_CHECK(hipMemcpy(out, o.d_levelsets.ptr + (size_t)manifold * n, n * sizeof(double), hipMemcpyDeviceToHost));
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_output_extract(ryujin_hip_ctx *ctx, int h_state, int levelsets, int precision, void *out)
+{
+  return guarded_ctx(ctx, [&]() {
+    ryujin_hip_ctx::Output &o = require_output(ctx, "output_extract");
+    if (levelsets && o.n_manifolds == 0)
+      throw HipError(RYUJIN_ERR_ARG, "output_extract: level-set output without a manifold");
+    if (precision != RYUJIN_OUT_FLOAT32 && precision != RYUJIN_OUT_FLOAT64)
+      throw HipError(RYUJIN_ERR_ARG, "output_extract: unknown precision " + std::to_string(precision));
+    const ryujin_hip_ctx::State &s = ctx->state(h_state);
+    const size_t n_nodes = levelsets ? o.n_selected_nodes : ctx->L.n_relevant;
+    if (!out && n_nodes > 0)
+      throw HipError(RYUJIN_ERR_ARG, "output_extract: null output array");
+    if (o.needs_precomputed && !s.prepared && !s.precomputed)
+      throw HipError(RYUJIN_ERR_ARG, "output_extract: a precomputed quantity of a state vector that no "
+                                     "prepare_state_vector has run on");
+    if (o.needs_postprocessed) {
+      bool same = ctx->pp_configured && ctx->pp_desc.n == o.n_postprocess;
+      for (int q = 0; same && q < o.n_postprocess; ++q)
+        same = ctx->pp_desc.kind[q] == o.pp_kind[q] && ctx->pp_desc.select[q] == o.pp_select[q];
+      if (!same)
+        throw HipError(RYUJIN_ERR_ARG, "output_extract: the postprocessor was configured anew since output_configure");
+      if (!ctx->pp_computed)
+        throw HipError(RYUJIN_ERR_ARG, "output_extract: a postprocessed quantity before postprocess_compute");
+    }
+    dispatch_equation(ctx->params.equation, ctx->dim, [&](auto tag) {
+      ctx->template output_extract<typename decltype(tag)::type>(o, h_state, levelsets != 0,
+                                                                 precision == RYUJIN_OUT_FLOAT64, out);
+      return 0;
+    });
     return RYUJIN_OK;
   });
 }

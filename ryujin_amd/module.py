@@ -490,6 +490,70 @@ class HyperbolicModule:
             self.initial_values_interpolate(analytic, t)
         return self.error_norms_compute(state, analytic, components, normalize)
 
+    # ------------------------------------------------------------------ VTUOutput (device backend only)
+    def output_configure(self, names, cells=None, manifolds=(), positions=None) -> tuple[int, int]:
+        """"vtu output quantities" and "manifolds" of VTUOutput (ryujin_hip_output_configure): names of conserved,
+        primitive, precomputed and initial-precomputed components, "alpha", and the postprocessed fields configured so
+        far; cells [n_cells, 2^dim] local indices of this rank's cells (default: those of the offline data); manifolds
+        a sequence of level-set expressions in x [y [z]]. The selection is computed here, once. Returns
+        (n_selected_cells, n_selected_nodes). A second call replaces the first."""
+        self._require_device("output_configure")
+        names = [names] if isinstance(names, str) else list(names)
+        manifolds = [manifolds] if isinstance(manifolds, str) else list(manifolds)
+        if cells is None:
+            cells = self.offline.cells
+        dofs_per_cell = 2 ** self.dim
+        cells = np.ascontiguousarray(cells, dtype=np.uint32).reshape(-1, dofs_per_cell)
+        pos = np.ascontiguousarray(self.offline.positions if positions is None else positions,
+                                   dtype=np.float64).reshape(-1)
+        assert pos.size == self.n_relevant * self.dim
+        c_names = (C.c_char_p * max(1, len(names)))(*[str(n).encode() for n in names])
+        c_manifolds = (C.c_char_p * max(1, len(manifolds)))(*[str(m).encode() for m in manifolds])
+        self._check(self._f("output_configure")(
+            self._ctx, len(names), c_names, capi.as_ptr(pos, capi.c_double_p) if pos.size else None, len(cells),
+            dofs_per_cell, capi.as_ptr(cells, capi.c_u32_p) if cells.size else None, len(manifolds), c_manifolds))
+        self._out_names, self._out_dofs_per_cell = names, dofs_per_cell
+        return self.output_info()
+
+    def output_info(self) -> tuple[int, int]:
+        """(n_selected_cells, n_selected_nodes) of the configured level-set selection"""
+        n_cells, n_nodes = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._f("output_info")(self._ctx, C.byref(n_cells), C.byref(n_nodes)))
+        return n_cells.value, n_nodes.value
+
+    def output_selection(self):
+        """(cell_ids [n_selected_cells], node_ids [n_selected_nodes], connectivity [n_selected_cells, 2^dim]): the
+        selected cells as positions in the configured cell list, their nodes as local indices, both ascending, and the
+        cells' vertices as indices into node_ids (ryujin_hip_output_selection)"""
+        n_cells, n_nodes = self.output_info()
+        cell_ids, node_ids = np.zeros(n_cells, dtype=np.uint32), np.zeros(n_nodes, dtype=np.uint32)
+        connectivity = np.zeros((n_cells, self._out_dofs_per_cell), dtype=np.uint32)
+        self._check(self._f("output_selection")(
+            self._ctx, capi.as_ptr(cell_ids, capi.c_u32_p) if n_cells else None,
+            capi.as_ptr(node_ids, capi.c_u32_p) if n_nodes else None,
+            capi.as_ptr(connectivity, capi.c_u32_p) if n_cells else None))
+        return cell_ids, node_ids, connectivity
+
+    def output_levelset_values(self, manifold: int) -> np.ndarray:
+        """[n_relevant]: level set `manifold` at the nodes as the device evaluated it"""
+        out = np.zeros(self.n_relevant, dtype=np.float64)
+        self._check(self._f("output_levelset_values")(self._ctx, int(manifold),
+                                                      capi.as_ptr(out, capi.c_double_p) if out.size else None))
+        return out
+
+    def output_extract(self, state: StateVector, levelsets: bool = False, precision: str = "float32") -> np.ndarray:
+        """[n_quantities, n_nodes]: the configured quantities at all locally relevant nodes, or with levelsets=True at
+        the nodes of output_selection(), as float32 (what the writer stores) or float64 (ryujin_hip_output_extract;
+        collective over the ranks)."""
+        dtype = {"float32": np.float32, "float64": np.float64}[precision]
+        n_nodes = self.output_info()[1] if levelsets else self.n_relevant
+        out = np.zeros((len(self._out_names), n_nodes), dtype=dtype)
+        self._check(self._f("output_extract")(
+            self._ctx, state.handle, int(bool(levelsets)),
+            capi.OUT_FLOAT64 if precision == "float64" else capi.OUT_FLOAT32,
+            out.ctypes.data_as(C.c_void_p) if out.size else None))
+        return out
+
     # ------------------------------------------------------------------ Quantities (device backend only)
     def quantities_add_manifold(self, index, weight, options: int) -> int:
         """A point map of this rank (ryujin_hip_quantities_add_manifold): owned local indices, a positive weight per
