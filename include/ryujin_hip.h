@@ -214,6 +214,14 @@ typedef struct ryujin_hip_params {
    * every sweep streams the explicit arrays, as for an unstructured mesh. Results are identical: the same bits reach
    * the same operations. */
   int debug_stencil_classes;
+  /* The tile mask from step 6 to step 7: the first of two limiter passes knows, per (64-row slice, column) tile, whether
+   * some pair of the tile is limited; the second-pass l'_ij of every other tile are exact zeros. Up to two dimensions
+   * its single-launch cached kernel leaves that mask (one word per slice), and the last pass requests the tile
+   * descriptor, l'_ij and the transposed l'_ji only of the tiles the mask names (ryujin_amd/csrc/kernels_limiter.hpp,
+   * SliceFlags::next_tiles; step_plan.hpp says which updates take it), and the first pass does not store the zeros of
+   * the other tiles outside the export slices. 0: on where the plan allows it (default); > 0: the mask, with every
+   * zero stored; < 0: off. Results are identical for finite data: min(0, l'_ji) = 0. */
+  int debug_next_tile_mask;
 } ryujin_hip_params;
 
 /* ---- offline data (input contract) ------------------------------------- */
@@ -491,6 +499,12 @@ int ryujin_hip_chain_info(ryujin_hip_ctx *ctx, unsigned long long *n_chained_til
  * rows may have none either), 3-D, debug_stencil_classes < 0. Diagnostics; any pointer may be NULL. */
 int ryujin_hip_stencil_class_info(ryujin_hip_ctx *ctx, unsigned long long *n_uniform_slices,
                                   unsigned long long *n_classes, double *uniform_entry_fraction);
+/* The tile mask of the latest step (ryujin_hip_params::debug_next_tile_mask): whether its plan handed the mask from
+ * step 6 to step 7, the number of off-diagonal (slice, column) tiles of the owned rows, and how many of them the mask
+ * named -- the others step 7 did not read. 0 / n_tiles / n_tiles where the plan did not take it. Synchronises and
+ * downloads one word per slice. Diagnostics; any pointer may be NULL. */
+int ryujin_hip_next_tile_mask_info(ryujin_hip_ctx *ctx, int *active, unsigned long long *n_tiles,
+                                   unsigned long long *n_named);
 /* Where the latest step stored P_ij per tile (pij_stored == 3): of the (slice, column) tiles between the two latest
  * host synchronisations, the fractions step 5 stored, step 6 read, and step 6 had to form itself because step 5 had
  * not stored them (ryujin_amd/csrc/kernels_limiter_stage0.hpp). 1 / 1 / 0 otherwise. Any pointer may be NULL. */
@@ -506,6 +520,11 @@ int ryujin_hip_tile_statistics(ryujin_hip_ctx *ctx, double *stored_fraction, dou
  * tests): 6 d_ij, 7 l_ij, 8 lij_next (plain CSR over n_relevant rows; d_ij is never exchanged, its ghost rows
  * stay zero as in the reference), 9 r_i (k per row, n_relevant rows) */
 int ryujin_hip_debug_fetch(ryujin_hip_ctx *ctx, int what, double *out, size_t n_doubles);
+/* Test hook: every off-diagonal slot of the owned rows of a module-owned matrix, padding included, set to `value` (a
+ * NaN included). what: 5 lij_next -- the buffer
+ * the next update's first high-order pass writes its l'_ij to (under the tile mask it leaves the slots of the unlimited
+ * tiles as they are: tests/test_gpu_next_tile_mask.py). */
+int ryujin_hip_debug_fill(ryujin_hip_ctx *ctx, int what, double value);
 /* Which kernels the LAST step() ran (ryujin_amd/csrc/step_plan.hpp: the plan decided once per update) and what its
  * sweeps of steps 5 and 6 launched, as RYUJIN_DEBUG_PLAN_LENGTH ints in this order:
  *    0 step2 (0 alpha_then_dij, 1 dij_alpha_sc, 2 records, 3 dij_alpha)   1 step2_split   2 fast_riemann

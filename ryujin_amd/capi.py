@@ -72,6 +72,7 @@ class Params(C.Structure):
         ("debug_pij_storage", C.c_int), ("debug_expensive_bounds_check", C.c_int),
         ("debug_tile_map", C.c_int), ("debug_band_stride", C.c_int),
         ("debug_xcd_chunk", C.c_int), ("debug_stencil_classes", C.c_int),
+        ("debug_next_tile_mask", C.c_int),
     ]
 
 
@@ -392,6 +393,7 @@ HIP_SYMBOLS = [
     "ryujin_hip_time_step_fn", "ryujin_hip_debug_addresses",
     "ryujin_hip_host_register", "ryujin_hip_host_unregister", "ryujin_hip_state_download_owned",
     "ryujin_hip_state_download_prepared", "ryujin_hip_layout_info", "ryujin_hip_chain_info", "ryujin_hip_stencil_class_info", "ryujin_hip_tile_statistics",
+    "ryujin_hip_next_tile_mask_info", "ryujin_hip_debug_fill",
     "ryujin_hip_default_params", "ryujin_hip_create", "ryujin_hip_destroy",
     "ryujin_hip_state_alloc", "ryujin_hip_state_free", "ryujin_hip_state_upload",
     "ryujin_hip_state_download", "ryujin_hip_state_download_precomputed", "ryujin_hip_state_integrals",
@@ -488,6 +490,11 @@ def load_hip():
         if hasattr(lib, "ryujin_hip_stencil_class_info"):  # (A/B libraries of earlier trees do not have it)
             lib.ryujin_hip_stencil_class_info.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
                                                           C.POINTER(C.c_double)]
+        if hasattr(lib, "ryujin_hip_debug_fill"):
+            lib.ryujin_hip_debug_fill.argtypes = [vp, C.c_int, C.c_double]
+        if hasattr(lib, "ryujin_hip_next_tile_mask_info"):  # (A/B libraries of earlier trees do not have it)
+            lib.ryujin_hip_next_tile_mask_info.argtypes = [vp, c_int_p, C.POINTER(C.c_ulonglong),
+                                                           C.POINTER(C.c_ulonglong)]
         lib.ryujin_hip_tile_statistics.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         lib.ryujin_hip_host_register.argtypes = [vp, C.c_void_p, C.c_size_t]
         lib.ryujin_hip_host_unregister.argtypes = [vp, C.c_void_p]

@@ -527,16 +527,20 @@ namespace ryujin_hip
    * 0.076 -> 0.126 ms on C2. */
   RYUJIN_DEV void batch_fence() { __builtin_amdgcn_sched_barrier(0); }
 
+  /* `cols` (wave-uniform, bit c: column c): the columns asked for; nothing is loaded for the others (step 7 under the
+   * tile mask of step 6, SliceFlags::next_tiles) and their position is 0. */
   template <bool USE, int N>
-  RYUJIN_DEV void transposed_positions(const DeviceMesh &M, const RowCtx &r, const int c0, uint32_t (&tpos)[N])
+  RYUJIN_DEV void transposed_positions(const DeviceMesh &M, const RowCtx &r, const int c0, uint32_t (&tpos)[N],
+                                       const uint32_t cols = ~0u)
   {
+    auto asked = [&](const int k) { return (uint32_t)(c0 + k) < r.width && ((cols >> ((c0 + k) & 31)) & 1u) != 0u; };
     if constexpr (USE) {
       if (M.tiles != nullptr) {
         int4 raw[N];
 #pragma unroll
         for (int k = 0; k < N; ++k) {
           raw[k] = int4{kTileIrregular, 0, 0, 0};
-          if ((uint32_t)(c0 + k) < r.width)
+          if (asked(k))
             raw[k] = load_tile_desc(M.tiles + ((uint64_t)r.base + c0 + k));
         }
         batch_fence();
@@ -544,7 +548,7 @@ namespace ryujin_hip
 #pragma unroll
         for (int k = 0; k < N; ++k) {
           tpos[k] = 0;
-          if ((uint32_t)(c0 + k) < r.width) {
+          if (asked(k)) {
             const int32_t delta = __builtin_amdgcn_readfirstlane(raw[k].x);
             const uint32_t ta = (uint32_t)__builtin_amdgcn_readfirstlane(raw[k].y);
             const uint32_t tb = (uint32_t)__builtin_amdgcn_readfirstlane(raw[k].z);
@@ -555,7 +559,7 @@ namespace ryujin_hip
         if (any_irregular) { /* wave-uniform, rare (boundary slices): the explicit array for those columns */
 #pragma unroll
           for (int k = 0; k < N; ++k)
-            if ((uint32_t)(c0 + k) < r.width && __builtin_amdgcn_readfirstlane(raw[k].x) == kTileIrregular)
+            if (asked(k) && __builtin_amdgcn_readfirstlane(raw[k].x) == kTileIrregular)
               tpos[k] = M.idx_t[((uint64_t)r.base + c0 + k) * 64 + r.lane];
         }
         /* (one wait for whatever the branch above loaded, here: otherwise the compiler waits -- for everything in
@@ -569,7 +573,7 @@ namespace ryujin_hip
 #pragma unroll
     for (int k = 0; k < N; ++k) {
       tpos[k] = 0;
-      if ((uint32_t)(c0 + k) < r.width)
+      if (asked(k))
         tpos[k] = M.idx_t[((uint64_t)r.base + c0 + k) * 64 + r.lane];
     }
 #pragma unroll

@@ -877,7 +877,29 @@ namespace ryujin_hip
      * last update; bits 10 + c, 20 + c: in the update before, and the one before that (tiles_predicted /
      * tiles_remember below). */
     uint32_t *needed_tiles;
+    /* written by step 6 (the single-launch cached kernel, up to two dimensions) for the last sweep of the same update,
+     * or NULL: [n_slices] words, bit c: some pair of the (slice, column c) tile is limited after the symmetrisation --
+     * step 6's `needed`. Every l'_ij of a tile outside it is an exact zero, and lmin(0, l'_ji) = 0 whatever the
+     * partner holds: step 7 sets l = 0 for those columns and requests no descriptor, no l'_ij and no l'_ji of theirs
+     * (last_cached_slice). A word of its own: needed_tiles exists only under per-tile P_ij storage and holds three
+     * generations. */
+    uint32_t *next_tiles;
+    /* != 0 (with next_tiles): this launch of step 6 does not store the zeros of the tiles outside the mask. The slot
+     * keeps what it held -- the first-pass l_ij of the update before (the two matrices are swapped every update), a NaN
+     * after a restarted update. The row itself never reads it (the mask); the partner row reads it as l'_ji of a pair
+     * whose own l'_ij is an exact zero and takes l = 0 without looking at it (last_cached_slice); what leaves the rank
+     * is always stored (the launch over the export slices never elides); k_fill_unnamed_tiles materialises the zeros
+     * before the matrix is handed to the host. */
+    uint32_t next_tiles_elide;
   };
+
+  /* the slice's word of SliceFlags::next_tiles: a scalar load through the constant address space (written by step 6,
+   * read by the launches of step 7 only; nothing in vmcnt), as the class index and the tile descriptors */
+  RYUJIN_DEV uint32_t slice_next_tiles(const uint32_t *next_tiles, const uint32_t slice)
+  {
+    typedef const uint32_t __attribute__((address_space(4))) *const_ptr;
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)*(const_ptr)(uintptr_t)(next_tiles + slice));
+  }
 
 #ifndef RYUJIN_GATHER_GROUP_3D
 #define RYUJIN_GATHER_GROUP_3D 6 /* columns whose l_ij / l_ji are fetched in one batch where the row has more than 9 (steps 6, 7 in 3-D). C4 share, same process (profiles/r06v_ab_batched_gathers_c4.log): step 6 1.497 -> 1.379 (9) / 1.327 (6) / 1.413 (13) ms, step 7 0.857 -> 0.789 / 0.761 / 0.801 */
@@ -928,7 +950,8 @@ namespace ryujin_hip
   RYUJIN_DEV void last_cached_slice(const typename E::Params &P, const DeviceMesh &M, const RowCtx &r,
                                     double *__restrict__ new_U, const double *__restrict__ pij,
                                     const double *__restrict__ lij, const FusedSadd &F, const FusedPrecompute &FP,
-                                    const uint8_t *__restrict__ slice_unlimited = nullptr)
+                                    const uint8_t *__restrict__ slice_unlimited = nullptr,
+                                    const uint32_t *__restrict__ next_tiles = nullptr)
   {
     constexpr int K = E::K;
     const bool row_active = r.len > 1;
@@ -945,24 +968,33 @@ namespace ryujin_hip
     double l[MAXW];
     uint32_t needed = 0; /* wave-uniform: bit c <=> some row of the slice has l(c) != 0 */
     const bool known_unlimited = slice_unlimited != nullptr && slice_unlimited[r.slice] != 0;
+    /* the tiles step 6 found limited (SliceFlags::next_tiles; all of them without the mask). A tile outside holds exact
+     * zeros in this row's l'_ij, and lmin(0, l'_ji) = 0 for every l'_ji in [0, 1]: l = 0 without a load. (Where the
+     * two differ -- an own exact zero against a partner's NaN of the same update -- the partner's row carries a NaN
+     * state already and the update is flagged for restart.) Wave-uniform. */
+    uint32_t cols = ~0u;
+    if constexpr (MAXW <= 10) {
+      if (next_tiles != nullptr)
+        cols = slice_next_tiles(next_tiles, r.slice);
+    }
 #pragma unroll
     for (int c = 1; c < MAXW; ++c)
       l[c] = 0.;
-    if (!known_unlimited) {
+    if (!known_unlimited && cols != 0u) {
       /* in groups of up to 9 columns: all transposed positions, all l_ij and l_ji, then the minima
        * (transposed_positions(), kernels_euler.hpp) */
       constexpr int CH = MAXW - 1 < 9 ? MAXW - 1 : RYUJIN_GATHER_GROUP_3D;
 #pragma unroll
       for (int c0 = 1; c0 < MAXW; c0 += CH) {
         uint32_t tpos[CH];
-        transposed_positions<tile_map_pays<E::DIMENSION>(), CH>(M, r, c0, tpos);
+        transposed_positions<tile_map_pays<E::DIMENSION>(), CH>(M, r, c0, tpos, cols);
         batch_fence();
         double l_a[CH], l_b[CH];
 #pragma unroll
         for (int k = 0; k < CH; ++k) {
           const int c = c0 + k;
           l_a[k] = l_b[k] = 0.;
-          if (c < MAXW && (uint32_t)c < r.width) {
+          if (c < MAXW && (uint32_t)c < r.width && ((cols >> c) & 1u)) {
             l_a[k] = lij[(uint32_t)(((uint64_t)r.base + c) * 64 + r.lane)];
             l_b[k] = lij[tpos[k]];
           }
@@ -976,8 +1008,16 @@ namespace ryujin_hip
 #pragma unroll
         for (int k = 0; k < CH; ++k) {
           const int c = c0 + k;
-          if (c < MAXW && (uint32_t)c < r.width)
+          if (c < MAXW && (uint32_t)c < r.width && ((cols >> c) & 1u)) {
             l[c] = (row_active && (uint32_t)c < r.len) ? lmin(l_a[k], l_b[k]) : 0.;
+            /* Under the mask l'_ji may be a slot step 6 did not store (SliceFlags::next_tiles_elide): the partner's
+             * tile lies outside ITS mask, so the pair's symmetrised first-pass l was 1 and this row's own l'_ij is an
+             * exact zero -- (1 - 1) l' or a stored 0. Then l = 0 whatever the slot holds; for finite operands that is
+             * lmin bit for bit (l'_ji in [0, 1]). Where the two differ -- an own exact zero against a partner's NaN of
+             * the same update -- the partner's row carries a NaN state already and the update is flagged for restart. */
+            if (next_tiles != nullptr)
+              l[c] = l_a[k] == 0. ? 0. : l[c];
+          }
         }
       }
 #pragma unroll
@@ -1036,12 +1076,13 @@ namespace ryujin_hip
   __global__ void __launch_bounds__(kBlock, (MAXW > 9 ? RYUJIN_OCC_LAST_3D : 1))
   k_high_order_last_cached(const typename E::Params P, const DeviceMesh M, double *__restrict__ new_U,
                            const double *__restrict__ pij, const double *__restrict__ lij, const FusedSadd F,
-                           const FusedPrecompute FP, const uint8_t *__restrict__ slice_unlimited = nullptr)
+                           const FusedPrecompute FP, const uint8_t *__restrict__ slice_unlimited = nullptr,
+                           const uint32_t *__restrict__ next_tiles = nullptr)
   {
     const RowCtx r = row_context(M);
     if (!r.valid)
       return;
-    last_cached_slice<E, MAXW, CHUNK>(P, M, r, new_U, pij, lij, F, FP, slice_unlimited);
+    last_cached_slice<E, MAXW, CHUNK>(P, M, r, new_U, pij, lij, F, FP, slice_unlimited, next_tiles);
   }
 
   /* Register-cached variant for stencils of at most MAXW columns (2-D Q1: 9, 1-D: 3): the row's
@@ -1089,6 +1130,11 @@ namespace ryujin_hip
     constexpr int NB = E::NB;
     static_assert(!SPLIT || CP == MAXW, "the split variant caches the whole row");
     static_assert(!SPLIT || MODE == kHoPlain, "small meshes keep the stored P_ij");
+    /* the launch that hands its tile mask to step 7 (SliceFlags::next_tiles): one wave per slice, one launch */
+    constexpr bool kNextTiles = !SPLIT && MODE == kHoPlain && MAXW <= 10;
+    bool elide = false; /* the zeros of the tiles outside the mask are not stored (SliceFlags::next_tiles_elide) */
+    if constexpr (kNextTiles)
+      elide = W.next_tiles != nullptr && W.next_tiles_elide != 0u;
     const bool row_active = r.len > 1;
     const uint32_t i = row_active ? r.row : (r.row < M.n_owned ? r.row : M.n_owned - 1);
     const uint32_t *__restrict__ idx_t = M.idx_t;
@@ -1232,6 +1278,9 @@ namespace ryujin_hip
       }
       if (W.unlimited != nullptr && r.lane == 0 && (!SPLIT || group == 0))
         W.unlimited[r.slice] = slice_limited ? 0 : 1;
+      if constexpr (kNextTiles) /* for step 7, on every path that returns (0 where nothing is limited) */
+        if (W.next_tiles != nullptr && r.lane == 0)
+          W.next_tiles[r.slice] = needed;
       if constexpr (kTileMode)
         if (tiles && r.lane == 0 && (!SPLIT || group == 0))
           tiles_remember<MAXW>(W, r.slice, needed);
@@ -1240,10 +1289,12 @@ namespace ryujin_hip
         if (row_active) {
           if (!SPLIT || group == 0)
             store_state<K>(new_U, i, U_i_new);
+          if (!elide) {
 #pragma unroll
-          for (int c = 1; c < MAXW; ++c)
-            if ((uint32_t)c < r.len && (!SPLIT || (uint32_t)(c - 1) % kWavesPerBlock == group))
-              st_stream(lij_next + ((r.base + c) * 64 + r.lane), 0.);
+            for (int c = 1; c < MAXW; ++c)
+              if ((uint32_t)c < r.len && (!SPLIT || (uint32_t)(c - 1) % kWavesPerBlock == group))
+                st_stream(lij_next + ((r.base + c) * 64 + r.lane), 0.);
+          }
         }
         return;
       }
@@ -1358,6 +1409,9 @@ namespace ryujin_hip
             needed |= 1u << c;
         }
       }
+      if constexpr (kNextTiles)
+        if (W.next_tiles != nullptr && r.lane == 0)
+          W.next_tiles[r.slice] = needed;
 #pragma unroll
       for (int c = 1; c < MAXW; ++c) {
         if (c < CP) {
@@ -1395,7 +1449,7 @@ namespace ryujin_hip
         continue;
       const bool lane_on = row_active && (uint32_t)c < r.len;
       if (!((needed >> c) & 1u)) {
-        if (lane_on)
+        if (lane_on && !elide)
           st_stream(lij_next + ((r.base + c) * 64 + r.lane), 0.);
         continue;
       }
@@ -1440,6 +1494,21 @@ namespace ryujin_hip
           const double old_l_ij = lmin(lij[pos], lij[idx_t[pos]]);
           st_stream(lij_next + (pos), (1. - old_l_ij) * new_l_ij);
         });
+  }
+
+  /* the zeros step 6 did not store (SliceFlags::next_tiles_elide), written after all: every tile outside the slice's mask
+   * (ryujin_hip_debug_fetch of the second-pass matrix) */
+  __global__ void __launch_bounds__(kBlock)
+  k_fill_unnamed_tiles(const DeviceMesh M, const uint32_t *__restrict__ next_tiles, double *__restrict__ lij)
+  {
+    const uint32_t slice = M.slice_begin + blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (slice >= M.slice_end)
+      return;
+    const RowCtx r = row_context_of_slice(M, slice);
+    const uint32_t named = next_tiles[slice];
+    for (uint32_t c = 1; c < r.width && c < 32u; ++c)
+      if (!((named >> c) & 1u) && c < r.len)
+        lij[((uint64_t)r.base + c) * 64 + r.lane] = 0.;
   }
 
   /* the launch between the light and the heavy one: completes the P_ij of the slices the light launch marked */

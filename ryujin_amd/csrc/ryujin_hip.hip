@@ -571,6 +571,7 @@ struct ryujin_hip_ctx {
    * context stores P_ij everywhere */
   DeviceBuffer<uint8_t> d_slice_unlimited, d_slice_first_stored, d_slice_todo;
   DeviceBuffer<uint32_t> d_slice_needed; /* SliceFlags::needed_tiles; starts as all ones: the first update stores every tile */
+  DeviceBuffer<uint32_t> d_slice_next_tiles; /* SliceFlags::next_tiles: step 6 writes every word before step 7 reads it */
   /* fractions of the (sampled) slices in which the first high-order sweep found a limited pair / whose P_ij step 5
    * stored, from the device counters at the latest host synchronisation (DeviceScalars::n_sampled_*); 1 until the
    * first measurement. Diagnostics only: nothing is decided from them. */
@@ -1474,7 +1475,9 @@ StepPlanInput ryujin_hip_ctx::plan_input(const int stages) const
   in.dg = dg;
   in.max_row_len = L.max_row_len;
   in.n_slices = L.n_slices;
+  in.n_export_slices = exch.n_nbr != 0 ? n_export_slices : 0u; /* the launches of sweep() */
   in.debug_pij_storage = params.debug_pij_storage;
+  in.debug_next_tile_mask = params.debug_next_tile_mask;
   in.checked = params.debug_expensive_bounds_check != 0;
   in.limited_fraction = limited_fraction;
   in.per_slice_max_limited = (double)RYUJIN_PER_SLICE_MAX_LIMITED;
@@ -1626,6 +1629,8 @@ void ryujin_hip_ctx::ensure_limiter_buffers(const StepPlan &plan)
     d_slice_needed.alloc(L.n_slices);
     HIP_CHECK(hipMemsetAsync(d_slice_needed.ptr, 0xff, (size_t)L.n_slices * sizeof(uint32_t), launch_stream));
   }
+  if (plan.next_tile_mask && d_slice_next_tiles.n == 0)
+    d_slice_next_tiles.alloc(L.n_slices);
 }
 
 /* Step 4: low-order update, bounds, r_i, p_ij; ghost r (:597-884) */
@@ -1814,6 +1819,10 @@ void ryujin_hip_ctx::step6_high_order_next(const StepPlan &plan, const StepArgs<
     if (plan.step6 == Step6::cached) {
       SliceFlags flags6 = a.tile_flags;
       flags6.unlimited = unlimited;
+      flags6.next_tiles = plan.next_tile_mask ? d_slice_next_tiles.ptr : nullptr;
+      /* (what the ghost exchange sends -- entries of the export slices -- is always stored) */
+      flags6.next_tiles_elide =
+          plan.next_tiles_elided && (exch.n_nbr == 0 || mm.slice_begin >= n_export_slices) ? 1u : 0u;
       hipLaunchKernelGGL((k_high_order_next_cached<E, kWidth, kCachedP>), grid, block, 0, launch_stream, eparams, mm,
                          nw.U.ptr, d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_lij_next.ptr, V, last_s0, flags6);
     } else
@@ -1849,7 +1858,8 @@ void ryujin_hip_ctx::step7_high_order_last(const StepPlan &plan, const StepArgs<
     if (plan.step7 == StepPlan::Step7::last_cached)
       hipLaunchKernelGGL((k_high_order_last_cached<E, kWidth, kLastChunk>), grid, block, 0, launch_stream, eparams,
                          mm, nw.U.ptr, d_pij.ptr, d_lij.ptr, a.fused_sadd, a.fused_prec,
-                         plan.step6_flags ? d_slice_unlimited.ptr : nullptr);
+                         plan.step6_flags ? d_slice_unlimited.ptr : nullptr,
+                         plan.next_tile_mask ? (const uint32_t *)d_slice_next_tiles.ptr : (const uint32_t *)nullptr);
     else
       hipLaunchKernelGGL((k_high_order<E, true>), grid, block, 0, launch_stream, eparams, mm, nw.U.ptr,
                          d_bounds.ptr, d_pij.ptr, d_lij.ptr, d_lij_next.ptr, a.fused_sadd);
@@ -2625,6 +2635,7 @@ void ryujin_hip_default_params(ryujin_hip_params *p, int equation, int dim)
   p->debug_band_stride = 0;
   p->debug_xcd_chunk = 0;
   p->debug_stencil_classes = 0;
+  p->debug_next_tile_mask = 0;
   /* the profiling scripts wrap bench.py, which takes the defaults: let them select a mapping without a flag */
   if (const char *e = std::getenv("RYUJIN_XCD_CHUNK"))
     p->debug_xcd_chunk = std::atoi(e);
@@ -3185,6 +3196,35 @@ int ryujin_hip_stencil_class_info(ryujin_hip_ctx *ctx, unsigned long long *n_uni
   });
 }
 
+int ryujin_hip_next_tile_mask_info(ryujin_hip_ctx *ctx, int *active, unsigned long long *n_tiles,
+                                   unsigned long long *n_named)
+{
+  return guarded_ctx(ctx, [&]() {
+    const auto &L = ctx->L;
+    const bool on = ctx->last_plan.next_tile_mask && ctx->d_slice_next_tiles.n == L.n_slices;
+    std::vector<uint32_t> words(on ? L.n_slices : 0u);
+    if (on) {
+      ctx->finish();
+      HIP_CHECK(hipMemcpy(words.data(), ctx->d_slice_next_tiles.ptr, words.size() * sizeof(uint32_t),
+                          hipMemcpyDeviceToHost));
+    }
+    unsigned long long tiles = 0, named = 0;
+    for (uint32_t s = 0; s < L.n_slices; ++s) {
+      const uint32_t width = L.slice_off[s + 1] - L.slice_off[s];
+      const uint32_t off_diagonal = width > 1 ? width - 1 : 0u;
+      tiles += off_diagonal;
+      named += on ? (unsigned long long)__builtin_popcount(words[s] & ~1u) : off_diagonal;
+    }
+    if (active)
+      *active = on ? 1 : 0;
+    if (n_tiles)
+      *n_tiles = tiles;
+    if (n_named)
+      *n_named = named;
+    return RYUJIN_OK;
+  });
+}
+
 int ryujin_hip_debug_plan(ryujin_hip_ctx *ctx, int *out, int n)
 {
   return guarded([&]() {
@@ -3233,6 +3273,18 @@ int ryujin_hip_debug_fetch(ryujin_hip_ctx *ctx, int what, double *out, size_t n_
   return guarded_ctx(ctx, [&]() {
     const auto &L = ctx->L;
     ctx->finish();
+    /* the second-pass matrix of an update whose step 6 elided the zeros of the unlimited tiles: written now */
+    auto materialise_zeros = [&](double *dev) {
+      if (!ctx->last_plan.next_tiles_elided || ctx->last_plan.step6 == StepPlan::Step6::none)
+        return;
+      DeviceMesh mm = ctx->mesh;
+      mm.slice_begin = 0;
+      mm.slice_end = L.n_slices;
+      hipLaunchKernelGGL(k_fill_unnamed_tiles, dim3((L.n_slices + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0,
+                         ctx->stream, mm, (const uint32_t *)ctx->d_slice_next_tiles.ptr, dev);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    };
     auto fetch_matrix = [&](const double *dev, uint32_t n_comp) {
       if (n_doubles < L.nnz_owned_logical * n_comp)
         throw HipError(RYUJIN_ERR_ARG, "output buffer too small");
@@ -3242,7 +3294,10 @@ int ryujin_hip_debug_fetch(ryujin_hip_ctx *ctx, int what, double *out, size_t n_
     };
     switch (what) {
     case 0: fetch_matrix(ctx->d_dij.ptr, 1); break;
-    case 1: fetch_matrix(ctx->d_lij.ptr, 1); break;
+    case 1:
+      materialise_zeros(ctx->d_lij.ptr);
+      fetch_matrix(ctx->d_lij.ptr, 1);
+      break;
     case 2:
       ctx->ensure_pij();
       if (ctx->last_plan.pij_stored != 1)
@@ -3259,6 +3314,8 @@ int ryujin_hip_debug_fetch(ryujin_hip_ctx *ctx, int what, double *out, size_t n_
     case 6:
     case 7:
     case 8: { /* plain CSR over ALL locally relevant rows: owned rows, then the ghost rows as received */
+      if (what == 7)
+        materialise_zeros(ctx->d_lij.ptr);
       const double *dev = what == 6 ? ctx->d_dij.ptr : (what == 7 ? ctx->d_lij.ptr : ctx->d_lij_next.ptr);
       const uint64_t n_ghost_entries = L.nnz_total - L.nnz_sell;
       if (n_doubles < L.nnz_owned_logical + n_ghost_entries)
@@ -3303,6 +3360,22 @@ int ryujin_hip_debug_fetch(ryujin_hip_ctx *ctx, int what, double *out, size_t n_
     }
     default: throw HipError(RYUJIN_ERR_ARG, "unknown debug_fetch selector");
     }
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_debug_fill(ryujin_hip_ctx *ctx, int what, double value)
+{
+  return guarded_ctx(ctx, [&]() {
+    if (what != 5)
+      throw HipError(RYUJIN_ERR_ARG, "unknown debug_fill selector");
+    ctx->finish();
+    const auto &L = ctx->L;
+    std::vector<double> tmp(L.nnz_total);
+    HIP_CHECK(hipMemcpy(tmp.data(), ctx->d_lij_next.ptr, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (uint32_t s = 0; s < L.n_slices; ++s) /* (column 0, the diagonal, is written by no sweep) */
+      std::fill(tmp.begin() + ((size_t)L.slice_off[s] + 1) * 64, tmp.begin() + (size_t)L.slice_off[s + 1] * 64, value);
+    HIP_CHECK(hipMemcpy(ctx->d_lij_next.ptr, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice));
     return RYUJIN_OK;
   });
 }

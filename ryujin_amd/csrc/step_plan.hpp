@@ -24,7 +24,9 @@ namespace ryujin_hip
     int stages = 0, limiter_iterations = 2;
     bool dg = false;
     uint32_t max_row_len = 0, n_slices = 0;
+    uint32_t n_export_slices = 0; /* a sweep on several ranks is two launches: [0, n_export_slices) and the rest */
     int debug_pij_storage = 0;
+    int debug_next_tile_mask = 0; /* < 0: step 6 hands no tile mask to step 7; > 0: it does, and stores every zero */
     bool checked = false; /* debug_expensive_bounds_check */
     double limited_fraction = 1.;
     double per_slice_max_limited = 1.; /* RYUJIN_PER_SLICE_MAX_LIMITED (kernels_euler.hpp) */
@@ -60,6 +62,12 @@ namespace ryujin_hip
     enum class Step6 { none, per_slice, cached, high_order } step6 = Step6::none;
     bool step6_flags = false; /* step 6 leaves SliceFlags::unlimited for every slice: the last sweep may use it */
     enum class Step7 { none, last_cached, high_order } step7 = Step7::none;
+    /* step 6 leaves SliceFlags::next_tiles -- the (slice, column) tiles in which some pair is limited -- and step 7 reads
+     * l'_ij, l'_ji and the descriptors of those tiles only (kernels_limiter.hpp). The single-launch cached step 6 with
+     * one wave per slice in EVERY launch of the sweep, up to two dimensions, in front of the cached step 7, unchecked */
+    bool next_tile_mask = false;
+    /* ... and step 6 does not store the zeros of the tiles outside the mask (outside the export slices) */
+    bool next_tiles_elided = false;
     bool fuse_precompute = false;
     bool checked = false;
     /* refusals: what step() throws as RYUJIN_ERR_UNSUPPORTED / as an internal error (nullptr: none) */
@@ -85,6 +93,32 @@ namespace ryujin_hip
              n_launch_slices * kPlanWavesPerBlock <= resident_waves_step6;
     }
   };
+
+  /* the launches of a sweep (ryujin_hip_ctx::sweep): the export part and the interior part, or the whole mesh */
+  inline bool some_launch_shares_slices(const StepPlan &p, const uint32_t n_slices, const uint32_t n_export_slices)
+  {
+    const uint32_t n_export = std::min(n_export_slices, n_slices);
+    return (n_export != 0 && p.step6_shares_slices(n_export)) ||
+           (n_slices > n_export && p.step6_shares_slices(n_slices - n_export));
+  }
+
+  /* what the tile mask relies on (nullptr: nothing violated): every launch of step 6 is the single-launch cached kernel
+   * with one wave per slice, which writes the mask; step 7 is the cached kernel, which reads it; the checked kernels
+   * read the whole second-pass matrix */
+  inline const char *next_tile_mask_violated(const StepPlan &p, const uint32_t n_slices, const uint32_t n_export_slices)
+  {
+    if (!p.next_tile_mask)
+      return p.next_tiles_elided ? "step plan: zeros are elided under the tile mask only" : nullptr;
+    if (p.step6 != StepPlan::Step6::cached || p.dim > 2)
+      return "step plan: the tile mask needs the single-launch cached step 6, dim <= 2";
+    if (some_launch_shares_slices(p, n_slices, n_export_slices))
+      return "step plan: the tile mask needs one wave per slice in every launch of step 6";
+    if (p.step7 != StepPlan::Step7::last_cached)
+      return "step plan: the tile mask needs the cached step 7";
+    if (p.checked)
+      return "step plan: the checked kernels read all of l_ij";
+    return nullptr;
+  }
 
   inline StepPlan plan_step(const StepPlanInput &in)
   {
@@ -204,6 +238,13 @@ namespace ryujin_hip
     if (n_iterations != 0)
       p.step7 = cached ? StepPlan::Step7::last_cached : StepPlan::Step7::high_order;
 
+    /* The tile mask from step 6 to step 7. Whether the waves of a block share a slice is decided per launch
+     * (step6_shares_slices), and the sharing variant writes no mask: none of the sweep's launches may take it. */
+    p.next_tile_mask = in.debug_next_tile_mask >= 0 && p.step6 == StepPlan::Step6::cached && in.dim <= 2 &&
+                       !some_launch_shares_slices(p, in.n_slices, in.n_export_slices) &&
+                       p.step7 == StepPlan::Step7::last_cached && !in.checked;
+    p.next_tiles_elided = p.next_tile_mask && in.debug_next_tile_mask == 0;
+
     /* the last sweep leaves the precomputed values and Riemann records of the new vector, where the next pre-pass
      * would be a sweep of its own (large meshes: below bc_fold_max_slices the boundary conditions ride on that sweep) */
     p.fuse_precompute = in.fusable_precompute && in.pending_precompute && n_iterations != 0 &&
@@ -219,6 +260,8 @@ namespace ryujin_hip
       p.violated = "step plan: rows of more than 64 entries need k_pij_lij<WIDE> in step 5";
     else if (p.checked && p.pij_stored != 1)
       p.violated = "step plan: the checked kernels read all of P_ij";
+    else if (const char *v = next_tile_mask_violated(p, in.n_slices, in.n_export_slices))
+      p.violated = v;
     return p;
   }
 } // namespace ryujin_hip

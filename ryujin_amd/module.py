@@ -692,6 +692,14 @@ class HyperbolicModule:
         self._check(self._lib.ryujin_hip_stencil_class_info(self._ctx, C.byref(n), C.byref(k), C.byref(f)))
         return dict(n_uniform_slices=n.value, n_classes=k.value, uniform_entry_fraction=f.value)
 
+    def next_tile_mask_info(self) -> dict:
+        """whether the plan of the latest step() handed the tile mask from step 6 to step 7, the off-diagonal (slice,
+        column) tiles of the owned rows and how many of them the mask named (ryujin_hip_next_tile_mask_info; device
+        backend only; synchronises)"""
+        a, n, k = C.c_int(0), C.c_ulonglong(0), C.c_ulonglong(0)
+        self._check(self._lib.ryujin_hip_next_tile_mask_info(self._ctx, C.byref(a), C.byref(n), C.byref(k)))
+        return dict(active=bool(a.value), n_tiles=n.value, n_named=k.value)
+
     PLAN_STEP2 = ("alpha_then_dij", "dij_alpha_sc", "records", "dij_alpha")
     PLAN_STEP5 = ("none", "stage0_per_tile", "stage0_per_slice", "stage0_groups", "recompute", "pij_lij")
     PLAN_STEP6 = ("none", "per_slice", "cached", "high_order")
@@ -717,6 +725,11 @@ class HyperbolicModule:
         out["step6_launches"] = [dict(n_slices=v[26 + 3 * q], grid_y=v[27 + 3 * q], shares_slices=bool(v[28 + 3 * q]))
                                  for q in range(min(v[21], 2))]
         return out
+
+    def debug_fill(self, what: str, value: float) -> None:
+        """test hook: every off-diagonal slot of the owned rows of a module-owned matrix set to `value`
+        (ryujin_hip_debug_fill; device backend only)"""
+        self._check(self._lib.ryujin_hip_debug_fill(self._ctx, {"lij_next": 5}[what], float(value)))
 
     def debug_fetch(self, what: str) -> np.ndarray:
         """`*_all`: over all locally relevant rows, i.e. including the ghost rows / ghost range received from
