@@ -745,6 +745,42 @@ int ryujin_hip_quantities_time_series(ryujin_hip_ctx *ctx, int manifold, double 
  *                                                                               1 "initial discharge"
  * The formulas, statement by statement, are those of ryujin_amd/initial_states.py.
  *
+ * The Riemann-data, shock-front, ramp-up and Noh states (values from 11 on; 10 is the library's own id of the function
+ * state below and RYUJIN_ERR_ARG here). They have a device function of their own, initial_state_library<E>()
+ * (ryujin_amd/csrc/initial_states_library_device.hpp), and kernels of their own; everything said above holds for
+ * them. Euler and EulerAEOS (from_initial_state through the context's equation of state, the function one included):
+ *   RYUJIN_IV_CONTRAST             euler/initial_state_contrast.h            0-2 "primitive state left", 3-5 "primitive
+ *                                                                            state right"; right where x > 0
+ *   RYUJIN_IV_THREE_STATE_CONTRAST euler/initial_state_three_state_contrast.h  0-2 "primitive state left", 3 "left
+ *                                  region length", 4-6 "primitive state middle", 7 "middle region length", 8-10
+ *                                  "primitive state right"; x >= left + middle: right, x >= left: middle
+ *   RYUJIN_IV_FOUR_STATE_CONTRAST  euler/initial_state_four_state_contrast.h (dim >= 2)  0-3 "primitive state bottom
+ *                                  left", 4-7 "... bottom right", 8-11 "... top left", 12-15 "... top right", each
+ *                                  (rho, u, v, p); x >= 0: right, y >= 0: top
+ *   RYUJIN_IV_SHOCK_FRONT          euler/initial_state_shock_front.h         0-2 "primitive state" (before the shock, to
+ *                                  the right), 3 "mach number" [2], 4 "gamma" [1.4] (EulerAEOS only); the state behind
+ *                                  the shock and its speed S3 are formed at configure time, for EulerAEOS with the
+ *                                  covolume b of the interpolatory equation of state the context has THEN; right where
+ *                                  x - S3 t > 0
+ *   RYUJIN_IV_RAMP_UP              euler/initial_state_ramp_up.h             0-2 "primitive state initial", 3-5
+ *                                  "primitive state final", 6 "time initial" [0], 7 "time final" [1]: the two
+ *                                  CONSERVED states blended with cos^2 in between
+ *   RYUJIN_IV_NOH                  euler/initial_state_noh.h                 0 "reference density" [1], 1 "reference
+ *                                  velocity magnitude" [1], 2 "reference pressure" [1e-12], 3 "gamma" [1.4] (EulerAEOS
+ *                                  only); the velocity is radial, in all dim components
+ *   RYUJIN_IV_SMOOTH_WAVE          euler/initial_state_smooth_wave.h         0 "reference density" [1], 1 "reference
+ *                                  pressure" [1], 2 "mach number" [1]; x_0 = 0.1 and x_1 = 0.3 are fixed
+ *   RYUJIN_IV_ASTRO_JET            euler/initial_state_astro_jet.h (dim >= 2)  0 "jet width" [0.05], 1-3 "primitive jet
+ *                                  state", 4-6 "primitive ambient right", 7 "gamma" [5/3] (EulerAEOS only; read by
+ *                                  nothing, as in the reference)
+ * Shallow water, zero bathymetry, dim = 1 and 2:
+ *   RYUJIN_IV_SW_UNIFORM           shallow_water/initial_state_uniform.h     0-1 "primitive state" (h, u) [1, 1]
+ *   RYUJIN_IV_SW_CONTRAST          shallow_water/initial_state_contrast.h    0-1 "primitive state left", 2-3 "primitive
+ *                                  state right"; right where x > 0
+ * Not offered: "icf like", "becker solution" (it needs the Navier-Stokes parameters), the shallow-water states that
+ * bring a bathymetry of their own ("flow over bump", "three bumps dam break", "hou test", "transient", "soliton",
+ * "geotiff"), perturbation != 0.
+ *
  *   configure     positions [n_relevant * dim]: the node positions of this rank, ghost rows included;
  *                 b_positions [n_bdry * dim]: the positions of the boundary_map entries in boundary_map order (NULL
  *                 if n_bdry == 0). Copied to the device once. A second configure replaces the first. Every rank of a
@@ -774,7 +810,18 @@ enum {
   RYUJIN_IV_PARABOLOID = 6,
   RYUJIN_IV_RITTER_DAM_BREAK = 7,
   RYUJIN_IV_SMOOTH_VORTEX = 8,
-  RYUJIN_IV_SLOPING_FRICTION = 9
+  RYUJIN_IV_SLOPING_FRICTION = 9,
+  /* 10: the function state, ryujin_hip_initial_values_configure_function */
+  RYUJIN_IV_CONTRAST = 11,
+  RYUJIN_IV_THREE_STATE_CONTRAST = 12,
+  RYUJIN_IV_FOUR_STATE_CONTRAST = 13,
+  RYUJIN_IV_SHOCK_FRONT = 14,
+  RYUJIN_IV_RAMP_UP = 15,
+  RYUJIN_IV_NOH = 16,
+  RYUJIN_IV_SMOOTH_WAVE = 17,
+  RYUJIN_IV_ASTRO_JET = 18,
+  RYUJIN_IV_SW_UNIFORM = 19,
+  RYUJIN_IV_SW_CONTRAST = 20
 };
 typedef struct ryujin_hip_initial_values {
   int state;           /* RYUJIN_IV_*: "configuration" of subsection "E - InitialValues" */

@@ -149,14 +149,69 @@ IV_STATES = {
 }
 
 
+# The Riemann-data, shock-front, ramp-up and Noh states (RYUJIN_IV_* from 11 on; 10 is the library's own id of the
+# "function" state and refused by ryujin_hip_initial_values_configure). "contrast" and "uniform" exist in two
+# Descriptions, so the key carries the family: ("euler", name) serves Euler and EulerAEOS, ("shallow water", name)
+# shallow water. Value: (RYUJIN_IV_*, parameters) with the parameters as in IV_STATES.
+(IV_CONTRAST, IV_THREE_STATE_CONTRAST, IV_FOUR_STATE_CONTRAST, IV_SHOCK_FRONT, IV_RAMP_UP, IV_NOH, IV_SMOOTH_WAVE,
+ IV_ASTRO_JET, IV_SW_UNIFORM, IV_SW_CONTRAST) = range(11, 21)
+
+IV_LIBRARY_STATES = {
+    ("euler", "contrast"): (IV_CONTRAST, (("primitive state left", 0, (1.4, 0.0, 1.0)),
+                                         ("primitive state right", 3, (1.4, 0.0, 1.0)))),
+    ("euler", "three state contrast"): (IV_THREE_STATE_CONTRAST, (
+        ("primitive state left", 0, (1.0, 0.0, 1.0e3)), ("left region length", 3, 0.1),
+        ("primitive state middle", 4, (1.0, 0.0, 1.0e-2)), ("middle region length", 7, 0.8),
+        ("primitive state right", 8, (1.0, 0.0, 1.0e2)))),
+    ("euler", "four state contrast"): (IV_FOUR_STATE_CONTRAST, (
+        ("primitive state bottom left", 0, (1.4, 0.0, 0.0, 1.0)), ("primitive state bottom right", 4, (1.4, 0.0, 0.0, 1.0)),
+        ("primitive state top left", 8, (1.4, 0.0, 0.0, 1.0)), ("primitive state top right", 12, (1.4, 0.0, 0.0, 1.0)))),
+    ("euler", "shock front"): (IV_SHOCK_FRONT, (("primitive state", 0, (1.4, 0.0, 1.0)), ("mach number", 3, 2.0),
+                                               ("gamma", 4, 1.4))),
+    ("euler", "ramp up"): (IV_RAMP_UP, (("primitive state initial", 0, (1.4, 0.0, 1.0)),
+                                       ("primitive state final", 3, (1.4, 3.0, 1.0)),
+                                       ("time initial", 6, 0.0), ("time final", 7, 1.0))),
+    ("euler", "noh"): (IV_NOH, (("reference density", 0, 1.0), ("reference velocity magnitude", 1, 1.0),
+                               ("reference pressure", 2, 1.0e-12), ("gamma", 3, 1.4))),
+    ("euler", "smooth wave"): (IV_SMOOTH_WAVE, (("reference density", 0, 1.0), ("reference pressure", 1, 1.0),
+                                               ("mach number", 2, 1.0))),
+    ("euler", "astro jet"): (IV_ASTRO_JET, (("jet width", 0, 0.05), ("primitive jet state", 1, (5.0, 30.0, 0.4127)),
+                                           ("primitive ambient right", 4, (5.0, 0.0, 0.4127)),
+                                           ("gamma", 7, 5.0 / 3.0))),
+    ("shallow water", "uniform"): (IV_SW_UNIFORM, (("primitive state", 0, (1.0, 1.0)),)),
+    ("shallow water", "contrast"): (IV_SW_CONTRAST, (("primitive state left", 0, (1.0, 0.0)),
+                                                    ("primitive state right", 2, (1.0, 0.0)))),
+}
+
+
+def iv_family(equation: int) -> str:
+    """the first entry of an IV_LIBRARY_STATES key for an EQ_* value"""
+    if equation in (EQ_EULER, EQ_EULER_AEOS):
+        return "euler"
+    if equation == EQ_SHALLOW_WATER:
+        return "shallow water"
+    return "scalar conservation"
+
+
 def initial_values_struct(name: str, dim: int, direction=None, position=None, perturbation: float = 0.0,
-                          **params) -> InitialValues:
+                          equation=None, **params) -> InitialValues:
     """ryujin_hip_initial_values for a configuration name of the reference with its parameter names (spaces may be
     written as underscores: mach_number=1.0); what is not given takes the reference's default. ValueError for an
-    unknown configuration or parameter."""
-    if name not in IV_STATES:
-        raise ValueError(f"Could not find an initial state description with name \"{name}\"")
-    state, _, spec = IV_STATES[name]
+    unknown configuration or parameter. `equation` (EQ_*) selects among the states of that Description first
+    (IV_LIBRARY_STATES: "uniform" of shallow water is another state than "uniform" of Euler), then in IV_STATES, then
+    among the IV_LIBRARY_STATES of the other Descriptions (which the library refuses); without it the name is looked
+    up in IV_STATES alone."""
+    key = (iv_family(equation), name) if equation is not None else None
+    if key in IV_LIBRARY_STATES:
+        state, spec = IV_LIBRARY_STATES[key]
+    elif name in IV_STATES:
+        state, _, spec = IV_STATES[name]
+    else:
+        # a state of another Description only: the struct is built, the library refuses it with its own status
+        other = [k for k in IV_LIBRARY_STATES if k[1] == name] if equation is not None else []
+        if not other:
+            raise ValueError(f"Could not find an initial state description with name \"{name}\"")
+        state, spec = IV_LIBRARY_STATES[other[0]]
     iv = InitialValues()
     iv.state = state
     given = {k.replace("_", " "): v for k, v in params.items()}

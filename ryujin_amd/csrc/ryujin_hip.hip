@@ -51,6 +51,7 @@
 #include "kernels_postprocessor.hpp"
 #include "kernels_quantities.hpp"
 #include "kernels_initial_values.hpp"
+#include "kernels_initial_values_library.hpp"
 #include "kernels_error_norms.hpp"
 #include "kernels_output.hpp"
 
@@ -1264,6 +1265,19 @@ void ryujin_hip_ctx::initial_values_points(const double *d_points, size_t n, dou
                        d_out);
   } else if constexpr (is_scalar_v<E>) {
     throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: scalar conservation has the function state only");
+  } else if (iv_is_library_state(iv.state)) {
+    /* the states of initial_states_library_device.hpp: kernels of their own */
+    if constexpr (std::is_same<typename E::Params, EulerAeosParams>::value) {
+      if (aeosparams.eos == RYUJIN_EOS_FUNCTION) {
+        hipLaunchKernelGGL(k_initial_values_library_eos_function_points<E::DIMENSION>,
+                           dim3(grid_for(n, kInitialValuesBlock)), dim3(kInitialValuesBlock), 0, stream, iv,
+                           d_eos_function.ptr, (uint32_t)n, d_points, t, stride, d_out);
+        HIP_CHECK(hipGetLastError());
+        return;
+      }
+    }
+    hipLaunchKernelGGL(k_initial_values_library_points<E>, dim3(grid_for(n, kInitialValuesBlock)),
+                       dim3(kInitialValuesBlock), 0, stream, iv, (uint32_t)n, d_points, t, stride, d_out);
   } else if (std::is_same<typename E::Params, EulerAeosParams>::value && aeosparams.eos == RYUJIN_EOS_FUNCTION) {
     /* the analytic state through the sie program of the function equation of state */
     hipLaunchKernelGGL(k_initial_values_eos_function_points<E::DIMENSION>, dim3(grid_for(n, kInitialValuesBlock)),
@@ -1297,6 +1311,24 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStag
       have_dirichlet = true;
     } else if constexpr (is_scalar_v<E>) {
       throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: scalar conservation has the function state only");
+    } else if (iv_is_library_state(iv.state)) {
+      join_export();
+      bool launched = false;
+      if constexpr (std::is_same<typename E::Params, EulerAeosParams>::value) {
+        if (aeosparams.eos == RYUJIN_EOS_FUNCTION) {
+          hipLaunchKernelGGL(k_initial_values_library_eos_function_dirichlet<E::DIMENSION>,
+                             dim3(grid_for(bdry.n_bdry, kInitialValuesBlock)), dim3(kInitialValuesBlock), 0, stream,
+                             iv, d_eos_function.ptr, bdry.n_bdry, d_iv_b_positions.ptr, d_b_id.ptr, iv_stage.t,
+                             iv_stage.c, d_scalars.ptr, d_dirichlet.ptr);
+          launched = true;
+        }
+      }
+      if (!launched)
+        hipLaunchKernelGGL(k_initial_values_library_dirichlet<E>, dim3(grid_for(bdry.n_bdry, kInitialValuesBlock)),
+                           dim3(kInitialValuesBlock), 0, stream, iv, bdry.n_bdry, d_iv_b_positions.ptr, d_b_id.ptr,
+                           iv_stage.t, iv_stage.c, d_scalars.ptr, d_dirichlet.ptr);
+      HIP_CHECK(hipGetLastError());
+      have_dirichlet = true;
     } else if (std::is_same<typename E::Params, EulerAeosParams>::value && aeosparams.eos == RYUJIN_EOS_FUNCTION) {
       join_export();
       hipLaunchKernelGGL(k_initial_values_eos_function_dirichlet<E::DIMENSION>,
@@ -4026,9 +4058,10 @@ namespace
   {
     const int dim = ctx.dim, eq = ctx.params.equation;
     InitialValuesParams P{};
-    if (in.state < RYUJIN_IV_UNIFORM || in.state > RYUJIN_IV_SLOPING_FRICTION)
+    const bool library_state = iv_is_library_state(in.state);
+    if ((in.state < RYUJIN_IV_UNIFORM || in.state > RYUJIN_IV_SLOPING_FRICTION) && !library_state)
       throw HipError(RYUJIN_ERR_ARG, "initial values: unknown state " + std::to_string(in.state));
-    const bool sw_state = in.state >= RYUJIN_IV_CIRCULAR_DAM_BREAK;
+    const bool sw_state = library_state ? in.state >= RYUJIN_IV_SW_UNIFORM : in.state >= RYUJIN_IV_CIRCULAR_DAM_BREAK;
     if (sw_state != (eq == RYUJIN_EQ_SHALLOW_WATER))
       throw HipError(RYUJIN_ERR_ARG, "initial values: the Description of this context has no such state");
     if (in.perturbation != 0.)
@@ -4038,6 +4071,11 @@ namespace
       throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: the vortex states are defined for dim = 2");
     if (in.state == RYUJIN_IV_PARABOLOID && dim != 1)
       throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: paraboloid is offered for dim = 1");
+    if ((in.state == RYUJIN_IV_FOUR_STATE_CONTRAST || in.state == RYUJIN_IV_ASTRO_JET) && dim == 1)
+      throw HipError(RYUJIN_ERR_UNSUPPORTED,
+                     "initial values: four state contrast and astro jet are defined for dim >= 2");
+    if (sw_state && library_state && dim == 3)
+      throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: shallow water is defined for dim = 1 and 2");
     for (int q = 0; q < 16; ++q)
       if (std::isnan(in.params[q]))
         throw HipError(RYUJIN_ERR_ARG, "initial values: NaN parameter");
@@ -4138,13 +4176,75 @@ namespace
       c[1] = in.params[2] / (2.0 * M_PI);
       c[2] = 1.0 / (2.0 * hp.gravity);
       break;
-    default: { /* RYUJIN_IV_SLOPING_FRICTION */
+    case RYUJIN_IV_SLOPING_FRICTION: {
       const double n_m = hp.manning_friction_coefficient, slope = in.params[0], q0 = in.params[1];
       const double exponent = 1.0 / (2.0 + 4.0 / 3.0);
       const double profile = n_m * n_m * q0 * q0 / slope;
       c[0] = std::pow(profile, exponent);
       break;
     }
+    /* the states of initial_states_library_device.hpp (its table of c[]); c[0]: the system's gamma, which
+     * from_primitive_state of Euler divides by */
+    case RYUJIN_IV_THREE_STATE_CONTRAST:
+      c[0] = hp.gamma;
+      c[1] = in.params[3] + in.params[7];
+      break;
+    case RYUJIN_IV_SHOCK_FRONT: {
+      /* the constructor of initial_state_shock_front.h, as initial_states.euler_shock_front_constants */
+      const double gamma = eq == RYUJIN_EQ_EULER ? hp.gamma : in.params[4];
+      const double b = eq == RYUJIN_EQ_EULER ? 0. : ctx.aeosparams.b; /* eos_interpolation_b */
+      const double rho_R = in.params[0], u_R = in.params[1], p_R = in.params[2], mach = in.params[3];
+      const double a_R = std::sqrt(gamma * p_R / rho_R / (1.0 - b * rho_R));
+      const double mach_R = u_R / a_R;
+      const double S3 = mach * a_R;
+      const double delta_mach = mach_R - mach;
+      const double rho_L =
+          rho_R * (gamma + 1.0) * delta_mach * delta_mach / ((gamma - 1.0) * delta_mach * delta_mach + 2.0);
+      const double u_L = (1.0 - rho_R / rho_L) * S3 + rho_R / rho_L * u_R;
+      const double p_L = p_R * (2.0 * gamma * delta_mach * delta_mach - (gamma - 1.0)) / (gamma + 1.0);
+      if (!std::isfinite(rho_L) || !std::isfinite(u_L) || !std::isfinite(p_L) || !std::isfinite(S3))
+        throw HipError(RYUJIN_ERR_ARG, "initial values: shock front: the state behind the shock is not finite");
+      c[0] = hp.gamma;
+      c[1] = rho_L;
+      c[2] = u_L;
+      c[3] = p_L;
+      c[4] = S3;
+      break;
+    }
+    case RYUJIN_IV_NOH: {
+      /* initial_states.euler_noh_constants: pow(., dim) and pow(., dim - 1) as products, left to right */
+      const double gamma = eq == RYUJIN_EQ_EULER ? hp.gamma : in.params[3];
+      if (!(gamma > 1.))
+        throw HipError(RYUJIN_ERR_ARG, "initial values: noh needs gamma > 1");
+      const double rho0 = in.params[0], u0 = in.params[1];
+      const double ratio = (gamma + 1.0) / (gamma - 1.0);
+      double ratio_dim = ratio, plus_dim = gamma + 1.0, minus_dim1 = 1.0;
+      for (int d = 1; d < dim; ++d) {
+        ratio_dim = ratio_dim * ratio;
+        plus_dim = plus_dim * (gamma + 1.0);
+        minus_dim1 = minus_dim1 * (gamma - 1.0);
+      }
+      double p_in = 0.5 * rho0 * u0 * u0;
+      p_in = p_in * (plus_dim / minus_dim1);
+      c[0] = hp.gamma;
+      c[1] = u0 * (gamma - 1.0) / 2.0;
+      c[2] = rho0 * ratio_dim;
+      c[3] = p_in;
+      c[4] = 10. * std::numeric_limits<double>::min();
+      break;
+    }
+    case RYUJIN_IV_SMOOTH_WAVE: {
+      const double left = 0.1, right = 0.3;
+      const double width2 = (right - left) * (right - left);
+      c[0] = hp.gamma;
+      c[1] = width2 * (width2 * width2); /* fixed_power<6>(right - left) */
+      c[2] = left;
+      c[3] = right;
+      break;
+    }
+    default: /* contrast, four state contrast, ramp up, astro jet; uniform and contrast of shallow water */
+      c[0] = hp.gamma;
+      break;
     }
     return P;
   }

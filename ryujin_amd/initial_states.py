@@ -307,3 +307,190 @@ def sw_sloping_friction(positions, manning=0.01, ramp_slope=1.0, initial_dischar
     U[:, 0] = h
     U[:, 1] = initial_discharge
     return U, -ramp_slope * x
+
+
+# ---------------------------------------------------------------------------
+# The Riemann-data, shock-front, ramp-up and Noh states (capi.IV_LIBRARY_STATES). Each function takes the positions in
+# the FRAME OF THE STATE (behind the affine transform of initial_values.template.h:66-148) and returns the primitive
+# state there: (rho, vel [n, dim], p) for Euler / EulerAEOS -- the conserved state is euler_from_primitive or
+# aeos_from_primitive of it, the momentum rotated back --, (h, u) for shallow water. `ramp up` blends two CONSERVED
+# states and returns the weights. The device follows these statements one by one (initial_states_library_device.hpp).
+
+def _frame(positions):
+    x = np.asarray(positions, dtype=np.float64)
+    return x, x.shape[0], x.shape[1]
+
+
+def _piecewise(n, dim, masks_and_states, otherwise):
+    """1-D primitive states (rho, u, p) selected by masks, the first that holds; velocity along the first axis"""
+    rho, u, p = (np.full(n, otherwise[q], dtype=np.float64) for q in range(3))
+    for mask, state in reversed(masks_and_states):
+        rho, u, p = (np.where(mask, state[q], c) for q, c in enumerate((rho, u, p)))
+    vel = np.zeros((n, dim))
+    vel[:, 0] = u
+    return rho, vel, p
+
+
+def euler_contrast_primitive(positions, left=(1.4, 0.0, 1.0), right=(1.4, 0.0, 1.0)):
+    """source/euler/initial_state_contrast.h: `right` where x > 0, else `left`."""
+    x, n, dim = _frame(positions)
+    return _piecewise(n, dim, [(x[:, 0] > 0.0, right)], left)
+
+
+def euler_three_state_contrast_primitive(positions, left=(1.0, 0.0, 1.0e3), left_length=0.1,
+                                         middle=(1.0, 0.0, 1.0e-2), middle_length=0.8, right=(1.0, 0.0, 1.0e2)):
+    """source/euler/initial_state_three_state_contrast.h: x >= left_length + middle_length -> right,
+    x >= left_length -> middle, else left."""
+    x, n, dim = _frame(positions)
+    return _piecewise(n, dim, [(x[:, 0] >= left_length + middle_length, right), (x[:, 0] >= left_length, middle)],
+                      left)
+
+
+def euler_four_state_contrast_primitive(positions, bottom_left=(1.4, 0.0, 0.0, 1.0), bottom_right=(1.4, 0.0, 0.0, 1.0),
+                                        top_left=(1.4, 0.0, 0.0, 1.0), top_right=(1.4, 0.0, 0.0, 1.0)):
+    """source/euler/initial_state_four_state_contrast.h (dim >= 2): states (rho, u, v, p); x >= 0 selects right,
+    y >= 0 selects top; a third velocity component is zero (expand_state)."""
+    x, n, dim = _frame(positions)
+    if dim == 1:
+        raise ValueError("four state contrast is not defined for dim = 1")
+    east, north = x[:, 0] >= 0.0, x[:, 1] >= 0.0
+    top = [np.where(east, top_right[q], top_left[q]) for q in range(4)]
+    bottom = [np.where(east, bottom_right[q], bottom_left[q]) for q in range(4)]
+    rho, u, v, p = (np.where(north, top[q], bottom[q]) for q in range(4))
+    vel = np.zeros((n, dim))
+    vel[:, 0], vel[:, 1] = u, v
+    return rho, vel, p
+
+
+def euler_shock_front_constants(right=(1.4, 0.0, 1.0), mach=2.0, gamma=1.4, b=0.0):
+    """The constructor of source/euler/initial_state_shock_front.h: (primitive left state (rho, u, p), S3) of the
+    shock that runs into `right` with Mach number `mach`; b: the covolume of the interpolatory equation of state
+    (eos_interpolation_b; 0 for Euler)."""
+    rho_R, u_R, p_R = (float(c) for c in right)
+    a_R = np.sqrt(gamma * p_R / rho_R / (1.0 - b * rho_R))
+    mach_R = u_R / a_R
+    S3 = mach * a_R
+    delta_mach = mach_R - mach
+    rho_L = rho_R * (gamma + 1.0) * delta_mach * delta_mach / ((gamma - 1.0) * delta_mach * delta_mach + 2.0)
+    u_L = (1.0 - rho_R / rho_L) * S3 + rho_R / rho_L * u_R
+    p_L = p_R * (2.0 * gamma * delta_mach * delta_mach - (gamma - 1.0)) / (gamma + 1.0)
+    return (float(rho_L), float(u_L), float(p_L)), float(S3)
+
+
+def euler_shock_front_primitive(positions, t, right=(1.4, 0.0, 1.0), mach=2.0, gamma=1.4, b=0.0):
+    """source/euler/initial_state_shock_front.h: `right` where x - S3 t > 0, else the post-shock state."""
+    x, n, dim = _frame(positions)
+    left, S3 = euler_shock_front_constants(right, mach, gamma, b)
+    position_1d = x[:, 0] - S3 * t
+    return _piecewise(n, dim, [(position_1d > 0.0, right)], left)
+
+
+def euler_ramp_up_weights(t, time_initial=0.0, time_final=1.0):
+    """source/euler/initial_state_ramp_up.h: (alpha, beta) of result = alpha U_initial + beta U_final with the two
+    CONSERVED states; (1, 0) up to time_initial and (0, 1) from time_final on mean "the state itself", unblended."""
+    if t <= time_initial:
+        return 1.0, 0.0
+    if t >= time_final:
+        return 0.0, 1.0
+    factor = np.cos(0.5 * np.pi * (t - time_initial) / (time_final - time_initial))
+    alpha = factor * factor
+    return float(alpha), float(1.0 - alpha)
+
+
+def ramp_up_blend(U_initial, U_final, t, time_initial=0.0, time_final=1.0):
+    """the blend of euler_ramp_up_weights on conserved states [n, k]"""
+    if t <= time_initial:
+        return np.array(U_initial, dtype=np.float64)
+    if t >= time_final:
+        return np.array(U_final, dtype=np.float64)
+    alpha, beta = euler_ramp_up_weights(t, time_initial, time_final)
+    return alpha * np.asarray(U_initial) + beta * np.asarray(U_final)
+
+
+NOH_MIN = 10.0 * float(np.finfo(np.float64).tiny)
+
+
+def euler_noh_constants(dim, rho0=1.0, u0=1.0, gamma=1.4):
+    """(D, interior density, interior pressure) of source/euler/initial_state_noh.h; the integer powers
+    pow(., dim) and pow(., dim - 1) written out as products, left to right."""
+    D = u0 * (gamma - 1.0) / 2.0
+    ratio = (gamma + 1.0) / (gamma - 1.0)
+    ratio_dim, plus_dim, minus_dim1 = ratio, gamma + 1.0, 1.0
+    for _ in range(dim - 1):
+        ratio_dim = ratio_dim * ratio
+        plus_dim = plus_dim * (gamma + 1.0)
+        minus_dim1 = minus_dim1 * (gamma - 1.0)
+    rho_in = rho0 * ratio_dim
+    p_in = 0.5 * rho0 * u0 * u0
+    p_in = p_in * (plus_dim / minus_dim1)
+    return float(D), float(rho_in), float(p_in)
+
+
+def euler_noh_primitive(positions, t, rho0=1.0, u0=1.0, p0=1.0e-12, gamma=1.4):
+    """source/euler/initial_state_noh.h: the radial implosion; velocity -u0 x / (|x| + min) in ALL dim components,
+    min = 10 DBL_MIN; inside the shock |x| / t < D the state at rest, outside rho0 (1 + t / (|x| + min))^(dim - 1);
+    t == 0 is never interior."""
+    x, n, dim = _frame(positions)
+    D, rho_in, p_in = euler_noh_constants(dim, rho0, u0, gamma)
+    norm2 = x[:, 0] * x[:, 0]
+    for d in range(1, dim):
+        norm2 = norm2 + x[:, d] * x[:, d]
+    norm = np.sqrt(norm2)
+    denominator = norm + NOH_MIN
+    interior = np.zeros(n, dtype=bool) if t == 0.0 else norm / t < D
+    growth = 1.0 + t / denominator
+    power = np.ones(n)
+    for _ in range(dim - 1):
+        power = power * growth
+    rho = np.where(interior, rho_in, rho0 * power)
+    vel = np.where(interior[:, None], 0.0 * x, (-u0 * x) / denominator[:, None])
+    p = np.where(interior, p_in, p0)
+    return rho, vel, p
+
+
+SMOOTH_WAVE_LEFT, SMOOTH_WAVE_RIGHT = 0.1, 0.3
+
+
+def fixed_power_3(x):
+    """dealii::Utilities::fixed_power<3>: x * ((x * x) * 1)"""
+    return x * (x * x)
+
+
+def fixed_power_6(x):
+    """dealii::Utilities::fixed_power<6>(x) = fixed_power<3>(x * x)"""
+    x2 = x * x
+    return x2 * (x2 * x2)
+
+
+def euler_smooth_wave_primitive(positions, t, rho_ref=1.0, p_ref=1.0, mach=1.0):
+    """source/euler/initial_state_smooth_wave.h: rho_ref + 64 (x - x0)^3 (x1 - x)^3 / (x1 - x0)^6 on
+    x0 = 0.1 <= x - mach t <= x1 = 0.3, rho_ref elsewhere; velocity `mach` along the first axis, pressure p_ref."""
+    x, n, dim = _frame(positions)
+    left, right = SMOOTH_WAVE_LEFT, SMOOTH_WAVE_RIGHT
+    xb = x[:, 0] - mach * t
+    polynomial = 64.0 * fixed_power_3(xb - left) * fixed_power_3(right - xb) / fixed_power_6(right - left)
+    rho = np.where((left <= xb) & (xb <= right), rho_ref + polynomial, rho_ref)
+    vel = np.zeros((n, dim))
+    vel[:, 0] = mach
+    return rho, vel, np.full(n, float(p_ref))
+
+
+def euler_astro_jet_primitive(positions, jet_width=0.05, jet=(5.0, 30.0, 0.4127), ambient=(5.0, 0.0, 0.4127)):
+    """source/euler/initial_state_astro_jet.h (dim >= 2): the jet state where x < 1e-12 and |y| <= jet_width."""
+    x, n, dim = _frame(positions)
+    if dim == 1:
+        raise ValueError("astro jet is not defined for dim = 1")
+    return _piecewise(n, dim, [((x[:, 0] < 1.0e-12) & (np.abs(x[:, 1]) <= jet_width), jet)], ambient)
+
+
+def sw_uniform_primitive(positions, state=(1.0, 1.0)):
+    """source/shallow_water/initial_state_uniform.h: (h, u) everywhere, zero bathymetry."""
+    x, n, _ = _frame(positions)
+    return np.full(n, float(state[0])), np.full(n, float(state[1]))
+
+
+def sw_contrast_primitive(positions, left=(1.0, 0.0), right=(1.0, 0.0)):
+    """source/shallow_water/initial_state_contrast.h: `right` where x > 0, else `left`; zero bathymetry."""
+    x, n, _ = _frame(positions)
+    east = x[:, 0] > 0.0
+    return np.where(east, right[0], left[0]), np.where(east, right[1], left[1])

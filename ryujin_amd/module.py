@@ -257,7 +257,8 @@ class HyperbolicModule:
         """Select the analytic state of subsection "E - InitialValues" (ryujin_hip_initial_values_configure):
         `name` and the parameter names are the reference's ("isentropic vortex", mach_number=1.0 for "mach number");
         the node and boundary positions come from the offline data. A second call replaces the first."""
-        iv = capi.initial_values_struct(name, self.dim, direction, position, perturbation, **params)
+        iv = capi.initial_values_struct(name, self.dim, direction, position, perturbation,
+                                        equation=self.equation, **params)
         pos = np.ascontiguousarray(self.offline.positions, dtype=np.float64).reshape(-1)
         assert pos.size == self.n_relevant * self.dim
         bpos = np.ascontiguousarray(self.offline.b_positions, dtype=np.float64).reshape(-1) \
