@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import helpers_row_width_cases as row_width_cases
+import helpers_small_meshes as small_meshes
 from ryujin_amd import _build, capi, offline
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,8 +38,18 @@ MESHES = {
     "box": lambda: offline.SyntheticOffline(offline.box_3d(20)),
     "wide": row_width_cases._lattice(row_width_cases.PLANE, 33),   # rows of 33 entries: no lower_mask
     "flat": lambda: offline.SyntheticOffline(offline.rectangle_2d(200, ny=12)),   # 13 lattice rows of 201 nodes
+    # ranks and meshes at and below one slice (tests/helpers_small_meshes.py): a 1-D middle rank that exports both of
+    # its rows and has no boundary row, a 2-D middle rank that exports all 16, rank 0 of 2 of the 3-D box (50 rows)
+    "small_line_mid": lambda: offline.SyntheticOffline(small_meshes.RANK_CASES["line_5_of_3"][1](3, 1)),
+    "small_plane_mid": lambda: offline.SyntheticOffline(small_meshes.RANK_CASES["plane_7x7_of_4"][1](4, 1)),
+    "small_box_0of2": lambda: offline.SyntheticOffline(small_meshes.RANK_CASES["box_4_of_2"][1](2, 0)),
 }
-TABLE_MESHES = ["step", "step_0of3", "step_1of3", "line", "box", "wide"]
+# ... and the single-rank meshes of 2, 64, 65, 4, 63, 8 and 27 rows
+SMALL = {"small_2": "euler_1d_1", "small_64": "euler_1d_63", "small_65": "euler_2d_12x4", "small_4": "euler_2d_1x1",
+         "small_63": "euler_2d_8x6", "small_8": "euler_3d_1x1x1", "small_27": "euler_3d_2x2x2"}
+MESHES.update({key: small_meshes.CASES[name]["mesh"] for key, name in SMALL.items()})
+TABLE_MESHES = ["step", "step_0of3", "step_1of3", "line", "box", "wide", "small_line_mid", "small_plane_mid",
+                "small_box_0of2"] + sorted(SMALL)
 
 
 @pytest.fixture(scope="module")
@@ -226,7 +237,8 @@ def test_export_slices(checker, meshes, name):
         assert r["n_export_slices"] == lowered // WAVE and r["interior_rows_read_ghosts"] == 1
 
 
-@pytest.mark.parametrize("name, n_nbr", [("step", 0), ("step_0of3", 1), ("step_1of3", 2)])
+@pytest.mark.parametrize("name, n_nbr", [("step", 0), ("step_0of3", 1), ("step_1of3", 2), ("small_line_mid", 2),
+                                         ("small_plane_mid", 2), ("small_box_0of2", 1)])
 def test_exchange_tables(tables, name, n_nbr):
     e, r, _ = tables(name)
     assert r["n_nbr"] == e.o.n_nbr == n_nbr

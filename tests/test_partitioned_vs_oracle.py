@@ -80,6 +80,49 @@ def test_partitioned_oracle_helper_reproduces_the_single_rank_oracle(oracle):
         assert (np.abs(states[r][: part.n_owned] - U_ref[rows]) / scale).max() < 1e-12
 
 
+import helpers_small_meshes as small_meshes  # noqa: E402
+
+
+@pytest.mark.parametrize("name, equation", [(n, e) for n in sorted(small_meshes.RANK_CASES)
+                                            for e in small_meshes.RANK_CASES[n][4]])
+def test_partitioned_oracle_helper_reproduces_the_single_rank_oracle_on_small_ranks(oracle, name, equation):
+    """CPU: the yardstick of tests/test_gpu_small_meshes.py -- ranks with fewer than 64 rows, ranks that export every
+    row, ranks without a boundary row (tests/helpers_small_meshes.py). Two updates on the oracle ranks, then the update
+    the GPU test compares: its U against the single-rank oracle, and on the 2-D and 3-D meshes the non-vacuity condition
+    of _compare_partitioned on the oracle's ghost rows alone."""
+    from ryujin_amd import HyperbolicModule
+    dim, recipe, n_ranks, counts, _ = small_meshes.RANK_CASES[name]
+    specs, parts = small_meshes.rank_parts(name)
+    if counts is not None:
+        assert [small_meshes.rank_counts(p) for p in parts] == counts
+    assert tuple(p.n_owned for p in parts) == small_meshes.RANK_N_OWNED.get(name, tuple(p.n_owned for p in parts))
+    assert tuple(p.n_export for p in parts) == small_meshes.RANK_N_EXPORT.get(name, tuple(p.n_export for p in parts))
+    make = _params(oracle, small_meshes.EQUATIONS[equation], dim)
+    run = lambda *a: run_oracle_ranks(oracle, *a)  # noqa: E731
+    states = _develop_on(run, parts, make, small_meshes.rank_states(equation, specs, parts), 2, None)
+    ref = run(parts, make, one_update_with_intermediates(states, None))
+    single_spec = recipe(1, 0)
+    single = offline.SyntheticOffline(single_spec)
+    assert single.n_owned == sum(p.n_owned for p in parts)
+    m = HyperbolicModule(single, make(), backend=oracle.backend())
+    a, b = m.new_state_vector(small_meshes.state(equation, single_spec, single.positions)), m.new_state_vector()
+    for _ in range(3):
+        m.prepare_state_vector(a, 0.0, None)
+        m.step(a, [], [], b)
+        assert m.last_status == 0
+        a, b = b, a
+    U_ref = a.download()
+    lookup = {int(g): i for i, g in enumerate(single.global_ids)}
+    scale = np.abs(U_ref).max(axis=0)
+    for r, part in enumerate(parts):
+        rows = [lookup[int(g)] for g in part.global_ids[: part.n_owned]]
+        assert ref[r]["status"] == 0 and np.isfinite(ref[r]["U"]).all()
+        assert (np.abs(ref[r]["U"] - U_ref[rows]) / scale).max() < 1e-12
+    if dim > 1:
+        ghost_l = np.concatenate([ref[r]["lij_next"][int(parts[r].row_starts[parts[r].n_owned]):] for r in range(n_ranks)])
+        assert ghost_l.size and ghost_l.min() < 1.0
+
+
 def _compare_partitioned(oracle, parts, equation, dim, U_init, dirichlet_of, n_warm, cfl=0.9):
     make = _params(oracle, equation, dim, cfl)
     k = {capi.EQ_EULER: dim + 2, capi.EQ_SHALLOW_WATER: dim + 1}[equation]

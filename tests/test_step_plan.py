@@ -261,6 +261,51 @@ def test_case_table_of_the_row_widths_on_ranks_is_what_plan_step_decides(checker
                             [dict(n_slices=s, grid_y=1, shares_slices=b) for s, _, b in expected["launches"]])
 
 
+# ---- the case table of tests/test_gpu_small_meshes.py against plan_step()
+
+import helpers_small_meshes as small_cases  # noqa: E402
+
+
+@pytest.mark.parametrize("name", sorted(small_cases.CASES))
+def test_case_table_of_the_small_meshes_is_what_plan_step_decides(checker, name):
+    """Every entry of tests/helpers_small_meshes.py: the mesh is built, n_owned and the widest row are taken from it, and
+    the plan and the launches plan_step() makes of them -- as the mesh selects its kernels, and with
+    debug_no_small_mesh_split -- must equal the table's literals; for the cases that also run ERK33 stages and the
+    checked kernels, those plans as well. (debug_bc_fold_max_slices decides no field of the plan of a step() outside
+    the device-resident driver.)"""
+    case = small_cases.CASES[name]
+    off = case["mesh"]()
+    widths = plan_cases.widths_of(off)
+    assert off.n_owned == case["n_points"] and widths.max() == case["width"]
+    assert (off.n_owned + 63) // 64 == case["n_slices"]
+    for run, options in enumerate(((), ("no_split=1",))):
+        launches = case["launches"][run]
+        sizes = [q["n_slices"] for q in launches["step5_launches"]]
+        n_slices, r = _checked_plan(checker, case["equation"], off.dim, widths, off.n_owned, 1.0, 0, sizes + list(options))
+        _assert_table_entry(r, n_slices, case["plans"][run], launches["step5_launches"], launches["step6_launches"])
+        # the tile mask from step 6 to step 7, from the pinned literals (tests/test_step_plan_next_tile_mask.py holds
+        # this expression against plan_step())
+        plan = case["plans"][run]
+        assert case["tile_mask"][run] == (plan["step6"] == "cached" and plan["step7"] == "last_cached" and off.dim <= 2
+                                          and not plan["checked"]
+                                          and not any(q["shares_slices"] for q in launches["step6_launches"]))
+    if name in small_cases.SUBSET:
+        for (plan, launches), stages, options in ((small_cases.stage_plan(name), 1, ()),
+                                                  (small_cases.stage_plan(name), 2, ()),
+                                                  (small_cases.checked_plan(name), 0, ("checked=1",))):
+            n_slices, r = _checked_plan(checker, case["equation"], off.dim, widths, off.n_owned, 1.0, stages,
+                                        [case["n_slices"]] + list(options))
+            _assert_table_entry(r, n_slices, plan, launches["step5_launches"], launches["step6_launches"])
+
+
+def test_case_table_of_the_small_meshes_covers_the_slice_counts_and_row_widths():
+    """one, two and three slices; widest rows of 2, 3, 4, 8, 9, 18 and 27 entries; every case of the subset exists"""
+    assert {c["n_slices"] for c in small_cases.CASES.values()} == {1, 2, 3}
+    assert {c["width"] for c in small_cases.CASES.values()} == {2, 3, 4, 8, 9, 18, 27}
+    assert {c["n_points"] for c in small_cases.CASES.values()} >= {2, 4, 8, 63, 64, 65}
+    assert set(small_cases.SUBSET) <= set(small_cases.CASES) and len(small_cases.CASES) == 76
+
+
 # ---- the dG case table of tests/test_gpu_dg_variants.py against plan_step()
 
 import helpers_dg_cases as dg_cases  # noqa: E402
