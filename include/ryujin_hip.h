@@ -730,7 +730,8 @@ int ryujin_hip_quantities_time_series(ryujin_hip_ctx *ctx, int manifold, double 
  *   RYUJIN_IV_LEBLANC            euler/initial_state_leblanc.h:63-120           none (gamma = 5/3 is part of the state)
  *   RYUJIN_IV_RAREFACTION        euler/initial_state_rarefaction.h:40-160       0 "gamma" [1.4] (EulerAEOS only)
  * Euler takes gamma from ryujin_hip_params. Shallow water (gravity and the Manning coefficient from ryujin_hip_params;
- * the bathymetry stays what ryujin_hip_create was given as initial_precomputed):
+ * the bathymetry stays what ryujin_hip_create was given as initial_precomputed until
+ * ryujin_hip_initial_values_interpolate_initial_precomputed below replaces it):
  *   RYUJIN_IV_CIRCULAR_DAM_BREAK shallow_water/initial_state_circular_dam_break.h:48-54   0 "still water depth",
  *                                                                               1 "radius", 2 "dam amplitude"
  *   RYUJIN_IV_PARABOLOID         shallow_water/initial_state_paraboloid.h:66-101 (dim = 1)  0 "free surface radius",
@@ -777,9 +778,24 @@ int ryujin_hip_quantities_time_series(ryujin_hip_ctx *ctx, int manifold, double 
  *   RYUJIN_IV_SW_UNIFORM           shallow_water/initial_state_uniform.h     0-1 "primitive state" (h, u) [1, 1]
  *   RYUJIN_IV_SW_CONTRAST          shallow_water/initial_state_contrast.h    0-1 "primitive state left", 2-3 "primitive
  *                                  state right"; right where x > 0
- * Not offered: "icf like", "becker solution" (it needs the Navier-Stokes parameters), the shallow-water states that
- * bring a bathymetry of their own ("flow over bump", "three bumps dam break", "hou test", "transient", "soliton",
- * "geotiff"), perturbation != 0.
+ * The shallow-water states that bring their own bathymetry (values from 21 on; shallow water only, gravity from
+ * ryujin_hip_params). They have a device function of their own, initial_state_sw_bathymetry<dim>()
+ * (ryujin_amd/csrc/initial_states_bathymetry_device.hpp), and kernels of their own. A state is (h, q): depth and
+ * discharge along the first axis behind the transform. A selector slot takes one of its integer values:
+ *   RYUJIN_IV_SW_FLOW_OVER_BUMP          shallow_water/initial_state_flow_over_bump.h (dim = 1, 2)
+ *                                        0 "flow type": 0 transcritical [default], 1 subsonic
+ *   RYUJIN_IV_SW_THREE_BUMPS_DAM_BREAK   shallow_water/initial_state_three_bumps_dam_break.h (dim = 1: one cone; 2)
+ *                                        0 "well balancing validation": 0 false [default], 1 true; 1 "left water depth"
+ *                                        [1.875]; 2 "right water depth" [0]; 3 "cone magnitude" [1]
+ *   RYUJIN_IV_SW_HOU_TEST                shallow_water/initial_state_hou_test.h (dim = 2)
+ *                                        0 "reservoir water depth" [35]
+ *   RYUJIN_IV_SW_TRANSIENT               shallow_water/initial_state_transient.h, "transient experiments" (dim = 2)
+ *                                        0-1 "flow state left" (h, q) [1, 0]; 2-3 "flow state right" [1, 0];
+ *                                        4 "experimental configuration": 0 G1 [default], 1 G2, 2 G3, 3 none
+ *   RYUJIN_IV_SW_SOLITON                 shallow_water/initial_state_soliton.h (dim = 1, 2)
+ *                                        0 "still water depth" [1]; 1 "amplitude" [0.1]
+ * Not offered: "icf like", "becker solution" (it needs the Navier-Stokes parameters), "geotiff" (it needs GDAL),
+ * perturbation != 0.
  *
  *   configure     positions [n_relevant * dim]: the node positions of this rank, ghost rows included;
  *                 b_positions [n_bdry * dim]: the positions of the boundary_map entries in boundary_map order (NULL
@@ -796,10 +812,28 @@ int ryujin_hip_quantities_time_series(ryujin_hip_ctx *ctx, int manifold, double 
  *                 host function is called and nothing crosses PCIe; one host synchronisation per RK step, at its
  *                 end. All seven schemes, bang-bang recovery with its internal re-run included. A rank without
  *                 boundary entries launches nothing for it.
+ *
+ * The bathymetry: InitialValues::interpolate_initial_precomputed_vector (initial_values.template.h:181-185, 270-300),
+ * initial_precomputations(affine_transform(point)) of the configured state. Valid after any configure or
+ * configure_function; RYUJIN_ERR_UNSUPPORTED on a Description with n_initial_precomputed == 0 (everything but shallow
+ * water). "paraboloid", "sloping friction", "flow over bump", "three bumps dam break", "hou test" and "transient
+ * experiments" have a bed; every other state -- "soliton" and the function state included, whose bathymetry member the
+ * reference never reads -- gives exact zeros, the default of the base class.
+ *   interpolate_initial_precomputed   the context's bathymetry := the bed at ALL n_relevant node positions (ghost
+ *                 rows are evaluated like owned ones: nothing to exchange). An enqueue on the context's stream. It
+ *                 replaces what ryujin_hip_create was given as initial_precomputed.
+ *   evaluate_initial_precomputed      out [n * n_initial_precomputed] = the bed at points [n * dim]; n = 0 returns
+ *                 RYUJIN_OK and writes nothing. Waits for the context's stream.
+ *   ryujin_hip_get_initial_precomputed   out [n_relevant * n_initial_precomputed] = what the context holds now: until
+ *                 interpolate_initial_precomputed is called, what ryujin_hip_create was given, or zeros. Like the
+ *                 other two it needs a configure or configure_function first (RYUJIN_ERR_ARG before one), also to
+ *                 read back what create was given.
+ *
  * RYUJIN_ERR_ARG: an unknown state or one the context's Description does not have, a zero direction, NULL positions,
- * any entry but configure before configure. RYUJIN_ERR_UNSUPPORTED: scalar conservation (its only state in the
- * reference is the expression-defined "function" state: ryujin_hip_initial_values_configure_function below),
- * perturbation != 0 (an unseeded generator in the reference), a state in a dimension it is not defined for. */
+ * a selector slot that is not one of its integer values, any entry but configure before configure.
+ * RYUJIN_ERR_UNSUPPORTED: scalar conservation (its only state in the reference is the expression-defined "function"
+ * state: ryujin_hip_initial_values_configure_function below), perturbation != 0 (an unseeded generator in the
+ * reference), a state in a dimension it is not defined for. */
 enum {
   RYUJIN_IV_UNIFORM = 0,
   RYUJIN_IV_RADIAL_CONTRAST = 1,
@@ -821,7 +855,12 @@ enum {
   RYUJIN_IV_SMOOTH_WAVE = 17,
   RYUJIN_IV_ASTRO_JET = 18,
   RYUJIN_IV_SW_UNIFORM = 19,
-  RYUJIN_IV_SW_CONTRAST = 20
+  RYUJIN_IV_SW_CONTRAST = 20,
+  RYUJIN_IV_SW_FLOW_OVER_BUMP = 21,
+  RYUJIN_IV_SW_THREE_BUMPS_DAM_BREAK = 22,
+  RYUJIN_IV_SW_HOU_TEST = 23,
+  RYUJIN_IV_SW_TRANSIENT = 24,
+  RYUJIN_IV_SW_SOLITON = 25
 };
 typedef struct ryujin_hip_initial_values {
   int state;           /* RYUJIN_IV_*: "configuration" of subsection "E - InitialValues" */
@@ -834,6 +873,10 @@ int ryujin_hip_initial_values_configure(ryujin_hip_ctx *ctx, const ryujin_hip_in
                                         const double *positions, const double *b_positions);
 int ryujin_hip_initial_values_evaluate(ryujin_hip_ctx *ctx, const double *points, size_t n, double t, double *out);
 int ryujin_hip_initial_values_interpolate(ryujin_hip_ctx *ctx, int handle, double t);
+int ryujin_hip_initial_values_interpolate_initial_precomputed(ryujin_hip_ctx *ctx);
+int ryujin_hip_initial_values_evaluate_initial_precomputed(ryujin_hip_ctx *ctx, const double *points, size_t n,
+                                                           double *out);
+int ryujin_hip_get_initial_precomputed(ryujin_hip_ctx *ctx, double *out /* [n_relevant * n_initial_precomputed] */);
 int ryujin_hip_prepare_state_vector_iv(ryujin_hip_ctx *ctx, int handle, double t);
 int ryujin_hip_time_step_iv(ryujin_hip_ctx *ctx, int scheme, int h_state, int n_tmp, const int *h_tmp, double t,
                             double tau_max, int cfl_recovery, double cfl_min, double cfl_max, double *tau_out);

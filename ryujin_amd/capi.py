@@ -184,6 +184,38 @@ IV_LIBRARY_STATES = {
 }
 
 
+# The shallow-water states that bring their own bathymetry (RYUJIN_IV_* from 21 on), keyed like IV_LIBRARY_STATES. A
+# selector parameter -- a string or a boolean of the reference -- has a fourth entry: its values in slot order, the
+# slot holds the index; the fifth is the reference's message for any other string.
+(IV_SW_FLOW_OVER_BUMP, IV_SW_THREE_BUMPS_DAM_BREAK, IV_SW_HOU_TEST, IV_SW_TRANSIENT, IV_SW_SOLITON) = range(21, 26)
+
+IV_BATHYMETRY_STATES = {
+    ("shallow water", "flow over bump"): (IV_SW_FLOW_OVER_BUMP, (
+        ("flow type", 0, "transcritical", ("transcritical", "subsonic"),
+         "Flow type must be 'transcritical' or 'subsonic'. "),)),
+    ("shallow water", "three bumps dam break"): (IV_SW_THREE_BUMPS_DAM_BREAK, (
+        ("well balancing validation", 0, False, (False, True), "\"well balancing validation\" takes a boolean"),
+        ("left water depth", 1, 1.875), ("right water depth", 2, 0.0), ("cone magnitude", 3, 1.0))),
+    ("shallow water", "hou test"): (IV_SW_HOU_TEST, (("reservoir water depth", 0, 35.0),)),
+    ("shallow water", "transient experiments"): (IV_SW_TRANSIENT, (
+        ("flow state left", 0, (1.0, 0.0)), ("flow state right", 2, (1.0, 0.0)),
+        ("experimental configuration", 4, "G1", ("G1", "G2", "G3", "none"),
+         "Case must be 'G1', 'G2', 'G3' or 'none'"))),
+    ("shallow water", "soliton"): (IV_SW_SOLITON, (("still water depth", 0, 1.0), ("amplitude", 1, 0.1))),
+}
+
+
+def iv_selector_slot(pname: str, value, choices, message: str) -> float:
+    """the slot value of a selector parameter: the index of a string or boolean of the reference among `choices`, or
+    a number that is passed on as it is (the library refuses what is none of the indices)"""
+    if isinstance(value, (str, bool, np.bool_)):
+        value = bool(value) if isinstance(value, np.bool_) else value
+        if isinstance(value, type(choices[0])) and value in choices:
+            return float(choices.index(value))
+        raise ValueError(message)
+    return float(value)
+
+
 def iv_family(equation: int) -> str:
     """the first entry of an IV_LIBRARY_STATES key for an EQ_* value"""
     if equation in (EQ_EULER, EQ_EULER_AEOS):
@@ -204,19 +236,25 @@ def initial_values_struct(name: str, dim: int, direction=None, position=None, pe
     key = (iv_family(equation), name) if equation is not None else None
     if key in IV_LIBRARY_STATES:
         state, spec = IV_LIBRARY_STATES[key]
+    elif key in IV_BATHYMETRY_STATES:
+        state, spec = IV_BATHYMETRY_STATES[key]
     elif name in IV_STATES:
         state, _, spec = IV_STATES[name]
     else:
         # a state of another Description only: the struct is built, the library refuses it with its own status
-        other = [k for k in IV_LIBRARY_STATES if k[1] == name] if equation is not None else []
+        tables = {**IV_LIBRARY_STATES, **IV_BATHYMETRY_STATES}
+        other = [k for k in tables if k[1] == name] if equation is not None else []
         if not other:
             raise ValueError(f"Could not find an initial state description with name \"{name}\"")
-        state, spec = IV_LIBRARY_STATES[other[0]]
+        state, spec = tables[other[0]]
     iv = InitialValues()
     iv.state = state
     given = {k.replace("_", " "): v for k, v in params.items()}
-    for pname, slot, default in spec:
+    for pname, slot, default, *selector in spec:
         value = given.pop(pname, default)
+        if selector:
+            iv.params[slot] = iv_selector_slot(pname, value, *selector)
+            continue
         values = tuple(value) if isinstance(default, tuple) else (value,)
         if len(values) != (len(default) if isinstance(default, tuple) else 1):
             raise ValueError(f"parameter \"{pname}\" of \"{name}\" takes {len(default)} values")
@@ -467,6 +505,8 @@ HIP_SYMBOLS = [
     "ryujin_hip_initial_values_configure", "ryujin_hip_initial_values_evaluate",
     "ryujin_hip_initial_values_interpolate", "ryujin_hip_prepare_state_vector_iv", "ryujin_hip_time_step_iv",
     "ryujin_hip_initial_values_configure_function", "ryujin_hip_expression_evaluate",
+    "ryujin_hip_initial_values_interpolate_initial_precomputed",
+    "ryujin_hip_initial_values_evaluate_initial_precomputed", "ryujin_hip_get_initial_precomputed",
     "ryujin_hip_error_norms_configure", "ryujin_hip_error_norms_compute",
     "ryujin_hip_flux_configure_function", "ryujin_hip_flux_function_evaluate", "ryujin_hip_flux_info",
     "ryujin_hip_eos_configure_function", "ryujin_hip_eos_function_evaluate",
@@ -583,6 +623,9 @@ def load_hip():
         lib.ryujin_hip_initial_values_configure.argtypes = [vp, C.POINTER(InitialValues), c_double_p, c_double_p]
         lib.ryujin_hip_initial_values_evaluate.argtypes = [vp, c_double_p, C.c_size_t, C.c_double, c_double_p]
         lib.ryujin_hip_initial_values_interpolate.argtypes = [vp, C.c_int, C.c_double]
+        lib.ryujin_hip_initial_values_interpolate_initial_precomputed.argtypes = [vp]
+        lib.ryujin_hip_initial_values_evaluate_initial_precomputed.argtypes = [vp, c_double_p, C.c_size_t, c_double_p]
+        lib.ryujin_hip_get_initial_precomputed.argtypes = [vp, c_double_p]
         lib.ryujin_hip_prepare_state_vector_iv.argtypes = [vp, C.c_int, C.c_double]
         lib.ryujin_hip_time_step_iv.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int_p, C.c_double, C.c_double,
                                                 C.c_int, C.c_double, C.c_double, c_double_p]

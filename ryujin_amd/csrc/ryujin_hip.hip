@@ -51,6 +51,7 @@
 #include "kernels_postprocessor.hpp"
 #include "kernels_quantities.hpp"
 #include "kernels_initial_values.hpp"
+#include "kernels_initial_values_bathymetry.hpp"
 #include "kernels_initial_values_library.hpp"
 #include "kernels_error_norms.hpp"
 #include "kernels_output.hpp"
@@ -519,7 +520,16 @@ struct ryujin_hip_ctx {
       throw HipError(RYUJIN_ERR_ARG, "initial values: not configured (ryujin_hip_initial_values_configure)");
   }
   template <typename E>
-  void initial_values_points(const double *d_points, size_t n, double t, int stride, double *d_out);
+  void initial_values_points(const double *d_points, size_t n, double t, int stride, double *d_out,
+                             bool nodes = false);
+  /* the bathymetry of the configured state (kernels_initial_values_bathymetry.hpp), shallow water only */
+  void require_initial_precomputed() const
+  {
+    require_initial_values();
+    if (params.equation != RYUJIN_EQ_SHALLOW_WATER)
+      throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: this Description has no initial_precomputed values");
+  }
+  void initial_precomputed_points(const double *d_points, size_t n, double *d_out, bool nodes);
 
   struct State {
     DeviceBuffer<double> U, prec;
@@ -1253,13 +1263,49 @@ void ryujin_hip_ctx::store_pij_for_debug()
   HIP_CHECK(hipStreamSynchronize(stream));
 }
 
-/* one thread per point (k_initial_values_points) on the compute stream */
-template <typename E>
-void ryujin_hip_ctx::initial_values_points(const double *d_points, size_t n, double t, int stride, double *d_out)
+/* initial_precomputations(affine_transform(point)) of the configured state, one thread per point, on the compute
+ * stream; nodes: d_points are the node positions and d_out the context's bathymetry */
+void ryujin_hip_ctx::initial_precomputed_points(const double *d_points, size_t n, double *d_out, bool nodes)
 {
   if (n == 0)
     return;
-  if (iv.state == kIvFunction) {
+  const dim3 grid(grid_for(n, kInitialValuesBlock)), block(kInitialValuesBlock);
+  if (dim == 1) {
+    if (nodes)
+      hipLaunchKernelGGL(k_initial_precomputed_nodes<1>, grid, block, 0, stream, iv, (uint32_t)n, d_points, d_out);
+    else
+      hipLaunchKernelGGL(k_initial_precomputed_points<1>, grid, block, 0, stream, iv, (uint32_t)n, d_points, d_out);
+  } else {
+    if (nodes)
+      hipLaunchKernelGGL(k_initial_precomputed_nodes<2>, grid, block, 0, stream, iv, (uint32_t)n, d_points, d_out);
+    else
+      hipLaunchKernelGGL(k_initial_precomputed_points<2>, grid, block, 0, stream, iv, (uint32_t)n, d_points, d_out);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+/* one thread per point (k_initial_values_points) on the compute stream; nodes: the points are the node positions and
+ * d_out a state vector (the states of kernels_initial_values_bathymetry.hpp have a kernel of their own for it) */
+template <typename E>
+void ryujin_hip_ctx::initial_values_points(const double *d_points, size_t n, double t, int stride, double *d_out,
+                                           bool nodes)
+{
+  if (n == 0)
+    return;
+  if (iv_is_bathymetry_state(iv.state)) {
+    /* the states of initial_states_bathymetry_device.hpp: kernels of their own */
+    if constexpr (std::is_same<typename E::Params, ShallowWaterParams>::value) {
+      const dim3 grid(grid_for(n, kInitialValuesBlock)), block(kInitialValuesBlock);
+      if (nodes)
+        hipLaunchKernelGGL(k_initial_values_bathymetry_nodes<E::DIMENSION>, grid, block, 0, stream, iv, (uint32_t)n,
+                           d_points, t, stride, d_out);
+      else
+        hipLaunchKernelGGL(k_initial_values_bathymetry_points<E::DIMENSION>, grid, block, 0, stream, iv, (uint32_t)n,
+                           d_points, t, d_out);
+    } else {
+      throw HipError(RYUJIN_ERR_ARG, "initial values: the Description of this context has no such state");
+    }
+  } else if (iv.state == kIvFunction) {
     hipLaunchKernelGGL(k_initial_values_function_points<E>, dim3(grid_for(n, kInitialValuesBlock)),
                        dim3(kInitialValuesBlock), 0, stream, iv, d_iv_function.ptr, (uint32_t)n, d_points, t, stride,
                        d_out);
@@ -1302,7 +1348,19 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStag
      * every kernel of the previous stage that read the buffer (compute stream order; the export part of the previous
      * pre-pass may have applied boundary conditions on comm_stream) and behind the step-4 kernel of the first stage,
      * which left tau_rk. Nothing on the host waits for tau. */
-    if (iv.state == kIvFunction) {
+    if (iv_is_bathymetry_state(iv.state)) {
+      if constexpr (std::is_same<typename E::Params, ShallowWaterParams>::value) {
+        join_export();
+        hipLaunchKernelGGL(k_initial_values_bathymetry_dirichlet<E::DIMENSION>,
+                           dim3(grid_for(bdry.n_bdry, kInitialValuesBlock)), dim3(kInitialValuesBlock), 0, stream, iv,
+                           bdry.n_bdry, d_iv_b_positions.ptr, d_b_id.ptr, iv_stage.t, iv_stage.c, d_scalars.ptr,
+                           d_dirichlet.ptr);
+        HIP_CHECK(hipGetLastError());
+        have_dirichlet = true;
+      } else {
+        throw HipError(RYUJIN_ERR_ARG, "initial values: the Description of this context has no such state");
+      }
+    } else if (iv.state == kIvFunction) {
       join_export();
       hipLaunchKernelGGL(k_initial_values_function_dirichlet<E>, dim3(grid_for(bdry.n_bdry, kInitialValuesBlock)),
                          dim3(kInitialValuesBlock), 0, stream, iv, d_iv_function.ptr, bdry.n_bdry, d_iv_b_positions.ptr,
@@ -4058,10 +4116,11 @@ namespace
   {
     const int dim = ctx.dim, eq = ctx.params.equation;
     InitialValuesParams P{};
-    const bool library_state = iv_is_library_state(in.state);
-    if ((in.state < RYUJIN_IV_UNIFORM || in.state > RYUJIN_IV_SLOPING_FRICTION) && !library_state)
+    const bool library_state = iv_is_library_state(in.state), bathymetry_state = iv_is_bathymetry_state(in.state);
+    if ((in.state < RYUJIN_IV_UNIFORM || in.state > RYUJIN_IV_SLOPING_FRICTION) && !library_state && !bathymetry_state)
       throw HipError(RYUJIN_ERR_ARG, "initial values: unknown state " + std::to_string(in.state));
-    const bool sw_state = library_state ? in.state >= RYUJIN_IV_SW_UNIFORM : in.state >= RYUJIN_IV_CIRCULAR_DAM_BREAK;
+    const bool sw_state = bathymetry_state || (library_state ? in.state >= RYUJIN_IV_SW_UNIFORM
+                                                             : in.state >= RYUJIN_IV_CIRCULAR_DAM_BREAK);
     if (sw_state != (eq == RYUJIN_EQ_SHALLOW_WATER))
       throw HipError(RYUJIN_ERR_ARG, "initial values: the Description of this context has no such state");
     if (in.perturbation != 0.)
@@ -4074,8 +4133,24 @@ namespace
     if ((in.state == RYUJIN_IV_FOUR_STATE_CONTRAST || in.state == RYUJIN_IV_ASTRO_JET) && dim == 1)
       throw HipError(RYUJIN_ERR_UNSUPPORTED,
                      "initial values: four state contrast and astro jet are defined for dim >= 2");
-    if (sw_state && library_state && dim == 3)
+    if (sw_state && (library_state || bathymetry_state) && dim == 3)
       throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: shallow water is defined for dim = 1 and 2");
+    if ((in.state == RYUJIN_IV_SW_HOU_TEST || in.state == RYUJIN_IV_SW_TRANSIENT) && dim != 2)
+      throw HipError(RYUJIN_ERR_UNSUPPORTED,
+                     "initial values: hou test and transient experiments are defined for dim = 2");
+    /* the selector slots: a string of the reference each, one of its integer values here */
+    const auto require_selector = [&](const int slot, const int n_values, const char *what) {
+      const double value = in.params[slot];
+      if (!(value >= 0. && value < (double)n_values && value == std::floor(value)))
+        throw HipError(RYUJIN_ERR_ARG, std::string("initial values: ") + what + " is none of 0, ..., " +
+                                           std::to_string(n_values - 1));
+    };
+    if (in.state == RYUJIN_IV_SW_FLOW_OVER_BUMP)
+      require_selector(0, 2, "flow type");
+    if (in.state == RYUJIN_IV_SW_THREE_BUMPS_DAM_BREAK)
+      require_selector(0, 2, "well balancing validation");
+    if (in.state == RYUJIN_IV_SW_TRANSIENT)
+      require_selector(4, 4, "experimental configuration");
     for (int q = 0; q < 16; ++q)
       if (std::isnan(in.params[q]))
         throw HipError(RYUJIN_ERR_ARG, "initial values: NaN parameter");
@@ -4240,6 +4315,36 @@ namespace
       c[1] = width2 * (width2 * width2); /* fixed_power<6>(right - left) */
       c[2] = left;
       c[3] = right;
+      break;
+    }
+    /* the states of initial_states_bathymetry_device.hpp (its table of c[]) */
+    case RYUJIN_IV_SW_FLOW_OVER_BUMP: {
+      /* initial_state_flow_over_bump.h:62-80, as initial_states.sw_flow_over_bump_constants */
+      const double g = hp.gravity;
+      double h_inflow = 0.28205279813802181, q_inflow = 0.18;
+      double cBer = 0.2 + 1.5 * std::pow(q_inflow * q_inflow / g, 1. / 3.);
+      if (in.params[0] == 1.) { /* subsonic */
+        q_inflow = 4.42;
+        h_inflow = 2.;
+        const double ratio = q_inflow / h_inflow;
+        cBer = ratio * ratio / (2. * g) + h_inflow;
+      }
+      c[0] = h_inflow;
+      c[1] = q_inflow;
+      c[2] = cBer;
+      c[3] = q_inflow * q_inflow / (2. * g);
+      break;
+    }
+    case RYUJIN_IV_SW_THREE_BUMPS_DAM_BREAK:
+      c[0] = in.params[1] * std::sqrt(hp.gravity * in.params[1]); /* h_L speed_of_sound((h_L, 0)) */
+      break;
+    case RYUJIN_IV_SW_HOU_TEST:
+    case RYUJIN_IV_SW_TRANSIENT:
+      break;
+    case RYUJIN_IV_SW_SOLITON: {
+      const double depth = in.params[0], amplitude = in.params[1];
+      c[0] = std::sqrt(hp.gravity * (amplitude + depth));
+      c[1] = std::sqrt(3. * amplitude / (4. * depth * depth * (amplitude + depth)));
       break;
     }
     default: /* contrast, four state contrast, ramp up, astro jet; uniform and contrast of shallow water */
@@ -4516,9 +4621,57 @@ int ryujin_hip_initial_values_interpolate(ryujin_hip_ctx *ctx, int handle, doubl
     s.precomputed = false;
     return dispatch_initial_values(ctx, [&](auto tag) {
       ctx->template initial_values_points<typename decltype(tag)::type>(ctx->d_iv_positions.ptr, ctx->L.n_relevant, t,
-                                                                        ctx->KP, s.U.ptr);
+                                                                        ctx->KP, s.U.ptr, true);
       return RYUJIN_OK;
     });
+  });
+}
+
+int ryujin_hip_initial_values_interpolate_initial_precomputed(ryujin_hip_ctx *ctx)
+{
+  return guarded_ctx(ctx, [&]() {
+    ctx->require_initial_precomputed();
+    /* on the compute stream, behind every kernel that reads the bathymetry (step 4, the output extraction) */
+    ctx->initial_precomputed_points(ctx->d_iv_positions.ptr, ctx->L.n_relevant, ctx->d_Z.ptr, true);
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_initial_values_evaluate_initial_precomputed(ryujin_hip_ctx *ctx, const double *points, size_t n,
+                                                           double *out)
+{
+  return guarded_ctx(ctx, [&]() {
+    ctx->require_initial_precomputed();
+    if (n == 0)
+      return RYUJIN_OK;
+    if (!points || !out || n > 0xffffffffull)
+      throw HipError(RYUJIN_ERR_ARG, "initial values: bad argument");
+    const size_t dim = (size_t)ctx->dim;
+    if (ctx->d_iv_points.n < n * dim)
+      ctx->d_iv_points.alloc(n * dim, false);
+    if (ctx->d_iv_values.n < n)
+      ctx->d_iv_values.alloc(n, false);
+    HIP_CHECK(hipMemcpyAsync(ctx->d_iv_points.ptr, points, n * dim * sizeof(double), hipMemcpyHostToDevice,
+                             ctx->stream));
+    ctx->initial_precomputed_points(ctx->d_iv_points.ptr, n, ctx->d_iv_values.ptr, false);
+    HIP_CHECK(hipMemcpyAsync(out, ctx->d_iv_values.ptr, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return RYUJIN_OK;
+  });
+}
+
+int ryujin_hip_get_initial_precomputed(ryujin_hip_ctx *ctx, double *out)
+{
+  return guarded_ctx(ctx, [&]() {
+    ctx->require_initial_precomputed();
+    if (ctx->L.n_relevant == 0)
+      return RYUJIN_OK;
+    if (!out)
+      throw HipError(RYUJIN_ERR_ARG, "initial values: bad argument");
+    HIP_CHECK(hipMemcpyAsync(out, ctx->d_Z.ptr, (size_t)ctx->L.n_relevant * sizeof(double), hipMemcpyDeviceToHost,
+                             ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return RYUJIN_OK;
   });
 }
 

@@ -494,3 +494,243 @@ def sw_contrast_primitive(positions, left=(1.0, 0.0), right=(1.0, 0.0)):
     x, n, _ = _frame(positions)
     east = x[:, 0] > 0.0
     return np.where(east, right[0], left[0]), np.where(east, right[1], left[1])
+
+
+# ---------------------------------------------------------------------------
+# The shallow-water states that bring their own bathymetry (capi.IV_BATHYMETRY_STATES). Positions in the FRAME OF THE
+# STATE, as above. Each sw_<state>() returns ((h, q) with q the discharge along the first axis of the frame, bathymetry);
+# each sw_<state>_bathymetry() is initial_precomputations(point) alone. The device follows these statements one by one
+# (initial_states_bathymetry_device.hpp): pow(x, 2) and pow(x, 3) are the products a * a and a * (a * a), std::max /
+# std::min are the comparisons the C++ library makes ((a < b) ? b : a and (b < a) ? b : a, folded from the left), and
+# only pow(q^2 / g, 1/3), pow(-Q, -1.5), acos, cos and cosh are library functions.
+
+def _square(a):
+    return a * a
+
+
+def _cube(a):
+    return a * (a * a)
+
+
+def _std_max(a, *others):
+    """std::max(a, b) = (a < b) ? b : a; std::max({a, b, ...}) folds it from the left"""
+    out = a
+    for b in others:
+        out = np.where(out < b, b, out)
+    return out
+
+
+def _std_min(a, b):
+    """std::min(a, b) = (b < a) ? b : a"""
+    return np.where(b < a, b, a)
+
+
+FLOW_OVER_BUMP_TYPES = ("transcritical", "subsonic")
+FLOW_OVER_BUMP_XM, FLOW_OVER_BUMP_XS = 10.0, 11.7
+FLOW_OVER_BUMP_H_OUTFLOW = 0.28205279813802181
+
+
+def sw_flow_over_bump_bathymetry(positions):
+    """source/shallow_water/initial_state_flow_over_bump.h:120-131: 0.2/64 (x - 8)^3 (12 - x)^3 on 8 <= x <= 12."""
+    x, _, _ = _frame(positions)
+    x = x[:, 0]
+    bump = (0.2 / 64.0) * _cube(x - 8.0) * _cube(12.0 - x)
+    return np.where((8.0 <= x) & (x <= 12.0), bump, 0.0)
+
+
+def sw_flow_over_bump_constants(gravity=9.81, flow_type="transcritical"):
+    """(h_inflow, q_inflow, cBer, d) of initial_state_flow_over_bump.h:62-80: what does not depend on the point."""
+    if flow_type not in FLOW_OVER_BUMP_TYPES:
+        raise ValueError("Flow type must be 'transcritical' or 'subsonic'. ")
+    g = float(gravity)
+    h_inflow, q_inflow = 0.28205279813802181, 0.18
+    cBer = 0.2 + 1.5 * float(np.power(q_inflow * q_inflow / g, 1.0 / 3.0))
+    if flow_type == "subsonic":
+        q_inflow, h_inflow = 4.42, 2.0
+        ratio = q_inflow / h_inflow
+        cBer = ratio * ratio / (2.0 * g) + h_inflow
+    d = q_inflow * q_inflow / (2.0 * g)
+    return h_inflow, q_inflow, cBer, d
+
+
+def sw_flow_over_bump_acos_argument(positions, gravity=9.81, flow_type="transcritical"):
+    """pow(-Q, -1.5) R of Cardano's formula: the argument of acos (-1 at x = 10 of the transcritical flow)"""
+    _, _, cBer, d = sw_flow_over_bump_constants(gravity, flow_type)
+    b = sw_flow_over_bump_bathymetry(positions) - cBer
+    Q = -_square(b) / 9.0
+    R = -(27.0 * d + 2.0 * _cube(b)) / 54.0
+    return np.power(-Q, -1.5) * R
+
+
+def sw_flow_over_bump(positions, t, gravity=9.81, flow_type="transcritical"):
+    """initial_state_flow_over_bump.h:55-106: the inflow state over the bump for t < 1e-12, afterwards the steady
+    solution by Cardano's formula (transcritical: the second root on xM <= x < xS, the outflow depth on xS < x;
+    x == xS keeps the first root)."""
+    x, n, _ = _frame(positions)
+    x = x[:, 0]
+    h_inflow, q_inflow, cBer, d = sw_flow_over_bump_constants(gravity, flow_type)
+    bath = sw_flow_over_bump_bathymetry(positions)
+    q = np.full(n, q_inflow)
+    if t < 1.0e-12:
+        h_initial = h_inflow - bath
+        return np.column_stack([h_initial, q]), bath
+    b = bath - cBer
+    Q = -_square(b) / 9.0
+    R = -(27.0 * d + 2.0 * _cube(b)) / 54.0
+    with np.errstate(invalid="ignore"):
+        theta = np.arccos(np.power(-Q, -1.5) * R)
+    h_exact = 2.0 * np.sqrt(-Q) * np.cos(theta / 3.0) - b / 3.0
+    if flow_type == "transcritical":
+        middle = (FLOW_OVER_BUMP_XM <= x) & (x < FLOW_OVER_BUMP_XS)
+        second = 2.0 * np.sqrt(-Q) * np.cos((4.0 * np.pi + theta) / 3.0) - b / 3.0
+        h_exact = np.where(middle, second, np.where(FLOW_OVER_BUMP_XS < x, FLOW_OVER_BUMP_H_OUTFLOW, h_exact))
+    return np.column_stack([h_exact, q]), bath
+
+
+THREE_BUMPS_CONES_2D = ((30.0, 6.0, 1.0, 1.0 / 8.0), (30.0, 24.0, 1.0, 1.0 / 8.0), (47.5, 15.0, 3.0, 3.0 / 10.0))
+
+
+def sw_three_bumps_dam_break_bathymetry(positions, cone_magnitude=1.0):
+    """initial_state_three_bumps_dam_break.h:95-122: one cone in 1-D (a square root of a square), three in 2-D."""
+    x, _, dim = _frame(positions)
+    if dim == 1:
+        z3 = 3.0 - 3.0 / 10.0 * np.sqrt(_square(x[:, 0] - 47.5))
+        return cone_magnitude * _std_max(z3, 0.0)
+    z = [top - slope * np.sqrt(_square(x[:, 0] - cx) + _square(x[:, 1] - cy))
+         for cx, cy, top, slope in THREE_BUMPS_CONES_2D]
+    return cone_magnitude * _std_max(z[0], z[1], z[2], 0.0)
+
+
+def sw_three_bumps_dam_break(positions, t, gravity=9.81, well_balancing_validation=False, left_depth=1.875,
+                             right_depth=0.0, cone_magnitude=1.0):
+    """initial_state_three_bumps_dam_break.h:63-82: the dam at x = 16 over the cones for t <= 1e-10 (or always, with
+    "well balancing validation"), afterwards the constant inflow (h_L, h_L sqrt(g h_L)) everywhere."""
+    x, n, _ = _frame(positions)
+    bath = sw_three_bumps_dam_break_bathymetry(positions, cone_magnitude)
+    if t <= 1.0e-10 or well_balancing_validation:
+        h = np.where(x[:, 0] < 16.0, float(left_depth), float(right_depth))
+        h = _std_max(h - bath, 0.0)
+        return np.column_stack([h, np.zeros(n)]), bath
+    h = float(left_depth)
+    a = float(np.sqrt(gravity * h))
+    return np.column_stack([np.full(n, h), np.full(n, h * a)]), bath
+
+
+def sw_hou_test_bathymetry(positions):
+    """initial_state_hou_test.h:74-107 (dim = 2): max(min of three paraboloids, max of a hill and two plateaus)."""
+    x, _, dim = _frame(positions)
+    if dim != 2:
+        raise ValueError("hou test is defined for dim = 2")
+    x, y = x[:, 0], x[:, 1]
+    base1 = _square(x + 250.0) / 1600.0 + _square(y) / 400.0
+    base2 = _square(x) / 225.0 + _square(y - 50.0) / 225.0
+    base3 = _square(x - 250.0) / 1225.0 + _square(y) / 225.0 - 10.0
+    base = _std_min(base1, base2)
+    base = _std_min(base, base3)
+    bump1 = 80.0 - _square(x + 250.0) / 50.0 - _square(y) / 50.0
+    bump2 = np.where(_square(x - 200.0) + _square(y + 10.0) <= 1000.0, 10.0, 0.0)
+    bump3 = np.where((np.abs(x - 380.0) <= 40.0) & (np.abs(y - 50.0) <= 40.0), 20.0, 0.0)
+    bumps = _std_max(bump1, bump2)
+    bumps = _std_max(bumps, bump3)
+    return _std_max(base, bumps)
+
+
+def sw_hou_test(positions, reservoir_water_depth=35.0):
+    """initial_state_hou_test.h:42-60: water up to the reservoir depth where x < -100, dry elsewhere; at rest."""
+    x, n, _ = _frame(positions)
+    bath = sw_hou_test_bathymetry(positions)
+    h = np.where(x[:, 0] < -100.0, _std_max(reservoir_water_depth - bath, 0.0), 0.0)
+    return np.column_stack([h, np.zeros(n)]), bath
+
+
+TRANSIENT_CONFIGURATIONS = ("G1", "G2", "G3", "none")
+TRANSIENT_HALF_WIDTH = 31.0 / 2.0 / 100.0           # of the circular bump (G2) and the half circles (G3)
+TRANSIENT_CENTERS = {"G1": 205.0 / 100.0 + (16.3 / 2.0 / 100.0), "G2": 184.5 / 100.0 + 31.0 / 2.0 / 100.0,
+                     "G3": 194 / 100.0 + 31.0 / 2.0 / 100.0, "rectangle": 235.0 / 100.0 + (16.3 / 2.0 / 100.0)}
+
+
+def _transient_rectangle(x, y, xc):
+    length, width = 16.3 / 100.0, 8.0 / 100.0
+    return np.abs((x - xc) / length + y / width) + np.abs((x - xc) / length - y / width)
+
+
+def _transient_semi_circle(x, xc):
+    ratio = (x - xc) / TRANSIENT_HALF_WIDTH
+    number = 1.0 - _square(ratio)
+    radicand = 0.5 * (np.abs(number) + number)       # positive_part
+    return 7.3 / 100.0 * np.sqrt(radicand)
+
+
+def sw_transient_bathymetry(positions, experimental_configuration="G1"):
+    """initial_state_transient.h:90-171 (dim = 2): the tank's floor, flat then two slopes, plus the obstacle of the
+    configuration; G2 and G3 overwrite `obstacle` in the order of the reference (the rectangle last)."""
+    if experimental_configuration not in TRANSIENT_CONFIGURATIONS:
+        raise ValueError("Case must be 'G1', 'G2', 'G3' or 'none'")
+    x, n, dim = _frame(positions)
+    if dim != 2:
+        raise ValueError("transient experiments is defined for dim = 2")
+    x, y = x[:, 0], x[:, 1]
+    knee = 326.0 / 100.0
+    bath = np.where((x >= 0.0) & (x <= knee), -0.00092 * x,
+                    np.where(x > knee, -0.0404 * (x - knee) - 0.00092 * 326.0 / 100.0, 0.0))
+    which = experimental_configuration
+    if which == "none":
+        return bath
+    obstacle = np.zeros(n)
+    if which == "G1":
+        obstacle = np.where(_transient_rectangle(x, y, TRANSIENT_CENTERS["G1"]) <= 1.0, 7.0 / 100.0, obstacle)
+    elif which == "G2":
+        semi_circle = _transient_semi_circle(x, TRANSIENT_CENTERS["G2"])
+        obstacle = _std_max(semi_circle, 0.0)
+        obstacle = np.where(_transient_rectangle(x, y, TRANSIENT_CENTERS["rectangle"]) <= 1.0, 7.0 / 100.0, obstacle)
+    else:
+        xc = TRANSIENT_CENTERS["G3"]
+        semi_circle = _transient_semi_circle(x, xc)
+        inside = np.abs(x - xc) <= TRANSIENT_HALF_WIDTH
+        obstacle = np.where((y < semi_circle - 24.0 / 2.0 / 100.0) & inside, 21.0 / 100.0, obstacle)
+        obstacle = np.where((y > -semi_circle + 24.0 / 2.0 / 100.0) & inside, 21.0 / 100.0, obstacle)
+        obstacle = np.where(_transient_rectangle(x, y, TRANSIENT_CENTERS["rectangle"]) <= 1.0, 7.0 / 100.0, obstacle)
+    return bath + obstacle
+
+
+def sw_transient(positions, flow_state_left=(1.0, 0.0), flow_state_right=(1.0, 0.0), experimental_configuration="G1"):
+    """initial_state_transient.h:66-77: the 1-D flow state (h, q) `right` where x > 1e-8, else `left`."""
+    x, _, _ = _frame(positions)
+    bath = sw_transient_bathymetry(positions, experimental_configuration)
+    east = x[:, 0] > 1.0e-8
+    h = np.where(east, float(flow_state_right[0]), float(flow_state_left[0]))
+    q = np.where(east, float(flow_state_right[1]), float(flow_state_left[1]))
+    return np.column_stack([h, q]), bath
+
+
+def sw_soliton_constants(gravity=9.81, still_water_depth=1.0, amplitude=0.1):
+    """(celerity, width) of initial_state_soliton.h:50-52"""
+    depth, amp = float(still_water_depth), float(amplitude)
+    celerity = float(np.sqrt(gravity * (amp + depth)))
+    width = float(np.sqrt(3.0 * amp / (4.0 * depth * depth * (amp + depth))))
+    return celerity, width
+
+
+def sw_soliton(positions, t, gravity=9.81, still_water_depth=1.0, amplitude=0.1):
+    """initial_state_soliton.h:43-63: depth + amplitude sech^2(width (x - celerity t)) over a flat bed."""
+    x, n, _ = _frame(positions)
+    depth, amp = float(still_water_depth), float(amplitude)
+    celerity, width = sw_soliton_constants(gravity, depth, amp)
+    sech_sqd = 1.0 / _square(np.cosh(width * (x[:, 0] - celerity * t)))
+    profile = depth + amp * sech_sqd
+    h = _std_max(profile, 0.0)
+    v = celerity * (profile - depth) / profile
+    return np.column_stack([h, h * v]), np.zeros(n)
+
+
+def sw_paraboloid_1d_bathymetry(positions, free_surface_radius=3000.0, water_height=10.0, length=10000.0):
+    """initial_state_paraboloid.h:137-141 (dim = 1): the statement of sw_paraboloid_1d, on its own"""
+    x, _, _ = _frame(positions)
+    a, h0 = free_surface_radius, water_height
+    return h0 / (a * a) * np.power(x[:, 0] - 0.5 * length, 2)
+
+
+def sw_sloping_friction_bathymetry(positions, ramp_slope=1.0):
+    """initial_state_sloping_friction.h:84-87: the statement of sw_sloping_friction, on its own"""
+    x, _, _ = _frame(positions)
+    return -ramp_slope * x[:, 0]

@@ -305,6 +305,30 @@ class HyperbolicModule:
         """InitialValues::interpolate_hyperbolic_vector(t) into `state`, ghost rows included (an enqueue)"""
         self._check(self._f("initial_values_interpolate")(self._ctx, state.handle, float(t)))
 
+    def initial_values_interpolate_initial_precomputed(self) -> None:
+        """InitialValues::interpolate_initial_precomputed_vector(): the context's bathymetry := the bed of the
+        configured state at every node, ghost rows included (an enqueue); exact zeros for a state without a bed.
+        Replaces what the offline data gave as initial_precomputed. Shallow water only."""
+        self._check(self._f("initial_values_interpolate_initial_precomputed")(self._ctx))
+
+    def initial_values_evaluate_initial_precomputed(self, points) -> np.ndarray:
+        """[n]: initial_precomputations(points[n, dim]) of the configured state, the bed, evaluated on the device"""
+        points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, self.dim)
+        out = np.zeros(points.shape[0], dtype=np.float64)
+        self._check(self._f("initial_values_evaluate_initial_precomputed")(
+            self._ctx, capi.as_ptr(points, capi.c_double_p) if points.size else None, points.shape[0],
+            capi.as_ptr(out, capi.c_double_p) if out.size else None))
+        return out
+
+    def initial_precomputed(self) -> np.ndarray:
+        """[n_relevant]: the bathymetry the context holds now (ryujin_hip_get_initial_precomputed): what the offline
+        data gave, or zeros, until initial_values_interpolate_initial_precomputed replaces it. Like the two calls
+        above it needs an initial_values_configure or initial_values_configure_function first (include/ryujin_hip.h)."""
+        out = np.zeros(self.n_relevant, dtype=np.float64)
+        self._check(self._f("get_initial_precomputed")(
+            self._ctx, capi.as_ptr(out, capi.c_double_p) if out.size else None))
+        return out
+
     # ------------------------------------------------------------------ FluxLibrary "function" (device backend only)
     def flux_configure_function(self, expression: str, delta: float = 1e-10) -> None:
         """Switch a scalar conservation module to the expression-defined flux "function"
