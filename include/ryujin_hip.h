@@ -611,7 +611,24 @@ enum {
   RYUJIN_DEBUG_EULER_LIMIT_CHECKED_1D = 15,
   /* the limiter as the sweeps compose it, dim = 2: in bounds[3], U[4], P[4]; out l, success, took the Newton tail,
    * t_r behind the density clip, psi_r of the first Newton iteration (as the device evaluates it) */
-  RYUJIN_DEBUG_EULER_LIMIT_2D = 16
+  RYUJIN_DEBUG_EULER_LIMIT_2D = 16,
+  /* The limiter of every other Description and dimension, pair by pair (a kernel of its own, one thread per item):
+   * in bounds[NB], U[K], P[K]; out l, success, took the Newton tail -- Euler and EulerAEOS also t_r behind the density
+   * clip and psi_r there, as RYUJIN_DEBUG_EULER_LIMIT_2D. Evaluated as the sweeps compose it: limit_fast(), and
+   * limit() for the undecided pairs. With params->debug_expensive_bounds_check != 0 these six evaluate limit_checked()
+   * instead (the EXPENSIVE_BOUNDS_CHECK control flow: the same l, `success` has more ways to be false; "took the
+   * Newton tail" is 0 then).
+   *   EULER_LIMIT_3D   NB = 3 (rho_min, rho_max, s_min), K = 5
+   *   AEOS_LIMIT_2D/3D NB = 4 (rho_min, rho_max, s_min, gamma_min), K = 4 / 5
+   *   SW_LIMIT_1D/2D   NB = 5 (h_min, h_max, h_small, kin_max, v2_max), K = 2 / 3; limiter_limit_on_kinetic_energy and
+   *                    limiter_limit_on_square_velocity select the constraints
+   *   SCALAR_LIMIT     NB = 2 (u_min, u_max), K = 1 */
+  RYUJIN_DEBUG_EULER_LIMIT_3D = 17,
+  RYUJIN_DEBUG_AEOS_LIMIT_2D = 18,
+  RYUJIN_DEBUG_AEOS_LIMIT_3D = 19,
+  RYUJIN_DEBUG_SW_LIMIT_1D = 20,
+  RYUJIN_DEBUG_SW_LIMIT_2D = 21,
+  RYUJIN_DEBUG_SCALAR_LIMIT = 22
 };
 int ryujin_hip_debug_function(int device, const ryujin_hip_params *params, int which, const double *in,
                               double *out, size_t n);

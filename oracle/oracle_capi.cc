@@ -774,4 +774,118 @@ int ryujin_oracle_scalar_limit(const ryujin_hip_params *p, int expensive_bounds_
   });
 }
 
+/* ---- the limiters on n independent items (tests/helpers_limiter_cases.py) ----------------------
+ * bounds[n * n_bounds], U[n * k], P[n * k] -> l[n], success[n]; dimension from p->dim; the production control flow,
+ * or the EXPENSIVE_BOUNDS_CHECK one. The same Limiter::limit calls as the item-wise entries above. */
+
+int ryujin_oracle_euler_limit_batch(const ryujin_hip_params *p, int expensive_bounds_check, size_t n,
+                                    const double *bounds, const double *U, const double *P, double *l, int *success)
+{
+  auto run = [&](auto dim_tag) {
+    constexpr int dim = decltype(dim_tag)::value;
+    constexpr int k = dim + 2;
+    const euler::View<dim> view(*p);
+    euler::Limiter<dim> lim(view, *p);
+    lim.expensive_bounds_check = expensive_bounds_check != 0;
+#pragma omp parallel for schedule(static)
+    for (size_t i = 0; i < n; ++i) {
+      typename euler::View<dim>::state_type u, pp;
+      for (int q = 0; q < k; ++q) {
+        u[q] = U[i * k + q];
+        pp[q] = P[i * k + q];
+      }
+      const auto [t, s] = lim.limit({{bounds[i * 3], bounds[i * 3 + 1], bounds[i * 3 + 2]}}, u, pp);
+      l[i] = t;
+      success[i] = s ? 1 : 0;
+    }
+  };
+  if (p->dim == 1)
+    run(std::integral_constant<int, 1>{});
+  else if (p->dim == 2)
+    run(std::integral_constant<int, 2>{});
+  else
+    run(std::integral_constant<int, 3>{});
+  return RYUJIN_OK;
+}
+
+int ryujin_oracle_aeos_limit_batch(const ryujin_hip_params *p, int expensive_bounds_check, size_t n,
+                                   const double *bounds, const double *U, const double *P, double *l, int *success)
+{
+  return guarded([&]() {
+    auto run = [&](auto dim_tag) {
+      constexpr int dim = decltype(dim_tag)::value;
+      constexpr int k = dim + 2;
+      const aeos::View<dim> view(*p);
+#pragma omp parallel for schedule(static)
+      for (size_t i = 0; i < n; ++i) {
+        aeos::Limiter<dim> lim(view, *p); /* (limit() is not const: it writes its trace) */
+        lim.expensive_bounds_check = expensive_bounds_check != 0;
+        typename aeos::Limiter<dim>::Bounds bnd;
+        typename aeos::View<dim>::state_type u, pp;
+        for (int q = 0; q < 4; ++q)
+          bnd[q] = bounds[i * 4 + q];
+        for (int q = 0; q < k; ++q) {
+          u[q] = U[i * k + q];
+          pp[q] = P[i * k + q];
+        }
+        const auto [t, s] = lim.limit(bnd, u, pp);
+        l[i] = t;
+        success[i] = s ? 1 : 0;
+      }
+      return RYUJIN_OK;
+    };
+    switch (p->dim) {
+    case 1: return run(std::integral_constant<int, 1>{});
+    case 2: return run(std::integral_constant<int, 2>{});
+    default: return run(std::integral_constant<int, 3>{});
+    }
+  });
+}
+
+/* shallow_water::Limiter<dim>::limit(bounds[5] = h_min, h_max, h_small, kin_max, v2_max; U[dim + 1]; P[dim + 1]) */
+int ryujin_oracle_sw_limit_batch(const ryujin_hip_params *p, int expensive_bounds_check, size_t n,
+                                 const double *bounds, const double *U, const double *P, double *l, int *success)
+{
+  auto run = [&](auto dim_tag) {
+    constexpr int dim = decltype(dim_tag)::value;
+    constexpr int k = dim + 1;
+    const shallow_water::View<dim> view(*p);
+    shallow_water::Limiter<dim> lim(view, *p);
+    lim.expensive_bounds_check = expensive_bounds_check != 0;
+#pragma omp parallel for schedule(static)
+    for (size_t i = 0; i < n; ++i) {
+      typename shallow_water::Limiter<dim>::Bounds bnd;
+      typename shallow_water::View<dim>::state_type u, pp;
+      for (int q = 0; q < 5; ++q)
+        bnd[q] = bounds[i * 5 + q];
+      for (int q = 0; q < k; ++q) {
+        u[q] = U[i * k + q];
+        pp[q] = P[i * k + q];
+      }
+      const auto [t, s] = lim.limit(bnd, u, pp);
+      l[i] = t;
+      success[i] = s ? 1 : 0;
+    }
+  };
+  if (p->dim == 1)
+    run(std::integral_constant<int, 1>{});
+  else
+    run(std::integral_constant<int, 2>{});
+  return RYUJIN_OK;
+}
+
+int ryujin_oracle_scalar_limit_batch(const ryujin_hip_params *p, int expensive_bounds_check, size_t n,
+                                     const double *bounds, const double *U, const double *P, double *l, int *success)
+{
+  scalar::Limiter<1> lim(*p);
+  lim.expensive_bounds_check = expensive_bounds_check != 0;
+#pragma omp parallel for schedule(static)
+  for (size_t i = 0; i < n; ++i) {
+    const auto [t, s] = lim.limit({{bounds[i * 2], bounds[i * 2 + 1]}}, U[i], P[i]);
+    l[i] = t;
+    success[i] = s ? 1 : 0;
+  }
+  return RYUJIN_OK;
+}
+
 } /* extern "C" */

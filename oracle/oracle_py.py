@@ -60,6 +60,9 @@ def load(path: str | None = None):
     lib.ryujin_oracle_scalar_riemann.argtypes = [pp, C.c_double, C.c_double, dp, dp, dp]
     lib.ryujin_oracle_scalar_flux.argtypes = [pp, C.c_double, dp]
     lib.ryujin_oracle_scalar_limit.argtypes = [pp, C.c_int, dp, C.c_double, C.c_double, dp, capi.c_int_p]
+    for name in ("euler", "aeos", "sw", "scalar"):   # (p, expensive_bounds_check, n, bounds, U, P, l, success)
+        getattr(lib, f"ryujin_oracle_{name}_limit_batch").argtypes = [pp, C.c_int, C.c_size_t, dp, dp, dp, dp,
+                                                                      capi.c_int_p]
     if path == _build_oracle.ORACLE_SO:
         _lib = lib
     return lib

@@ -3686,12 +3686,108 @@ namespace
   }
 } // namespace
 
+/* The limiter of one Description on n independent items bounds[NB], U[K], P[K], as the sweeps compose it:
+ * limit_fast(), and limit() for the undecided pairs -- or limit_checked() alone (debug_expensive_bounds_check).
+ * out: l, success, undecided; WITH_TRACE (Euler, EulerAEOS): also t_r behind the density clip and psi_r there. */
+extern "C++" {
+namespace
+{
+  template <typename E, bool WITH_TRACE>
+  __global__ void __launch_bounds__(kBlock)
+  k_debug_limit(const typename E::Params P, const bool checked, const size_t n, const double *__restrict__ in,
+                double *__restrict__ out)
+  {
+    constexpr int K = E::K, NB = E::NB, n_in = NB + 2 * K, n_out = WITH_TRACE ? 5 : 3;
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n)
+      return;
+    const double *v = in + q * n_in;
+    double bnd[NB], U[K], Pij[K];
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+      bnd[b] = v[b];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      U[k] = v[NB + k];
+      Pij[k] = v[NB + K + k];
+    }
+    bool success, undecided = false;
+    double l;
+    if (checked) {
+      l = E::limit_checked(P, bnd, U, Pij, success);
+    } else {
+      l = E::limit_fast(P, bnd, U, Pij, success, undecided);
+      if (undecided)
+        l = E::limit(P, bnd, U, Pij, success);
+    }
+    out[q * n_out + 0] = l;
+    out[q * n_out + 1] = success ? 1. : 0.;
+    out[q * n_out + 2] = undecided ? 1. : 0.;
+    if constexpr (WITH_TRACE) {
+      bool s2;
+      double t_r, psi_r;
+      if constexpr (std::is_same<typename E::Params, EulerParams>::value) {
+        psi_r = E::first_psi_r(P, bnd, U, Pij, s2, t_r);
+      } else {
+        t_r = E::density_clip(P, bnd, U, Pij, s2);
+        double U_r[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+          U_r[k] = U[k] + t_r * Pij[k];
+        psi_r = E::psi_of(P, U_r, bnd[2], bnd[3], 1. + P.vacuum_small * DBL_EPSILON).psi;
+      }
+      out[q * n_out + 3] = t_r;
+      out[q * n_out + 4] = psi_r;
+    }
+  }
+
+  template <typename E, bool WITH_TRACE>
+  void debug_limit(const typename E::Params &P, const bool checked, const double *in, double *out, const size_t n)
+  {
+    constexpr size_t n_in = E::NB + 2 * E::K, n_out = WITH_TRACE ? 5 : 3;
+    DeviceBuffer<double> din, dout;
+    din.upload(in, n * n_in);
+    dout.alloc(n * n_out);
+    hipLaunchKernelGGL((k_debug_limit<E, WITH_TRACE>), dim3(grid_for(n)), dim3(kBlock), 0, nullptr, P, checked, n,
+                       din.ptr, dout.ptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpy(out, dout.ptr, n * n_out * sizeof(double), hipMemcpyDeviceToHost));
+  }
+} // namespace
+} /* extern "C++": templates */
+
 int ryujin_hip_debug_function(int device, const ryujin_hip_params *params, int which, const double *in,
                               double *out, size_t n)
 {
   return guarded([&]() {
     if (!params || !in || !out)
       throw HipError(RYUJIN_ERR_ARG, "null argument");
+    /* the limiters pair by pair: a kernel of their own (k_debug_limit) */
+    if (which >= RYUJIN_DEBUG_EULER_LIMIT_3D && which <= RYUJIN_DEBUG_SCALAR_LIMIT) {
+      HIP_CHECK(hipSetDevice(device));
+      const bool checked = params->debug_expensive_bounds_check != 0;
+      switch (which) {
+      case RYUJIN_DEBUG_EULER_LIMIT_3D:
+        debug_limit<Euler<3>, true>(make_euler_params(*params), checked, in, out, n);
+        break;
+      case RYUJIN_DEBUG_AEOS_LIMIT_2D:
+        debug_limit<EulerAeos<2>, true>(make_aeos_params(*params), checked, in, out, n);
+        break;
+      case RYUJIN_DEBUG_AEOS_LIMIT_3D:
+        debug_limit<EulerAeos<3>, true>(make_aeos_params(*params), checked, in, out, n);
+        break;
+      case RYUJIN_DEBUG_SW_LIMIT_1D:
+        debug_limit<ShallowWater<1>, false>(make_sw_params(*params), checked, in, out, n);
+        break;
+      case RYUJIN_DEBUG_SW_LIMIT_2D:
+        debug_limit<ShallowWater<2>, false>(make_sw_params(*params), checked, in, out, n);
+        break;
+      default: /* the scalar limiter reads no parameter (scalar_conservation/limiter.template.h) */
+        debug_limit<ScalarConservation<1>, false>(ScalarParams{}, checked, in, out, n);
+        break;
+      }
+      return RYUJIN_OK;
+    }
     size_t n_in, n_out;
     switch (which) {
     case RYUJIN_DEBUG_EULER_RIEMANN:
