@@ -11,10 +11,16 @@ rows of length 1 get 0;  q_max = max |.| from 0, q_min = min |.| over the owned 
     r = max(0, |v| - q_min - floor) / max(q_max - q_min, eps),   copysign(1 - exp(-beta r), v),
 eps = DBL_EPSILON, floor = 1e-10.
 
-Tolerances (derived, not tuned). Device and numpy add the same <= 27 dim products of a row in different orders, so
-    |raw_dev - raw_np| <= C eps sum_j |c_ij| |q_j| / m_i        row by row,
-with the project's function-level 1e-13 in place of C eps (about 30 x 1.1e-16 x the few operations of a primitive
-state; tests/test_oracle_golden_* use the same figure): raw_tolerance() returns that bound PER ROW. The bounds carry
+Tolerances (derived, not tuned). Device and numpy add the same W_i dim products of a row (W_i its entry count) in
+different orders, so
+    |raw_dev - raw_np| <= C_i eps sum_j |c_ij| |q_j| / m_i        row by row,
+with C_i eps = max(1e-13, 2 W_i u), u = eps / 2 = 1.1e-16 the unit round-off: the project's function-level 1e-13
+(about 30 x 1.1e-16 x the few operations of a primitive state; tests/test_oracle_golden_* use the same figure), and for
+wide rows the forward bound of recursive summation, W_i u, on both sides. 2 W u exceeds 1e-13 from W = 451 on: for every
+row of up to 450 entries -- every row of a Q1, Q2 or P1 mesh -- the bound IS the 1e-13 it has always been, bit for bit
+(the factor below is exactly 1.0 there); a row of 1023 entries gets 2.27e-13. raw_values() returns the row magnitude with
+that factor folded in, scale_i = max(1, 2 W_i u / 1e-13) sum_j |c_ij| |q_j| / m_i, and raw_tolerance() = 1e-13 scale_i
+is the bound PER ROW. The bounds carry
 the bound of the rows that attain them. The normalisation has slope <= beta / max(q_max - q_min, eps) in the raw value
 and in each of the two bounds, hence normalised_tolerance() = beta (delta_i + 2 delta_bounds) / (q_max - q_min) + 4 eps."""
 from __future__ import annotations
@@ -31,16 +37,24 @@ SCHLIEREN, VORTICITY = capi.PP_SCHLIEREN, capi.PP_VORTICITY
 
 
 def csr(off):
-    """(row of every entry, column of every entry, c_ij [nnz_owned, dim], m_i [n_owned], row lengths) of the OWNED rows"""
+    """(row of every entry, column of every entry, c_ij [nnz_owned, dim], m_i [n_owned], row lengths) of the OWNED rows.
+    The generator's offline object carries row_starts, columns, cij and mi as attributes; the numpy-backed
+    helpers_layout.OfflineView (P1, Q2 and prescribed-width meshes, partitions of them) keeps the arrays it hands to the
+    library in _keep -- the same plain CSR, read from there."""
     o = off.c.contents
     assert o.simd_length == 1 or o.n_internal == 0, "plain CSR expected"
     n = off.n_owned
-    ptr = off.row_starts.astype(np.int64)[: n + 1]
+    keep = getattr(off, "_keep", None)
+    if keep is not None:
+        row_starts, columns, cij, mi = keep["row_starts"], keep["columns"], keep["cij"].reshape(-1, off.dim), keep["mi"]
+    else:
+        row_starts, columns, cij, mi = off.row_starts, off.columns, off.cij, off.mi
+    ptr = row_starts.astype(np.int64)[: n + 1]
     assert ptr[0] == 0
     lens = np.diff(ptr)
     rows = np.repeat(np.arange(n, dtype=np.int64), lens)
     nnz = int(ptr[n])
-    return rows, off.columns[:nnz].astype(np.int64), off.cij[:nnz], off.mi[:n], lens
+    return rows, columns[:nnz].astype(np.int64), cij[:nnz], mi[:n], lens
 
 
 def primitive_state(equation: int, dim: int, U: np.ndarray, params=None) -> np.ndarray:
@@ -72,7 +86,8 @@ def primitive_state(equation: int, dim: int, U: np.ndarray, params=None) -> np.n
 
 def raw_values(off, U, quantities, equation=capi.EQ_EULER, params=None):
     """quantities: [(kind, is_primitive, component)]. Returns (raw [nq, n_owned], scale [nq, n_owned]) with
-    scale_i = sum_j |c_ij| |q_j| / m_i, the magnitude the rounding error of row i is proportional to."""
+    scale_i = max(1, 2 W_i u / 1e-13) sum_j |c_ij| |q_j| / m_i (u = eps / 2), the magnitude the rounding error of row i is
+    proportional to (the first factor is exactly 1.0 for rows of up to 450 entries, see the module docstring)."""
     dim = off.dim
     rows, cols, c, mi, lens = csr(off)
     n = off.n_owned
@@ -80,6 +95,7 @@ def raw_values(off, U, quantities, equation=capi.EQ_EULER, params=None):
     V = primitive_state(equation, dim, U, params) if any(p for _, p, _ in quantities) else U
     c_norm = np.sqrt((c * c).sum(axis=1))
     active = lens > 1
+    wide = np.maximum(1.0, 2.0 * lens * (0.5 * EPS) / FUNCTION_LEVEL)
 
     def row_sum(w):
         return np.bincount(rows, weights=w, minlength=n)
@@ -105,7 +121,7 @@ def raw_values(off, U, quantities, equation=capi.EQ_EULER, params=None):
                 value = np.sqrt((w * w).sum(axis=1)) / mi
             q_norm = np.sqrt((q * q).sum(axis=1))
         raw[k] = np.where(active, value, 0.0)
-        scale[k] = row_sum(c_norm * q_norm) / mi
+        scale[k] = wide * (row_sum(c_norm * q_norm) / mi)
     return raw, scale
 
 
