@@ -24,7 +24,8 @@ On a REAL dG stencil the column positions are not alike: an entry (i, j) with j 
 common face has c_ij = m_ij = (M^-1)_ij = 0, its P_ij is exactly 0 and its l_ij exactly 1 whatever the data -- among them
 position 1 of every row with a lower neighbour and the last position of every row with an upper one. There the
 conditions on "the first / the last column" are stated for the first / last position of the block (of a widest row) that
-holds a structurally non-zero entry in some row; on the synthetic data they are the plain ones."""
+holds a structurally non-zero entry in some row; on the synthetic data they are the plain ones. (dG-Q1 in ONE dimension:
+the face pairs themselves have P_ij = 0 without stage vectors -- can_be_limited() leaves them out.)"""
 from __future__ import annotations
 
 import numpy as np
@@ -239,6 +240,14 @@ _entry("euler_q2_2d", _dg_mesh((12, 12), 2, grade=True), 1296, 45, "euler", _eul
        _dg_plan(D, 0, False, fast_riemann=True), warm=12, incidence=True)
 _entry("sw_q2_2d", _dg_mesh((12, 12), 2, grade=True), 1296, 45, "shallow_water", _sw_hump(radius=0.25),
        _dg_plan(D, 0, False), warm=12, incidence=True)
+# EulerAEOS dG in 1-D on the 64 graded cells of euler_q2_1d: rows of 4 / 6 (degree 1) and 6 / 9 (degree 2) entries, inside
+# the limit of 32. k_low_order_aeos<1, false | true, true, true>, k_pij_lij<EulerAeos<1>, true, false>
+_entry("aeos_q1_1d", _dg_mesh((64,), 1, grade=True), 128, 6, "euler_aeos", _aeos_blast(),
+       _dg_plan(A, 9, False, step2_split=True), warm=12, edit=_polytropic)
+_entry("aeos_q2_1d", _dg_mesh((64,), 2, grade=True), 192, 9, "euler_aeos", _aeos_blast(),
+       _dg_plan(A, 9, False, step2_split=True), warm=12, edit=_polytropic, incidence=True)
+_entry("aeos_q1_1d_erk33_step2", _dg_mesh((64,), 1, grade=True), 128, 6, "euler_aeos", _aeos_blast(),
+       _dg_plan(A, 9, False, step2_split=True, step4_has_stages=True), warm=12, edit=_polytropic, stages=2)
 # Euler dG-Q2 3-D, 4^3 cells: rows of up to 189 entries = three blocks of 63. k_pij_lij<Euler<3>, true, true>,
 # k_high_order<.., false, true>
 _entry("euler_q2_3d", _dg_mesh((4, 4, 4), 2, grade=True), 1728, 189, "euler", _euler_blast(0.5, radius=0.4),
@@ -520,15 +529,27 @@ def structurally_nonzero(off):
     return (np.abs(cij).max(axis=1) > 0.0) | (np.asarray(off._keep["mij"]) != 0.0) | (off._dg[1] != 0.0)
 
 
+def can_be_limited(off):
+    """structurally_nonzero() without the entries whose P_ij vanishes for another reason. dG-Q1 in ONE dimension: the only
+    coupling across a face is between the two DoFs on the common node, with incidence 1 -- alpha_ij = fmax(.., 1) = 1, so
+    d^H_ij = d^L_ij, and m_ij = (M^-1)_ij = 0: without stage vectors P_ij is exactly 0 and l_ij exactly 1 whatever the
+    data (tests/test_dg_cases_cpu.py asserts it on the oracle). In two and three dimensions those pairs share their column
+    positions with the other DoFs of the face, and nothing is excluded."""
+    held = structurally_nonzero(off)
+    if off.dim == 1:
+        held = held & ~((off._dg[0] == 1.0) & (np.asarray(off._keep["mij"]) == 0.0) & (off._dg[1] == 0.0))
+    return held
+
+
 def coverage(off, first_pass_lij, width):
     """dict of counts that must all be positive (see the module docstring). `first` / `last` of a block: the first / last
-    column position of the block at which some row holds a structurally non-zero entry -- the block's own first and last
-    position wherever the data is synthetic."""
+    column position of the block at which some row holds an entry that can be limited (can_be_limited: structurally
+    non-zero) -- the block's own first and last position wherever the data is synthetic."""
     widths, rs, rows, position = _pattern(off)
     l = np.asarray(first_pass_lij)[: rs[-1]]
     inside = (l > 0.0) & (l < 1.0) & (position > 0)
     per_position = np.bincount(position[inside], minlength=width)
-    can = np.bincount(position[structurally_nonzero(off) & (position > 0)], minlength=width) > 0
+    can = np.bincount(position[can_be_limited(off) & (position > 0)], minlength=width) > 0
     out = {}
     for first in range(1, width, BLOCK):
         last = min(first + BLOCK, width) - 1
@@ -538,7 +559,7 @@ def coverage(off, first_pass_lij, width):
         out[f"first column {held[0]} of block {first}..{last}"] = int(per_position[held[0]])
         out[f"last column {held[-1]} of block {first}..{last}"] = int(per_position[held[-1]])
     widest = widths[rows] == width
-    held = np.flatnonzero(np.bincount(position[structurally_nonzero(off) & widest & (position > 0)], minlength=width))
+    held = np.flatnonzero(np.bincount(position[can_be_limited(off) & widest & (position > 0)], minlength=width))
     out[f"last column {held[-1]} of a widest row"] = int((inside & widest & (position == held[-1])).sum())
     for w in np.unique(widths):
         out[f"width {w}"] = int((inside & (widths[rows] == w)).sum())

@@ -4,7 +4,8 @@
   3 | 4 (1-D), 9 | 10 (2-D), 27 | 28 (3-D)   k_dij_diag_unrolled<3 | 9 | 27> -> k_dij_diag; steps 6 / 7 cached ->
                                              k_high_order; step 5 k_lij_stage0 -> k_pij_lij_recompute (Euler, dim <= 2)
                                              or k_pij_lij; shallow water leaves the single walk of step 4
-  32 | 33                                    step 2: records / alpha_then_dij -> k_dij_alpha; EulerAEOS is refused
+  32 | 33                                    step 2: records / alpha_then_dij -> k_dij_alpha; EulerAEOS is refused (its
+                                             cases stand at 4, 9 | 10, 31 in 1-D, 10, 32 in 2-D, 28, 32 in 3-D)
   64 | 65                                    `wide`: k_pij_lij / k_high_order walk the columns in blocks of 63; Euler up
                                              to two dimensions leaves k_pij_lij_recompute (one 64-bit mask per row)
   127 | 128                                  two full blocks | a third block of one column
@@ -45,7 +46,7 @@ def _lattice(shape, width, n_pairs=12):
     return make
 
 
-def _ring(n, width):
+def _ring(n, width, two_partners=False):
     """1-D: a ring (the row sums of an open chain vanish only with c_ij of both signs that cancel across every cut).
     Rows of width - 2 or width - 3 entries, widened in every slice: the nodes a with 8 <= a mod 64 < 24 are paired with
     a + s, s the first offset beyond the stencil -- one or two more entries per row --, and for an even width the nodes
@@ -53,14 +54,16 @@ def _ring(n, width):
     More than 64 entries (s >= 32: the run and its partners a + s no longer overlap, no row would get two more entries):
     every node of the run is paired with a + s AND a + s + 1, all indices modulo n -- the run has the full width, its
     partners one or two entries more than the other rows --, and for an even width the nodes 14 mod 64 with a + s + 2 as
-    well; s is raised until s mod 64 lies in [17, 38], so that no partner is a node of another slice's run."""
+    well; s is raised until s mod 64 lies in [17, 38], so that no partner is a node of another slice's run.
+    two_partners: that recipe at any width (the first one reaches 31 entries at the most: a request of 32 or 33 gives
+    rows of 31 or 32)."""
     def make():
         base = width - 2 if width % 2 else width - 3
         s = (base - 1) // 2 + 1
         a = np.arange(n)
         if base == 1:   # width 4: rows of three entries, a single pair per slice
             base, pairs = 3, np.stack([a[a % 64 == 10], a[a % 64 == 10] + 2], axis=1)
-        elif width > 64:
+        elif width > 64 or two_partners:
             while not 17 <= s % 64 <= 38:   # the partners 8 + s ... 23 + s + 2 stay clear of the runs of other slices
                 s += 1
             run, extra = a[(a % 64 >= 8) & (a % 64 < 24)], a[a % 64 == 14]
@@ -182,6 +185,11 @@ def _aeos(p):
     p.compute_strict_bounds = 1
 
 
+def _aeos_checked(p):
+    _aeos(p)
+    _checked(p)
+
+
 # ------------------------------------------------------------------ expected plans (literals)
 
 def _euler_recompute(step2, diag_width, **kw):
@@ -203,11 +211,14 @@ def _runs(n_slices, *grid_y):
                  step6_launches=[dict(n_slices=n_slices, grid_y=1, shares_slices=False)]) for y in grid_y]
 
 
-def _entry(name, shape, n_slices, width, equation, data, plan, grid_y=(1,), *, edit=None, options=(), stages=0):
+def _entry(name, shape, n_slices, width, equation, data, plan, grid_y=(1,), *, edit=None, options=(), stages=0,
+           request=None):
+    """width: the widest row the mesh has; request: the width asked of the recipe where the two differ"""
     runs = _runs(n_slices, *grid_y)
-    mesh = _ring(shape[0], width) if len(shape) == 1 else _lattice(shape, width)
+    request = width if request is None else request
+    mesh = _ring(shape[0], request) if len(shape) == 1 else _lattice(shape, request)
     case = _case(mesh, equation, data, int(np.prod(shape)), plan, runs[0], warm=1, edit=edit, cfl=0.5, stages=stages)
-    CASES[name] = dict(case, width=width, runs=runs, options=tuple(options))
+    CASES[name] = dict(case, width=width, request=request, runs=runs, options=tuple(options))
 
 
 CASES = {}
@@ -261,12 +272,34 @@ for _w, _flux, _diag, _wide in ((10, _kpp, 27, F), (28, _burgers, 0, F), (65, _k
 for _w, _diag in ((10, 27), (32, 0)):
     _entry(f"aeos_2d_{_w}", PLANE, 15, _w, "euler_aeos", _euler_patches,
            _stored("alpha_then_dij", _diag, F, step2_split=True), edit=_aeos)
+# ... in 1-D (rings; the recipe reaches 31 entries at a request of 32) and 3-D, step<2> of ERK33 with stage vectors, the
+# checked build: four bounds and four precomputed values per node throughout
+_A = "alpha_then_dij"
+for _w, _diag, _request in ((4, 9, 4), (9, 9, 9), (10, 27, 10), (31, 0, 32)):
+    _entry(f"aeos_1d_{_w}", LINE, 10, _w, "euler_aeos", _euler_patches, _stored(_A, _diag, F, step2_split=True),
+           edit=_aeos, request=_request)
+for _w in (28, 32):
+    _entry(f"aeos_3d_{_w}", BOX, 16, _w, "euler_aeos", _euler_patches, _stored(_A, 0, F, step2_split=True), edit=_aeos)
+_entry("aeos_3d_erk33_28", BOX, 16, 28, "euler_aeos", _euler_patches,
+       _stored(_A, 0, F, step2_split=True, step4_has_stages=True), edit=_aeos, stages=2)
+_entry("aeos_2d_erk33_32", PLANE, 15, 32, "euler_aeos", _euler_patches,
+       _stored(_A, 0, F, step2_split=True, step4_has_stages=True), edit=_aeos, stages=2)
+_entry("aeos_3d_checked_28", BOX, 16, 28, "euler_aeos", _euler_patches,
+       _stored(_A, 0, F, step2_split=True, checked=True), edit=_aeos_checked, options=("checked=1",))
 
-del _w, _flux, _step2, _diag, _wide, R, D, F, T
+del _w, _flux, _step2, _diag, _wide, _request, _A, R, D, F, T
 
 # EulerAEOS with 33 entries: step() refuses on the host, before any launch, and the context runs on (step_plan.hpp)
 AEOS_REFUSED = dict(shape=PLANE, width=33, accepted=CASES["aeos_2d_32"],
                     message="euler aeos: stencils of more than 32 entries")
+# ... and in 1-D (a ring with two partners per widened node: rows of exactly 33 entries) and 3-D; `accepted`: the case
+# run afterwards
+AEOS_REFUSED_DIMENSIONS = {
+    "1d": dict(mesh=_ring(LINE[0], 33, two_partners=True), dim=1, n_slices=10, width=33, accepted="aeos_1d_31",
+               message=AEOS_REFUSED["message"]),
+    "3d": dict(mesh=_lattice(BOX, 33), dim=3, n_slices=16, width=33, accepted="aeos_3d_32",
+               message=AEOS_REFUSED["message"]),
+}
 
 
 # ------------------------------------------------------------------ what a case must show before it counts

@@ -48,6 +48,16 @@ def slabs(n_ranks):
     return owner
 
 
+def halves_from(start):
+    """1-D: the contiguous half of the ring that begins at node `start`, and the rest. (slabs(2) cuts a ring of whole
+    slices between two slices, where no widened row of a ring of at most 64 entries reaches: with `start` inside the
+    widened run both cuts pass through rows of the widest width.)"""
+    def owner(off):
+        n = off.lattice_shape[0]
+        return (((np.arange(off.n_owned) - start) % n) >= n // 2).astype(np.int64)
+    return owner
+
+
 def uneven(off):
     """three ranks: cuts at 1/8 and 1/2 of the last axis, one node further wherever the axis-0 index is a multiple of 7
     -- a ragged cut; the small first rank has nothing but export rows, and not a multiple of 64 of them"""
@@ -99,14 +109,17 @@ LINE, PLANE, PLANE_LONG, PLANE_1023, BOX_LONG = (640,), (40, 24), (40, 48), (40,
 RANK_CASES = {}
 
 
-def _rank_entry(name, basis, shape, owner, ranks, *, no_split=False, n_pairs=None):
+def _rank_entry(name, basis, shape, owner, ranks, *, no_split=False, n_pairs=None, ghost_extrema=False):
     """ranks: per rank (n_owned, n_export, [(slices, gridDim.y of step 5, step 6 shares) per launch]); n_pairs (an even
     width): that many widened pairs, so that every rank has widest rows next to a cut, and the nodes of their last
-    columns made extrema (last_ghost_columns)"""
+    columns made extrema (last_ghost_columns); ghost_extrema: those extrema on the mesh as it is"""
     base = CASES[basis]
     data = base["data"]
+    if ghost_extrema:
+        def data(off, inner=base["data"]):
+            return inner(off, more=lambda o: last_ghost_columns(o, owner(o)))
     if len(shape) == 1:
-        mesh = cases._ring(shape[0], base["width"])
+        mesh = cases._ring(shape[0], base["request"])   # (the width asked of the recipe: aeos_1d_31 asks for 32)
     elif n_pairs is None:
         mesh = cases._lattice(shape, base["width"])
     else:
@@ -165,6 +178,9 @@ _rank_entry("scalar_2d_65", "scalar_2d_65", PLANE_LONG, slabs(2), [_two(960, 320
 _rank_entry("aeos_2d_32", "aeos_2d_32", PLANE_LONG, slabs(2), [_two(960, 240, 4, 15)] * 2)
 # a ring of rows of up to 65 entries, cut into two contiguous halves: k_pij_lij<Euler<1>, false, true>
 _rank_entry("euler_1d_65", "euler_1d_65", LINE, slabs(2), [_two(320, 62, 1, 5)] * 2)
+# EulerAEOS in 3-D and 1-D: four bound vectors and four precomputed values per node in the ghost range
+_rank_entry("aeos_3d_28", "aeos_3d_28", BOX_LONG, slabs(2), [_two(1024, 256, 4, 16)] * 2, n_pairs=96)
+_rank_entry("aeos_1d_31", "aeos_1d_31", LINE, halves_from(24), [_two(320, 30, 1, 5)] * 2, ghost_extrema=True)
 
 
 # ------------------------------------------------------------------ building and running a case (shared by the tests)

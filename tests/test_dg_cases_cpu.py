@@ -288,8 +288,33 @@ def test_structural_zeros_of_a_dg_stencil_are_never_limited(oracle):
         assert (alone["lij_next"][: len(held)][~held] == 1.0).all()
 
 
+def test_unit_incidence_pairs_of_a_1d_dg_q1_stencil_are_never_limited(oracle):
+    """why coverage() leaves the face pairs of dG-Q1 in one dimension out (helpers_dg_cases.can_be_limited): incidence 1,
+    m_ij = (M^-1)_ij = 0 -- without stage vectors the oracle's P_ij is exactly 0 there and its first-pass l_ij exactly 1;
+    they are the column positions 2 and 4, every other structurally non-zero entry stays in the condition; and no other
+    1-D case of the table has such an entry"""
+    import helpers_plan_cases as plan_cases
+    name = "aeos_q1_1d"
+    case = cases.CASES[name]
+    (off, dirichlet, states, _, _), alone = cases.developed(name, oracle)
+    widths, rs, rows, position = cases._pattern(off)
+    left_out = cases.structurally_nonzero(off) & ~cases.can_be_limited(off)
+    assert left_out.sum() == 2 * 63 and set(position[left_out]) == {2, 4} and (off._dg[0][left_out] == 1.0).all()
+    m = HyperbolicModule(off, plan_cases.params_of(case, oracle, 1), backend=oracle.backend())
+    old, new = m.new_state_vector(states[-1]), m.new_state_vector()
+    m.prepare_state_vector(old, 0.0, dirichlet)
+    m.step(old, [], [], new)
+    pij = np.asarray(m.debug_fetch("pij")).reshape(rs[-1], -1)
+    m.close()
+    assert not pij[left_out].any() and np.abs(pij[cases.can_be_limited(off) & (position > 0)]).max() > 1.0
+    assert (alone["lij_next"][: rs[-1]][left_out] == 1.0).all()
+    for other in ("euler_q2_1d", "aeos_q2_1d", "synthetic_euler_1d_65"):
+        mesh = cases.CASES[other]["mesh"]()
+        assert np.array_equal(cases.can_be_limited(mesh), cases.structurally_nonzero(mesh)), other
+
+
 @pytest.mark.parametrize("name", ["euler_q2_1d", "euler_q1_2d_checked", "euler_q1_3d", "sw_q1_2d_checked", "sw_q2_2d",
-                                  "aeos_q1_2d", "synthetic_euler_1d_65", "synthetic_euler_2d_65",
+                                  "aeos_q1_2d", "aeos_q1_1d", "aeos_q2_1d", "synthetic_euler_1d_65", "synthetic_euler_2d_65",
                                   "synthetic_euler_3d_65", "synthetic_sw_2d_65"])
 def test_the_dg_branch_is_in_effect(oracle, name):
     """once per Description and dimension: the same data with discontinuous_ansatz = 0 changes U_new by more than 1e-6 of

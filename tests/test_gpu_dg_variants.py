@@ -20,6 +20,8 @@ Kernels per case (step 6 is k_high_order<E, false, W > 64>, step 7 k_high_order<
   euler | sw | aeos_q1_2d_checked    k_check_limiter / k_check_admissible on the combined bounds
   euler_q1_2d_slip | dirichlet       boundary rows of a dG stencil
   euler_q2_1d, euler | sw_q2_2d      rows of 9 / 45 entries, graded meshes: fractional incidence, (M^-1)_ij per cell
+  aeos_q1_1d, aeos_q2_1d, aeos_q1_1d_erk33_step2
+                                     k_low_order_aeos<1, false | true, true, true>, k_pij_lij<EulerAeos<1>, true, false>
   euler_q2_3d                        rows of 189 entries: k_pij_lij<Euler<3>, true, true>, k_high_order<.., false, true>
   synthetic_*                        k_pij_lij<E, true, W > 64> on lattices with the widest row at 64 | 65, 127 | 128
   EulerAEOS dG-Q1 3-D, dG-Q2 2-D     refused by step() on the host

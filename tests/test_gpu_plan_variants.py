@@ -17,11 +17,18 @@ block share a slice in step 6):
   euler_2d_step_1588, box_4096, box_4097   k_lij_stage0<Euler<2>, 1, false, true>, not shared; boundary conditions
                                            folded into the pre-pass up to 4096 slices, a launch of their own above
   aeos_2d_step_674 / 896                   k_lij_stage0<EulerAeos<2>, 3 / 2>, shared
+  aeos_1d_512 / 513 / 680 / 681 / 1024     k_lij_stage0<EulerAeos<1>, 4 / 3 / 3 / 2 / 2>, shared
+  aeos_1d_1025, aeos_2d_step_1588          k_lij_stage0<EulerAeos<1 | 2>, 1, false, true> (P_ij per tile), not shared
+  aeos_3d_box_562 / 1000 / 1424            k_lij_stage0<EulerAeos<3>, 3 / 2 / 1>, 1000 with the Noble-Abel stiffened gas;
+                                           1424, second update: <EulerAeos<3>, 1, true, false> and step 6 as light,
+                                           repair, heavy
   euler_3d_box_562 / 1000 / 1424           k_lij_stage0<Euler<3>, 3 / 2 / 1>; 1424, second update: <Euler<3>, 1, true, false>
                                            (P_ij per slice) and step 6 as light, repair, heavy
   sw_2d_1001 / 1148, scalar_2d_1001 / 1148 k_pij_lij, P_ij everywhere; step 6 shared / not shared
   euler_q2_625 / 900 / 1225                k_pij_lij_recompute<2, 3 / 2 / 1>, k_high_order
   erk33 (896 slices)                       step<1>, step<2>: k_pij_lij, step 6 shared
+  erk33_aeos_1d_681, erk33_aeos_3d_box_562 step<1>, step<2>: k_low_order_aeos<1 | 3, true, ...>, k_pij_lij<EulerAeos<1 | 3> >,
+                                           step 6 shared in 1-D, not shared in 3-D
   two ranks, shallow water                 step 6 shared in the export part, not shared in the interior part"""
 import numpy as np
 import pytest
@@ -47,8 +54,15 @@ def _assert_plan(m, expected_plan, step5_launches, step6_launches, label):
     assert got["step6_launches"] == step6_launches, (label, got["step6_launches"])
 
 
+def _print_measured(label, g):
+    """the largest difference of every compared array, in its bound's units (profiles/aeos_dimensions_pytest_gpu.txt)"""
+    print(f"\nplan_variants {label}: " + " ".join(f"{k}={v:.2e}" for k, v in g["measured"].items()) +
+          f" slack_used={g['slack_used']} flips={g['n_flips']}")
+
+
 def _compare(off, mods, oracle, params, dirichlet, label, **kw):
     g, c = compare_step(off, mods, dirichlet, oracle=oracle, params=params, label=label, **kw)
+    _print_measured(label, g)
     assert g["status"] == 0
     return g, c
 
@@ -81,7 +95,17 @@ def test_erk33_stages_with_stage_vectors_share_slices_in_step_6(oracle):
     """step<1> and step<2> of ERK33 (time_integrator.template.h:373-403) on the Mach-3 step at 896 slices: with stage
     vectors step 4 stores P_ij, step 5 is k_pij_lij and step 6 shares slices. Every stage on identical inputs (the
     oracle's stage result goes to both backends), as test_erk43_erk54_parity_with_the_oracle."""
-    case = cases.ERK33_CASE
+    _erk33_stages(oracle, cases.ERK33_CASE, "erk33")
+
+
+@pytest.mark.parametrize("name", sorted(set(cases.ERK33_CASES) - {"erk33"}))
+def test_erk33_stages_with_stage_vectors_on_euler_aeos(oracle, name):
+    """the same on EulerAEOS in 1-D (681 slices: step 6 shares slices) and 3-D (562 slices): k_low_order_aeos with stage
+    vectors -- the stage vectors' precomputed pressures enter the fluxes --, step 5 is k_pij_lij"""
+    _erk33_stages(oracle, cases.ERK33_CASES[name], name)
+
+
+def _erk33_stages(oracle, case, name):
     off, U0, dirichlet, after_warm = cases.build(case)
     assert off.n_owned == case["n_points"]
     U_start = cases.warm_up(case, oracle, off, U0, dirichlet, after_warm)
@@ -97,14 +121,15 @@ def test_erk33_stages_with_stage_vectors_share_slices_in_step_6(oracle):
             for q in idx:   # stage vectors are prepared state vectors (hyperbolic_module.h:207-213)
                 m.prepare_state_vector(vec[id(m)][q], 0.0, dirichlet)
         step_mods = [(mg, vec[id(mg)][stage], vec[id(mg)][stage + 1]), (mc, vec[id(mc)][stage], vec[id(mc)][stage + 1])]
-        g, c = compare_step(off, step_mods, dirichlet, tau, oracle=oracle, params=params, label=f"erk33 stage {stage}",
+        g, c = compare_step(off, step_mods, dirichlet, tau, oracle=oracle, params=params, label=f"{name} stage {stage}",
                             stage_vectors=([vec[id(mg)][q] for q in idx], [vec[id(mc)][q] for q in idx]),
                             stage_weights=weights)
+        _print_measured(f"{name} stage {stage}", g)
         assert g["status"] == 0
         tau = c["tau"]
         if stage > 0:
-            _assert_coverage(off, c["lij_next"], f"erk33 stage {stage}")
-            _assert_plan(mg, case["plan"], case["step5_launches"], case["step6_launches"], f"erk33 stage {stage}")
+            _assert_coverage(off, c["lij_next"], f"{name} stage {stage}")
+            _assert_plan(mg, case["plan"], case["step5_launches"], case["step6_launches"], f"{name} stage {stage}")
         vec[id(mg)][stage + 1].upload(vec[id(mc)][stage + 1].download())
     for m, _, _ in mods:
         m.close()

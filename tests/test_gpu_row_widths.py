@@ -24,7 +24,12 @@ Kernels of steps 2 / 3 / 5 / 6 per case (W the widest row; step 7 is k_high_orde
   sw_1d_4, sw_2d_10 ... 128          k_low_order_sw (two walks; friction at 33), k_pij_lij<ShallowWater<dim>, false, W > 64>
   scalar_2d_10, 28, 65, 128          k_dij_alpha_sc, k_low_order_sc, k_pij_lij<ScalarConservation<2>, false, W > 64>
   aeos_2d_10, 32                     k_alpha_aeos + k_dij_aeos, k_low_order_aeos storing P_ij, k_pij_lij<EulerAeos<2> >
-  EulerAEOS with 33 entries          refused by step() on the host"""
+  aeos_1d_4, 9 | 10, 31              k_dij_diag_unrolled<9 | 27> | k_dij_diag, k_low_order_aeos<1, false, true, false>,
+                                     k_pij_lij<EulerAeos<1> >, k_high_order
+  aeos_3d_28, 32                     k_low_order_aeos<3, false, true, false>, k_pij_lij<EulerAeos<3> >
+  aeos_3d_erk33_28, aeos_2d_erk33_32 step<2> of ERK33: k_low_order_aeos<3 | 2, true, true, false>
+  aeos_3d_checked_28                 k_check_limiter / k_check_admissible on four bounds
+  EulerAEOS with 33 entries          refused by step() on the host, in one, two and three dimensions"""
 import numpy as np
 import pytest
 
@@ -76,7 +81,20 @@ def test_euler_aeos_refuses_33_entries_and_runs_on(oracle):
     refusal on the host before any launch, again on the next call --, the state vectors are untouched, and the library
     runs the 32-wide case afterwards as ever."""
     refused = cases.AEOS_REFUSED
-    case = dict(refused["accepted"], mesh=cases._lattice(refused["shape"], refused["width"]))
+    _refused_then_accepted(oracle, dict(refused["accepted"], mesh=cases._lattice(refused["shape"], refused["width"])),
+                           refused["message"], "aeos_2d_32")
+
+
+@pytest.mark.parametrize("key", sorted(cases.AEOS_REFUSED_DIMENSIONS))
+def test_euler_aeos_refuses_33_entries_in_one_and_three_dimensions(oracle, key):
+    """the same on a ring and on a 3-D lattice with a row of 33 entries; afterwards the widest accepted case of that
+    dimension runs"""
+    refused = cases.AEOS_REFUSED_DIMENSIONS[key]
+    _refused_then_accepted(oracle, dict(cases.CASES[refused["accepted"]], mesh=refused["mesh"]), refused["message"],
+                           refused["accepted"])
+
+
+def _refused_then_accepted(oracle, case, message, accepted):
     import helpers_plan_cases as plan_cases
     off, U0, dirichlet, _ = plan_cases.build(case)
     assert off.max_row_len == 33
@@ -84,8 +102,8 @@ def test_euler_aeos_refuses_33_entries_and_runs_on(oracle):
     old, new = m.new_state_vector(U0), m.new_state_vector(np.zeros_like(U0))
     m.prepare_state_vector(old, 0.0, dirichlet)
     for _ in range(2):
-        with pytest.raises(RuntimeError, match=f"status {capi.RYUJIN_ERR_UNSUPPORTED}: {refused['message']}"):
+        with pytest.raises(RuntimeError, match=f"status {capi.RYUJIN_ERR_UNSUPPORTED}: {message}"):
             m.step(old, [], [], new)
     assert np.array_equal(old.download(), U0) and not new.download().any()
     m.close()
-    _run_case(oracle, "aeos_2d_32")
+    _run_case(oracle, accepted)

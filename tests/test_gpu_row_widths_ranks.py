@@ -24,7 +24,9 @@ Kernels of steps 2 / 3 / 5 / 6 per case (step 7 is k_high_order<E, true, false> 
   euler_2d_checked_65                 the same with k_check_limiter / k_check_admissible behind them
   euler_3d_33, 128                    k_pij_lij<Euler<3>, false, false | true>
   sw_2d_10, 33 (friction), 65         the two walks of k_low_order_sw, k_pij_lij<ShallowWater<2>, false, W > 64>
-  scalar_2d_65, aeos_2d_32            k_dij_alpha_sc / k_alpha_aeos + k_dij_aeos, k_pij_lij<.., false, W > 64>"""
+  scalar_2d_65, aeos_2d_32            k_dij_alpha_sc / k_alpha_aeos + k_dij_aeos, k_pij_lij<.., false, W > 64>
+  aeos_3d_28 (two slabs), aeos_1d_31 (two halves of the ring, cut through the widened run)
+                                      k_ghost_records_aeos<3 | 1>, k_pij_lij<EulerAeos<3 | 1> >, four bounds in the ghost range"""
 import numpy as np
 import pytest
 

@@ -61,12 +61,15 @@ def test_the_lattice_of_the_wide_ragged_parity_test():
     assert widths.max() == 49 and widths.min() == 16
 
 
-@pytest.mark.parametrize("name", sorted(cases.CASES) + ["aeos_refused"])
+@pytest.mark.parametrize("name", sorted(cases.CASES) + ["aeos_refused", "aeos_refused_1d", "aeos_refused_3d"])
 def test_layout_round_trip(name):
     """ryujin_hip_debug_layout (CSR -> SELL-64 -> logical view): the pattern and a three-component matrix come back
     entry by entry, and `transposed` is the involution (i, j) <-> (j, i)"""
     if name == "aeos_refused":
         off = cases._lattice(cases.AEOS_REFUSED["shape"], cases.AEOS_REFUSED["width"])()
+    elif name.startswith("aeos_refused_"):
+        off = cases.AEOS_REFUSED_DIMENSIONS[name[-2:]]["mesh"]()
+        assert off.max_row_len == 33
     else:
         off = _mesh(name)
     n, nnz = off.n_owned, len(off.columns)

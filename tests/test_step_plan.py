@@ -139,12 +139,12 @@ def _assert_table_entry(r, n_slices, plan, step5_launches, step6_launches):
     assert sum(q["n_slices"] for q in launches) == n_slices
 
 
-@pytest.mark.parametrize("name", sorted(plan_cases.CASES) + ["erk33"])
+@pytest.mark.parametrize("name", sorted(plan_cases.CASES) + sorted(plan_cases.ERK33_CASES))
 def test_case_table_of_the_gpu_variants_is_what_plan_step_decides(checker, name):
     """Every entry of tests/helpers_plan_cases.py: the mesh of the case is built, n_owned and the widest row are taken
     from it, and the plan and the per-launch decisions plan_step() makes of them must equal the table's literals -- the
     table the GPU test holds HyperbolicModule.last_plan() against."""
-    case = plan_cases.ERK33_CASE if name == "erk33" else plan_cases.CASES[name]
+    case = plan_cases.ERK33_CASES[name] if name in plan_cases.ERK33_CASES else plan_cases.CASES[name]
     off = case["mesh"]()
     assert off.n_owned == case["n_points"]
     widths = plan_cases.widths_of(off)
@@ -155,6 +155,23 @@ def test_case_table_of_the_gpu_variants_is_what_plan_step_decides(checker, name)
         n_slices, r = _checked_plan(checker, case["equation"], off.dim, widths, off.n_owned, update["limited_fraction"],
                                     case["stages"], sizes)
         _assert_table_entry(r, n_slices, update["plan"], update["step5_launches"], update["step6_launches"])
+
+
+def test_limited_fraction_of_the_second_update_is_the_oracles(oracle):
+    """aeos_3d_box_1424: the fraction the second update's plan literal carries is the share of slices in which the
+    oracle's first-pass l_ij of the FIRST compared update is below 1, and it lies below the 0.8 up to which P_ij is
+    stored per slice"""
+    from ryujin_amd import HyperbolicModule
+    case = plan_cases.CASES["aeos_3d_box_1424"]
+    off, U0, dirichlet, after_warm = plan_cases.build(case)
+    U_start = plan_cases.warm_up(case, oracle, off, U0, dirichlet, after_warm)
+    m = HyperbolicModule(off, plan_cases.params_of(case, oracle, off.dim), backend=oracle.backend())
+    old, new = m.new_state_vector(U_start), m.new_state_vector()
+    m.prepare_state_vector(old, 0.0, dirichlet)
+    m.step(old, [], [], new)
+    fraction = plan_cases.limited_slice_fraction(off, m.debug_fetch("lij_next"))
+    m.close()
+    assert fraction == case["second_update"]["limited_fraction"] == 719 / 1424 < 0.8
 
 
 def test_case_table_two_ranks(checker):
@@ -215,6 +232,20 @@ def test_euler_aeos_with_33_entries_is_refused_and_32_is_not(checker):
     assert out.returncode == 1 and out.stderr.strip() == refused["message"]
     off = width_cases._lattice(refused["shape"], refused["width"])()
     assert plan_cases.widths_of(off).max() == 33 and refused["accepted"]["width"] == 32
+
+
+@pytest.mark.parametrize("key", sorted(width_cases.AEOS_REFUSED_DIMENSIONS))
+def test_euler_aeos_with_33_entries_is_refused_in_one_and_three_dimensions(checker, key):
+    refused = width_cases.AEOS_REFUSED_DIMENSIONS[key]
+    off = refused["mesh"]()
+    assert off.dim == refused["dim"] and plan_cases.widths_of(off).max() == 33 == refused["width"]
+    assert (off.n_owned + 63) // 64 == refused["n_slices"]
+    n_slices = str(refused["n_slices"])
+    out = subprocess.run([checker, "plan", "euler_aeos", str(off.dim), "33", n_slices, "1.0", "0", n_slices],
+                         capture_output=True, text=True)
+    assert out.returncode == 1 and out.stderr.strip() == refused["message"]
+    accepted = width_cases.CASES[refused["accepted"]]
+    assert accepted["equation"] == "euler_aeos" and 30 < accepted["width"] <= 32
 
 
 def test_wide_rows_never_take_the_recompute_kernel(checker):

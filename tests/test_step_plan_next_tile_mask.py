@@ -68,7 +68,7 @@ def test_the_table_reaches_both_values():
     values = {name: _expected({3: 1, 9: 2, 27: 3}[c["plan"]["diag_width"]], c["plan"], c["step6_launches"])
               for name, c in plan_cases.CASES.items()}
     on = sorted(k for k, v in values.items() if v)
-    assert on == ["euler_1d_1025", "euler_2d_box_4096", "euler_2d_box_4097", "euler_2d_step_1588", "scalar_2d_1148",
+    assert on == ["aeos_1d_1025", "aeos_2d_step_1588", "euler_1d_1025", "euler_2d_box_4096", "euler_2d_box_4097", "euler_2d_step_1588", "scalar_2d_1148",
                   "sw_2d_1148"], on
     assert len(values) - len(on) >= 10
 
