@@ -3,8 +3,8 @@
 // Reference: source/vtu_output.template.h:80-205 (schedule_output) and source/selected_components_extractor.h.
 // Configure time (everything that depends on the mesh and the manifolds only):
 //   k_output_levelsets     the manifold programs at the nodes, f [n_manifolds][n_nodes]: the shape of
-//                          k_initial_values_function_points -- the programs read by scalar loads, the operand stack a
-//                          [slot][lane] column of LDS, no thread leaves before the interpreter has run
+//                          k_initial_state_points<IvFunctionSource> -- the programs read by scalar loads, the operand
+//                          stack a [slot][lane] column of LDS, no thread leaves before the interpreter has run
 //   k_output_cell_flags    one lane per cell: output_cell_selected() (output_selection.hpp) on the vertex values
 //   k_output_count         set flags per block of kBlock items: wave ballots, one LDS add per wave
 //   k_output_scan          ONE block turns the block counts into exclusive offsets, kBlock counts per round with a

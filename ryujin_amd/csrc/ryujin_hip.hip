@@ -51,8 +51,6 @@
 #include "kernels_postprocessor.hpp"
 #include "kernels_quantities.hpp"
 #include "kernels_initial_values.hpp"
-#include "kernels_initial_values_bathymetry.hpp"
-#include "kernels_initial_values_library.hpp"
 #include "kernels_error_norms.hpp"
 #include "kernels_output.hpp"
 
@@ -519,17 +517,20 @@ struct ryujin_hip_ctx {
     if (!iv_configured)
       throw HipError(RYUJIN_ERR_ARG, "initial values: not configured (ryujin_hip_initial_values_configure)");
   }
+  /* f(source, program): the source of the configured state on this context (kernels_initial_values.hpp) and the
+   * program its evaluator interprets, IvNoProgram where it interprets none */
+  template <typename E, typename F>
+  void with_initial_state_source(F &&f);
   template <typename E>
-  void initial_values_points(const double *d_points, size_t n, double t, int stride, double *d_out,
-                             bool nodes = false);
-  /* the bathymetry of the configured state (kernels_initial_values_bathymetry.hpp), shallow water only */
+  void initial_values_points(const double *d_points, size_t n, double t, int stride, double *d_out);
+  /* the bathymetry of the configured state (k_initial_precomputed), shallow water only */
   void require_initial_precomputed() const
   {
     require_initial_values();
     if (params.equation != RYUJIN_EQ_SHALLOW_WATER)
       throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: this Description has no initial_precomputed values");
   }
-  void initial_precomputed_points(const double *d_points, size_t n, double *d_out, bool nodes);
+  void initial_precomputed_points(const double *d_points, size_t n, double *d_out);
 
   struct State {
     DeviceBuffer<double> U, prec;
@@ -1264,75 +1265,65 @@ void ryujin_hip_ctx::store_pij_for_debug()
 }
 
 /* initial_precomputations(affine_transform(point)) of the configured state, one thread per point, on the compute
- * stream; nodes: d_points are the node positions and d_out the context's bathymetry */
-void ryujin_hip_ctx::initial_precomputed_points(const double *d_points, size_t n, double *d_out, bool nodes)
+ * stream: into a caller's buffer, or at the node positions into the context's bathymetry */
+void ryujin_hip_ctx::initial_precomputed_points(const double *d_points, size_t n, double *d_out)
 {
   if (n == 0)
     return;
   const dim3 grid(grid_for(n, kInitialValuesBlock)), block(kInitialValuesBlock);
-  if (dim == 1) {
-    if (nodes)
-      hipLaunchKernelGGL(k_initial_precomputed_nodes<1>, grid, block, 0, stream, iv, (uint32_t)n, d_points, d_out);
-    else
-      hipLaunchKernelGGL(k_initial_precomputed_points<1>, grid, block, 0, stream, iv, (uint32_t)n, d_points, d_out);
-  } else {
-    if (nodes)
-      hipLaunchKernelGGL(k_initial_precomputed_nodes<2>, grid, block, 0, stream, iv, (uint32_t)n, d_points, d_out);
-    else
-      hipLaunchKernelGGL(k_initial_precomputed_points<2>, grid, block, 0, stream, iv, (uint32_t)n, d_points, d_out);
-  }
+  if (dim == 1)
+    hipLaunchKernelGGL(k_initial_precomputed<1>, grid, block, 0, stream, iv, (uint32_t)n, d_points, d_out);
+  else
+    hipLaunchKernelGGL(k_initial_precomputed<2>, grid, block, 0, stream, iv, (uint32_t)n, d_points, d_out);
   HIP_CHECK(hipGetLastError());
 }
 
-/* one thread per point (k_initial_values_points) on the compute stream; nodes: the points are the node positions and
- * d_out a state vector (the states of kernels_initial_values_bathymetry.hpp have a kernel of their own for it) */
-template <typename E>
-void ryujin_hip_ctx::initial_values_points(const double *d_points, size_t n, double t, int stride, double *d_out,
-                                           bool nodes)
+/* Which evaluator the configured state gets on a context of Description E: the one place that decides it, for the
+ * points and for the Dirichlet kernel alike. */
+template <typename E, typename F>
+void ryujin_hip_ctx::with_initial_state_source(F &&f)
 {
-  if (n == 0)
-    return;
+  constexpr int DIM = E::DIMENSION;
   if (iv_is_bathymetry_state(iv.state)) {
-    /* the states of initial_states_bathymetry_device.hpp: kernels of their own */
-    if constexpr (std::is_same<typename E::Params, ShallowWaterParams>::value) {
-      const dim3 grid(grid_for(n, kInitialValuesBlock)), block(kInitialValuesBlock);
-      if (nodes)
-        hipLaunchKernelGGL(k_initial_values_bathymetry_nodes<E::DIMENSION>, grid, block, 0, stream, iv, (uint32_t)n,
-                           d_points, t, stride, d_out);
-      else
-        hipLaunchKernelGGL(k_initial_values_bathymetry_points<E::DIMENSION>, grid, block, 0, stream, iv, (uint32_t)n,
-                           d_points, t, d_out);
-    } else {
+    /* the states of initial_states_bathymetry_device.hpp */
+    if constexpr (std::is_same<typename E::Params, ShallowWaterParams>::value)
+      f(IvBathymetrySource<DIM>{}, IvNoProgram{});
+    else
       throw HipError(RYUJIN_ERR_ARG, "initial values: the Description of this context has no such state");
-    }
   } else if (iv.state == kIvFunction) {
-    hipLaunchKernelGGL(k_initial_values_function_points<E>, dim3(grid_for(n, kInitialValuesBlock)),
-                       dim3(kInitialValuesBlock), 0, stream, iv, d_iv_function.ptr, (uint32_t)n, d_points, t, stride,
-                       d_out);
+    f(IvFunctionSource<E>{}, d_iv_function.ptr);
   } else if constexpr (is_scalar_v<E>) {
     throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: scalar conservation has the function state only");
-  } else if (iv_is_library_state(iv.state)) {
-    /* the states of initial_states_library_device.hpp: kernels of their own */
+  } else {
+    /* the states of initial_states_library_device.hpp, or the analytic ones */
+    const bool library = iv_is_library_state(iv.state);
     if constexpr (std::is_same<typename E::Params, EulerAeosParams>::value) {
       if (aeosparams.eos == RYUJIN_EOS_FUNCTION) {
-        hipLaunchKernelGGL(k_initial_values_library_eos_function_points<E::DIMENSION>,
-                           dim3(grid_for(n, kInitialValuesBlock)), dim3(kInitialValuesBlock), 0, stream, iv,
-                           d_eos_function.ptr, (uint32_t)n, d_points, t, stride, d_out);
-        HIP_CHECK(hipGetLastError());
+        /* through the sie program of the function equation of state */
+        if (library)
+          f(IvLibraryEosFunctionSource<DIM>{}, d_eos_function.ptr);
+        else
+          f(IvEosFunctionSource<DIM>{}, d_eos_function.ptr);
         return;
       }
     }
-    hipLaunchKernelGGL(k_initial_values_library_points<E>, dim3(grid_for(n, kInitialValuesBlock)),
-                       dim3(kInitialValuesBlock), 0, stream, iv, (uint32_t)n, d_points, t, stride, d_out);
-  } else if (std::is_same<typename E::Params, EulerAeosParams>::value && aeosparams.eos == RYUJIN_EOS_FUNCTION) {
-    /* the analytic state through the sie program of the function equation of state */
-    hipLaunchKernelGGL(k_initial_values_eos_function_points<E::DIMENSION>, dim3(grid_for(n, kInitialValuesBlock)),
-                       dim3(kInitialValuesBlock), 0, stream, iv, d_eos_function.ptr, (uint32_t)n, d_points, t, stride,
-                       d_out);
-  } else {
-    hipLaunchKernelGGL(k_initial_values_points<E>, dim3(grid_for(n, kInitialValuesBlock)), dim3(kInitialValuesBlock),
-                       0, stream, iv, (uint32_t)n, d_points, t, stride, d_out);
+    if (library)
+      f(IvLibrarySource<E>{}, IvNoProgram{});
+    else
+      f(IvAnalyticSource<E>{}, IvNoProgram{});
   }
+}
+
+/* one thread per point (k_initial_state_points) on the compute stream */
+template <typename E>
+void ryujin_hip_ctx::initial_values_points(const double *d_points, size_t n, double t, int stride, double *d_out)
+{
+  if (n == 0)
+    return;
+  with_initial_state_source<E>([&](auto source, auto program) {
+    hipLaunchKernelGGL(k_initial_state_points<decltype(source)>, dim3(grid_for(n, kInitialValuesBlock)),
+                       dim3(kInitialValuesBlock), 0, stream, iv, program, (uint32_t)n, d_points, t, stride, d_out);
+  });
   HIP_CHECK(hipGetLastError());
 }
 
@@ -1348,61 +1339,14 @@ void ryujin_hip_ctx::prepare_state_vector(int h, const double *dirichlet, IvStag
      * every kernel of the previous stage that read the buffer (compute stream order; the export part of the previous
      * pre-pass may have applied boundary conditions on comm_stream) and behind the step-4 kernel of the first stage,
      * which left tau_rk. Nothing on the host waits for tau. */
-    if (iv_is_bathymetry_state(iv.state)) {
-      if constexpr (std::is_same<typename E::Params, ShallowWaterParams>::value) {
-        join_export();
-        hipLaunchKernelGGL(k_initial_values_bathymetry_dirichlet<E::DIMENSION>,
-                           dim3(grid_for(bdry.n_bdry, kInitialValuesBlock)), dim3(kInitialValuesBlock), 0, stream, iv,
-                           bdry.n_bdry, d_iv_b_positions.ptr, d_b_id.ptr, iv_stage.t, iv_stage.c, d_scalars.ptr,
-                           d_dirichlet.ptr);
-        HIP_CHECK(hipGetLastError());
-        have_dirichlet = true;
-      } else {
-        throw HipError(RYUJIN_ERR_ARG, "initial values: the Description of this context has no such state");
-      }
-    } else if (iv.state == kIvFunction) {
+    with_initial_state_source<E>([&](auto source, auto program) {
       join_export();
-      hipLaunchKernelGGL(k_initial_values_function_dirichlet<E>, dim3(grid_for(bdry.n_bdry, kInitialValuesBlock)),
-                         dim3(kInitialValuesBlock), 0, stream, iv, d_iv_function.ptr, bdry.n_bdry, d_iv_b_positions.ptr,
+      hipLaunchKernelGGL(k_initial_state_dirichlet<decltype(source)>, dim3(grid_for(bdry.n_bdry, kInitialValuesBlock)),
+                         dim3(kInitialValuesBlock), 0, stream, iv, program, bdry.n_bdry, d_iv_b_positions.ptr,
                          d_b_id.ptr, iv_stage.t, iv_stage.c, d_scalars.ptr, d_dirichlet.ptr);
-      HIP_CHECK(hipGetLastError());
-      have_dirichlet = true;
-    } else if constexpr (is_scalar_v<E>) {
-      throw HipError(RYUJIN_ERR_UNSUPPORTED, "initial values: scalar conservation has the function state only");
-    } else if (iv_is_library_state(iv.state)) {
-      join_export();
-      bool launched = false;
-      if constexpr (std::is_same<typename E::Params, EulerAeosParams>::value) {
-        if (aeosparams.eos == RYUJIN_EOS_FUNCTION) {
-          hipLaunchKernelGGL(k_initial_values_library_eos_function_dirichlet<E::DIMENSION>,
-                             dim3(grid_for(bdry.n_bdry, kInitialValuesBlock)), dim3(kInitialValuesBlock), 0, stream,
-                             iv, d_eos_function.ptr, bdry.n_bdry, d_iv_b_positions.ptr, d_b_id.ptr, iv_stage.t,
-                             iv_stage.c, d_scalars.ptr, d_dirichlet.ptr);
-          launched = true;
-        }
-      }
-      if (!launched)
-        hipLaunchKernelGGL(k_initial_values_library_dirichlet<E>, dim3(grid_for(bdry.n_bdry, kInitialValuesBlock)),
-                           dim3(kInitialValuesBlock), 0, stream, iv, bdry.n_bdry, d_iv_b_positions.ptr, d_b_id.ptr,
-                           iv_stage.t, iv_stage.c, d_scalars.ptr, d_dirichlet.ptr);
-      HIP_CHECK(hipGetLastError());
-      have_dirichlet = true;
-    } else if (std::is_same<typename E::Params, EulerAeosParams>::value && aeosparams.eos == RYUJIN_EOS_FUNCTION) {
-      join_export();
-      hipLaunchKernelGGL(k_initial_values_eos_function_dirichlet<E::DIMENSION>,
-                         dim3(grid_for(bdry.n_bdry, kInitialValuesBlock)), dim3(kInitialValuesBlock), 0, stream, iv,
-                         d_eos_function.ptr, bdry.n_bdry, d_iv_b_positions.ptr, d_b_id.ptr, iv_stage.t, iv_stage.c,
-                         d_scalars.ptr, d_dirichlet.ptr);
-      HIP_CHECK(hipGetLastError());
-      have_dirichlet = true;
-    } else {
-      join_export();
-      hipLaunchKernelGGL(k_initial_values_dirichlet<E>, dim3(grid_for(bdry.n_bdry, kInitialValuesBlock)),
-                         dim3(kInitialValuesBlock), 0, stream, iv, bdry.n_bdry, d_iv_b_positions.ptr, d_b_id.ptr,
-                         iv_stage.t, iv_stage.c, d_scalars.ptr, d_dirichlet.ptr);
-      HIP_CHECK(hipGetLastError());
-      have_dirichlet = true;
-    }
+    });
+    HIP_CHECK(hipGetLastError());
+    have_dirichlet = true;
   } else if (dirichlet && bdry.n_bdry) {
     /* permute into the grouped order, then upload */
     if (deferred) {
@@ -4166,6 +4110,27 @@ namespace
     return dispatch_equation(ctx->params.equation, ctx->dim, [&](auto tag) { return f(tag); });
   }
 
+  /* n points of the caller through a points kernel that writes `width` doubles per point: upload into d_iv_points,
+   * launch() from there into d_iv_values, download, synchronise. On the compute stream, in order with whatever it
+   * holds; may be called from a Dirichlet callback inside a Runge-Kutta step (nothing of the exchange bookkeeping is
+   * touched). */
+  template <typename Launch>
+  void initial_values_round_trip(ryujin_hip_ctx *ctx, const double *points, const size_t n, const size_t width,
+                                 double *out, Launch &&launch)
+  {
+    const size_t dim = (size_t)ctx->dim;
+    if (ctx->d_iv_points.n < n * dim)
+      ctx->d_iv_points.alloc(n * dim, false);
+    if (ctx->d_iv_values.n < n * width)
+      ctx->d_iv_values.alloc(n * width, false);
+    HIP_CHECK(hipMemcpyAsync(ctx->d_iv_points.ptr, points, n * dim * sizeof(double), hipMemcpyHostToDevice,
+                             ctx->stream));
+    launch();
+    HIP_CHECK(hipMemcpyAsync(out, ctx->d_iv_values.ptr, n * width * sizeof(double), hipMemcpyDeviceToHost,
+                             ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  }
+
   /* InitialValues::parse_parameters_callback (initial_values.template.h:154-196): `position`, and the rolls of
    * affine_transform (:78-106) that take the normalised `direction` onto the x-axis */
   void set_initial_values_frame(InitialValuesParams &P, const int dim, const double *direction,
@@ -4688,22 +4653,13 @@ int ryujin_hip_initial_values_evaluate(ryujin_hip_ctx *ctx, const double *points
       return RYUJIN_OK;
     if (!points || !out || n > 0xffffffffull)
       throw HipError(RYUJIN_ERR_ARG, "initial values: bad argument");
-    const size_t dim = (size_t)ctx->dim, K = (size_t)ctx->K;
-    if (ctx->d_iv_points.n < n * dim)
-      ctx->d_iv_points.alloc(n * dim, false);
-    if (ctx->d_iv_values.n < n * K)
-      ctx->d_iv_values.alloc(n * K, false);
-    /* on the compute stream, in order with whatever it holds; may be called from a Dirichlet callback inside a
-     * Runge-Kutta step (nothing of the exchange bookkeeping is touched) */
-    HIP_CHECK(hipMemcpyAsync(ctx->d_iv_points.ptr, points, n * dim * sizeof(double), hipMemcpyHostToDevice,
-                             ctx->stream));
-    dispatch_initial_values(ctx, [&](auto tag) {
-      ctx->template initial_values_points<typename decltype(tag)::type>(ctx->d_iv_points.ptr, n, t, (int)K,
-                                                                        ctx->d_iv_values.ptr);
-      return RYUJIN_OK;
+    initial_values_round_trip(ctx, points, n, (size_t)ctx->K, out, [&]() {
+      dispatch_initial_values(ctx, [&](auto tag) {
+        ctx->template initial_values_points<typename decltype(tag)::type>(ctx->d_iv_points.ptr, n, t, ctx->K,
+                                                                          ctx->d_iv_values.ptr);
+        return RYUJIN_OK;
+      });
     });
-    HIP_CHECK(hipMemcpyAsync(out, ctx->d_iv_values.ptr, n * K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return RYUJIN_OK;
   });
 }
@@ -4717,7 +4673,7 @@ int ryujin_hip_initial_values_interpolate(ryujin_hip_ctx *ctx, int handle, doubl
     s.precomputed = false;
     return dispatch_initial_values(ctx, [&](auto tag) {
       ctx->template initial_values_points<typename decltype(tag)::type>(ctx->d_iv_positions.ptr, ctx->L.n_relevant, t,
-                                                                        ctx->KP, s.U.ptr, true);
+                                                                        ctx->KP, s.U.ptr);
       return RYUJIN_OK;
     });
   });
@@ -4728,7 +4684,7 @@ int ryujin_hip_initial_values_interpolate_initial_precomputed(ryujin_hip_ctx *ct
   return guarded_ctx(ctx, [&]() {
     ctx->require_initial_precomputed();
     /* on the compute stream, behind every kernel that reads the bathymetry (step 4, the output extraction) */
-    ctx->initial_precomputed_points(ctx->d_iv_positions.ptr, ctx->L.n_relevant, ctx->d_Z.ptr, true);
+    ctx->initial_precomputed_points(ctx->d_iv_positions.ptr, ctx->L.n_relevant, ctx->d_Z.ptr);
     return RYUJIN_OK;
   });
 }
@@ -4742,16 +4698,9 @@ int ryujin_hip_initial_values_evaluate_initial_precomputed(ryujin_hip_ctx *ctx, 
       return RYUJIN_OK;
     if (!points || !out || n > 0xffffffffull)
       throw HipError(RYUJIN_ERR_ARG, "initial values: bad argument");
-    const size_t dim = (size_t)ctx->dim;
-    if (ctx->d_iv_points.n < n * dim)
-      ctx->d_iv_points.alloc(n * dim, false);
-    if (ctx->d_iv_values.n < n)
-      ctx->d_iv_values.alloc(n, false);
-    HIP_CHECK(hipMemcpyAsync(ctx->d_iv_points.ptr, points, n * dim * sizeof(double), hipMemcpyHostToDevice,
-                             ctx->stream));
-    ctx->initial_precomputed_points(ctx->d_iv_points.ptr, n, ctx->d_iv_values.ptr, false);
-    HIP_CHECK(hipMemcpyAsync(out, ctx->d_iv_values.ptr, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    initial_values_round_trip(ctx, points, n, 1, out, [&]() {
+      ctx->initial_precomputed_points(ctx->d_iv_points.ptr, n, ctx->d_iv_values.ptr);
+    });
     return RYUJIN_OK;
   });
 }

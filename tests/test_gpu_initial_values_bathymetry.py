@@ -1,5 +1,5 @@
 """The shallow-water states that bring their own bathymetry, and the bed of every shallow-water state, on the device
-(capi.IV_BATHYMETRY_STATES; ryujin_amd/csrc/initial_states_bathymetry_device.hpp, kernels_initial_values_bathymetry.hpp).
+(capi.IV_BATHYMETRY_STATES; ryujin_amd/csrc/initial_states_bathymetry_device.hpp, kernels_initial_values.hpp).
 
 A  state and bed against ryujin_amd.initial_states, tolerances DERIVED in tests/helpers_initial_values_bathymetry.py; the
    piecewise-polynomial beds bit for bit

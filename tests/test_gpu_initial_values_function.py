@@ -1,5 +1,5 @@
 """The expression-defined "function" state on the device (ryujin_hip_initial_values_configure_function;
-ryujin_amd/csrc/expression.hpp, initial_states_device.hpp::initial_state_function, k_initial_values_function_*).
+ryujin_amd/csrc/expression.hpp, initial_states_device.hpp::initial_state_function, kernels_initial_values.hpp::IvFunctionSource).
 
 1  the device interpreter against the host interpreter (ryujin_hip_expression_evaluate) composed in numpy with the
    affine transform and from_primitive_state: every Description, arithmetic bit for bit, library functions within

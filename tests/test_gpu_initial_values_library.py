@@ -1,5 +1,5 @@
 """The Riemann-data, shock-front, ramp-up and Noh states on the device (capi.IV_LIBRARY_STATES;
-ryujin_amd/csrc/initial_states_library_device.hpp, kernels_initial_values_library.hpp).
+ryujin_amd/csrc/initial_states_library_device.hpp, kernels_initial_values.hpp).
 
 A  the device function against ryujin_amd.initial_states, tolerances DERIVED in tests/helpers_initial_values_library.py
 B  three consumers, one function: evaluate at the nodes, interpolate and the Dirichlet kernel give the same bits
