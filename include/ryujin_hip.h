@@ -212,7 +212,9 @@ typedef struct ryujin_hip_params {
    * that gain from it (steps 2 and 4) take c_ij and the column offset of such a slice from the table with scalar loads
    * instead of streaming 64 copies of them (m_ij is part of the key but read by no kernel). 0: on where it pays (default); < 0: off -- no table is built and
    * every sweep streams the explicit arrays, as for an unstructured mesh. Results are identical: the same bits reach
-   * the same operations. */
+   * the same operations. Euler's step 2 in 1-D / 2-D also reads |c_ij| and 1 / |c_ij| of such a slice from a second
+   * table, computed on the host by the operations the kernel would use; 1: the classes without that table (to
+   * measure it alone). Values above 1 are refused. */
   int debug_stencil_classes;
   /* The tile mask from step 6 to step 7: the first of two limiter passes knows, per (64-row slice, column) tile, whether
    * some pair of the tile is limited; the second-pass l'_ij of every other tile are exact zeros. Up to two dimensions

@@ -33,6 +33,10 @@ namespace ryujin_hip
 
 #define RYUJIN_DEV __device__ __forceinline__
 
+#ifndef RYUJIN_COMPACT_RECORD
+#define RYUJIN_COMPACT_RECORD 1 /* 0 (A/B, the bit-identity reference): Euler 1-D / 2-D store the whole 64-byte node record */
+#endif
+
 
   /*
    * ryujin::pow (source/simd.template.h:196-272) on the device.
@@ -229,8 +233,23 @@ namespace ryujin_hip
     /* f(U): hyperbolic_system.h:1164-1181 */
     static RYUJIN_DEV void flux(const EulerParams &P, const double (&U)[K], double (&f)[K][DIM])
     {
-      const double rho_inverse = 1. / U[0];
-      const double p = (P.gamma - 1.) * internal_energy(U);
+      flux(U, state_values(P, U), f);
+    }
+
+    /* 1 / rho and p of a state, by the expressions flux() and node_record() have always used: what the sweeps of a
+     * Description with kRecordNeedsState (below) compute ONCE per neighbour for the indicator and the Riemann solve */
+    struct StateValues {
+      double rho_inverse, p;
+    };
+    static RYUJIN_DEV StateValues state_values(const EulerParams &P, const double (&U)[K])
+    {
+      return {1. / U[0], (P.gamma - 1.) * internal_energy(U)};
+    }
+
+    static RYUJIN_DEV void flux(const double (&U)[K], const StateValues &values, double (&f)[K][DIM])
+    {
+      const double rho_inverse = values.rho_inverse;
+      const double p = values.p;
       const double E = U[1 + DIM];
 #pragma unroll
       for (int d = 0; d < DIM; ++d)
@@ -310,10 +329,17 @@ namespace ryujin_hip
       RYUJIN_DEV void accumulate(const EulerParams &P, const double (&U_j)[K], const double2 prec_j,
                                  const double (&c_ij)[DIM])
       {
+        accumulate(U_j, prec_j, state_values(P, U_j), c_ij);
+      }
+
+      /* ... with 1 / rho_j and p_j handed in (state_values(): the same bits) */
+      RYUJIN_DEV void accumulate(const double (&U_j)[K], const double2 prec_j, const StateValues &s_j,
+                                 const double (&c_ij)[DIM])
+      {
         const double eta_j = prec_j.y;
-        const double rho_j_inverse = 1. / U_j[0];
+        const double rho_j_inverse = s_j.rho_inverse;
         double f_j[K][DIM];
-        flux(P, U_j, f_j);
+        flux(U_j, s_j, f_j);
         double m_j_c = U_j[1] * c_ij[0];
 #pragma unroll
         for (int d = 1; d < DIM; ++d)
@@ -591,7 +617,12 @@ namespace ryujin_hip
      * (tests/test_gpu_device_functions.py) and in every sweep comparison. With Newton iterations of the
      * Riemann solver switched on (non-default) the reference path (riemann_compute) is used on the same data.
      *
-     * record = (rho, p, a, pw, a / pw, 1 / p, v[DIM]) padded to an even number of doubles in 1-D and 2-D (64 B).
+     * record = (rho, p, a, pw, a / pw, 1 / p, v[DIM]) padded to an even number of doubles in 1-D and 2-D: what a
+     * kernel holds in registers. STORED of it are only (a, pw, a / pw, 1 / p), 32 B per node (kRecordNeedsState):
+     * every kernel that reads a record has the node's state anyway, and rho, p = (gamma - 1) rho e and
+     * v = m (1 / rho) are then the very expressions flux() evaluates for the indicator (state_values(),
+     * complete_record()) -- the same operands in the same operations, the same bits, half the record's stores in the
+     * last sweep of a step and half its gathers in step 2. RYUJIN_COMPACT_RECORD=0 stores all 64 B as before.
      * In 3-D the record is (rho, p, a, pw, a / pw, 1 / p, m[DIM], E, eta, 1 / rho), 96 B: the Riemann data of the
      * node AND what the indicator needs of it (the state, the Harten entropy, 1 / rho), so that step 2 gathers ONE
      * record per neighbour instead of the state (48 B), the precomputed values (16 B) and a Riemann record (80 B)
@@ -603,6 +634,25 @@ namespace ryujin_hip
     static constexpr int kRecRho = 0, kRecP = 1, kRecA = 2, kRecPw = 3, kRecApw = 4, kRecPinv = 5, kRecM = 6,
                          kRecE = 6 + DIM, kRecEta = 7 + DIM, kRecRinv = 8 + DIM;
     static constexpr int RS = ((kRecordHoldsState ? 9 : 6) + DIM + 1) / 2 * 2;
+    /* the doubles [kRecordFirst, kRecordFirst + kRecordStored) of a record are what memory holds of it */
+    static constexpr bool kRecordNeedsState = RYUJIN_COMPACT_RECORD != 0 && !kRecordHoldsState;
+    static constexpr int kRecordFirst = kRecordNeedsState ? kRecA : 0;
+    static constexpr int kRecordStored = kRecordNeedsState ? 4 : RS;
+    static_assert(!kRecordNeedsState || (kRecPinv + 1 == kRecordFirst + kRecordStored && kRecordFirst % 2 == 0),
+                  "the stored part of the record: (a, pw, a / pw, 1 / p) as two aligned pairs");
+
+    /* kRecordNeedsState: the entries a loaded record lacks, from the node's state -- node_record()'s expressions */
+    static RYUJIN_DEV void complete_record(const double (&U)[K], const StateValues &s, double (&rec)[RS])
+    {
+      rec[kRecRho] = U[0];
+      rec[kRecP] = s.p;
+#pragma unroll
+      for (int d = 0; d < DIM; ++d)
+        rec[kRecM + d] = U[1 + d] * s.rho_inverse;
+#pragma unroll
+      for (int d = 6 + DIM; d < RS; ++d)
+        rec[d] = 0.;
+    }
 
     static RYUJIN_DEV double record_velocity(const double (&rec)[RS], const int d)
     {
@@ -712,16 +762,35 @@ namespace ryujin_hip
     static RYUJIN_DEV double dij_from_records(const EulerParams &P, const double (&ri)[RS],
                                               const double (&rj)[RS], const double (&c)[DIM])
     {
+      double norm, inverse_norm;
+      cij_norm(c, norm, inverse_norm);
+      return dij_from_records<GENERAL>(P, ri, rj, c, norm, inverse_norm);
+    }
+
+    /* |c_ij| and 1 / |c_ij|. Mesh constants: a uniform slice reads them from the table next to its stencil class
+     * (SellLayout::class_norms, host_layout.hpp, which evaluates these very operations on the host) */
+    static RYUJIN_DEV void cij_norm(const double (&c)[DIM], double &norm, double &inverse_norm)
+    {
       double norm2 = c[0] * c[0];
+#pragma unroll
+      for (int d = 1; d < DIM; ++d)
+        norm2 += c[d] * c[d];
+      norm = sqrt(norm2);
+      inverse_norm = 1. / norm;
+    }
+
+    /* ... with norm = |c| and inverse_norm = 1 / |c| handed in (cij_norm(), or the table's copy of it) */
+    template <bool GENERAL = true>
+    static RYUJIN_DEV double dij_from_records(const EulerParams &P, const double (&ri)[RS],
+                                              const double (&rj)[RS], const double (&c)[DIM], const double norm,
+                                              const double inverse_norm)
+    {
       double vc_i = record_velocity(ri, 0) * c[0], vc_j = record_velocity(rj, 0) * c[0];
 #pragma unroll
       for (int d = 1; d < DIM; ++d) {
-        norm2 += c[d] * c[d];
         vc_i += record_velocity(ri, d) * c[d];
         vc_j += record_velocity(rj, d) * c[d];
       }
-      const double norm = sqrt(norm2);
-      const double inverse_norm = 1. / norm;
       const double u_i = vc_i * inverse_norm, u_j = vc_j * inverse_norm;
 
       if constexpr (GENERAL) {

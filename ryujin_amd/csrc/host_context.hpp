@@ -36,18 +36,26 @@ namespace ryujin_hip
    * knows them on the host; ryujin_hip.hip ties every field to the Descriptions of the device headers. */
   struct SystemShape {
     int K, KP, NB, NPREC, RS;
+    int RS_stored; /* the doubles of the record that memory holds (the stride of the per-state buffer): RS, or 4 of
+                    * Euler's 8 in 1-D and 2-D (Euler<DIM>::kRecordStored, euler_device.hpp) */
   };
+
+#ifndef RYUJIN_COMPACT_RECORD
+#define RYUJIN_COMPACT_RECORD 1 /* as euler_device.hpp; ryujin_hip.hip ties the two together (shape_matches) */
+#endif
 
   constexpr SystemShape system_shape(const int equation, const int dim)
   {
-    SystemShape s{dim + 2, 0, 3, 2, ((dim == 3 ? 9 : 6) + dim + 1) / 2 * 2}; /* Euler: the record holds the state in 3-D */
+    SystemShape s{dim + 2, 0, 3, 2, ((dim == 3 ? 9 : 6) + dim + 1) / 2 * 2, 0}; /* Euler: the record holds the state in 3-D */
+    const bool stores_whole_record = RYUJIN_COMPACT_RECORD == 0 || dim == 3;
     if (equation == RYUJIN_EQ_EULER_AEOS)
-      s = SystemShape{dim + 2, 0, 4, 4, (6 + dim + 1) / 2 * 2};
+      s = SystemShape{dim + 2, 0, 4, 4, (6 + dim + 1) / 2 * 2, 0};
     else if (equation == RYUJIN_EQ_SHALLOW_WATER)
-      s = SystemShape{dim + 1, 0, 5, 2, (2 + dim + 1) / 2 * 2};
+      s = SystemShape{dim + 1, 0, 5, 2, (2 + dim + 1) / 2 * 2, 0};
     else if (equation == RYUJIN_EQ_SCALAR_CONSERVATION)
-      s = SystemShape{1, 0, 2, 2 * dim, 0};
+      s = SystemShape{1, 0, 2, 2 * dim, 0, 0};
     s.KP = (s.K + 1) / 2 * 2;
+    s.RS_stored = (equation == RYUJIN_EQ_EULER && !stores_whole_record) ? 4 : s.RS;
     return s;
   }
 
@@ -85,6 +93,8 @@ namespace ryujin_hip
       throw HipError(RYUJIN_ERR_ARG, "dim must be 1, 2 or 3");
     if (p.limiter_iterations < 0 || p.limiter_iterations > 2)
       throw HipError(RYUJIN_ERR_ARG, "The number of limiter iterations must be between [0,2]");
+    if (p.debug_stencil_classes > 1)
+      throw HipError(RYUJIN_ERR_ARG, "debug_stencil_classes must be < 0 (off), 0 or 1 (classes without the table of norms)");
     if (p.debug_pij_storage > 2)
       throw HipError(RYUJIN_ERR_ARG, "debug_pij_storage must be < 0, 0, 1 or 2 (per-tile P_ij in 3-D was retired)");
     if (p.equation == RYUJIN_EQ_SCALAR_CONSERVATION && p.sc_flux == RYUJIN_FLUX_FUNCTION &&

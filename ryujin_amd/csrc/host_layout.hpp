@@ -19,6 +19,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <exception>
@@ -159,6 +160,11 @@ namespace ryujin_hip
     std::vector<uint32_t> slice_class; /* [n_slices] first entry of the slice's class in class_table, or kStencilClassNone */
     std::vector<uint64_t> class_table; /* [n_class_entries * stencil_class_entry_words(dim)] */
     std::vector<uint32_t> class_first; /* [n_classes + 1] first entry of every class (its width: the difference) */
+    /* [n_class_entries * 2] parallel to class_table: |c_ij| = sqrt(c_0 c_0 + c_1 c_1 [+ c_2 c_2]) and 1 / |c_ij| of
+     * every entry, by the operations of Euler<DIM>::cij_norm() (euler_device.hpp) in their order -- multiplication,
+     * addition, square root and division are correctly rounded on both sides, so step 2 reads of a uniform slice what
+     * it would compute (this header is compiled without contraction into fused multiply-adds) */
+    std::vector<double> class_norms;
     uint64_t n_uniform_slices = 0, n_uniform_tiles = 0; /* ... and the 64-entry columns they hold */
     std::vector<TileDesc> tiles;     /* [slice_off[n_slices]] */
     std::vector<uint64_t> chain_loads; /* [slice_off[n_slices]] the lanes of a chained tile that fetch their node themselves */
@@ -457,6 +463,7 @@ namespace ryujin_hip
       slice_class.clear();
       class_table.clear();
       class_first.clear();
+      class_norms.clear();
       n_uniform_slices = n_uniform_tiles = 0;
       auto bits = [](const double x) {
         uint64_t b;
@@ -521,6 +528,17 @@ namespace ryujin_hip
       }
       if (n_uniform_slices != 0)
         slice_class = std::move(of_slice);
+      class_norms.reserve(class_table.size() / W * 2);
+      for (size_t e = 0; e < class_table.size() / W; ++e) {
+        double c[3] = {0., 0., 0.};
+        std::memcpy(c, class_table.data() + e * W, sizeof(double) * (size_t)dim);
+        double norm2 = c[0] * c[0];
+        for (int d = 1; d < dim; ++d)
+          norm2 += c[d] * c[d];
+        const double norm = std::sqrt(norm2);
+        class_norms.push_back(norm);
+        class_norms.push_back(1. / norm);
+      }
     }
 
     uint32_t n_stencil_classes() const { return class_first.empty() ? 0u : (uint32_t)class_first.size() - 1u; }

@@ -71,6 +71,7 @@ namespace ryujin_hip
     const uint64_t *chain_loads; /* [slice_off[n_slices]] with the tile map: the lanes of a chained tile that fetch their node (TileDesc::chain) */
     const uint32_t *slice_class; /* [n_slices] first entry of the slice's stencil class in class_table or kStencilClassNone; NULL: no uniform slice */
     const StencilClassEntry *class_table; /* the stencil classes (host_layout.hpp), or NULL */
+    const double *class_norms; /* [entries][2] |c_ij| and 1 / |c_ij| of the class entries (SellLayout::class_norms), or NULL */
     uint32_t tail_queue_columns; /* min(63, widest row - 1): columns of the dynamic-LDS queue of undecided pairs (k_pij_lij) */
     /* > 1: the four waves of a block take slices that are band_stride apart (one lattice row / plane of a structured
      * patch) instead of four consecutive ones: row_context() */
@@ -425,6 +426,16 @@ namespace ryujin_hip
       c[1] = uniform_double(v.z, v.w);
   }
 
+  /* |c_ij| and 1 / |c_ij| of entry `e`: one scalar 16-byte load (M.class_norms != NULL) */
+  RYUJIN_DEV void class_norm(const DeviceMesh &M, const uint32_t e, double &norm, double &inverse_norm)
+  {
+    typedef int v4i __attribute__((ext_vector_type(4)));
+    typedef const v4i __attribute__((address_space(4))) *const_ptr;
+    const v4i v = *(const_ptr)(uintptr_t)(M.class_norms + 2 * (size_t)e);
+    norm = uniform_double(v.x, v.y);
+    inverse_norm = uniform_double(v.z, v.w);
+  }
+
   /* j - i of entry `e` */
   RYUJIN_DEV int32_t class_delta(const DeviceMesh &M, const uint32_t e)
   {
@@ -731,6 +742,48 @@ namespace ryujin_hip
     apply_bc_group<E>(P, B, g, b_i[B.grp_start[g]], U);
   }
 
+  /* A node record (E::node_record / E::riemann_record) as 16-byte loads and stores. Memory holds the entries
+   * [kRecordFirst, kRecordFirst + kRecordStored) of it: all of them, or with E::kRecordNeedsState (Euler in 1-D and
+   * 2-D) the four a kernel cannot form from the node's state in one multiplication -- E::complete_record() fills in
+   * the others behind load_record() */
+  template <typename E>
+  RYUJIN_DEV void load_record(const double *__restrict__ rec, const uint32_t i, double (&r)[E::RS])
+  {
+    const double2 *b = reinterpret_cast<const double2 *>(rec + (size_t)i * E::kRecordStored);
+#pragma unroll
+    for (int g = 0; g < E::kRecordStored / 2; ++g) {
+      const double2 t = b[g];
+      r[E::kRecordFirst + 2 * g] = t.x;
+      r[E::kRecordFirst + 2 * g + 1] = t.y;
+    }
+  }
+
+  /* the record of node i as node_record() made it: with E::kRecordNeedsState from the stored part and the state U_i */
+  template <typename E>
+  RYUJIN_DEV void load_whole_record(const typename E::Params &P, const double *__restrict__ rec,
+                                    const double *__restrict__ U, const uint32_t i, double (&r)[E::RS])
+  {
+    load_record<E>(rec, i, r);
+    if constexpr (E::kRecordNeedsState) {
+      double U_i[E::K];
+      load_state<E::K>(U, i, U_i);
+      E::complete_record(U_i, E::state_values(P, U_i), r);
+    }
+  }
+
+  template <typename E>
+  RYUJIN_DEV void store_record(double *__restrict__ rec, const uint32_t i, const double (&r)[E::RS])
+  {
+    double2 *out = reinterpret_cast<double2 *>(rec + (size_t)i * E::kRecordStored);
+#pragma unroll
+    for (int g = 0; g < E::kRecordStored / 2; ++g) {
+      double2 t;
+      t.x = r[E::kRecordFirst + 2 * g];
+      t.y = r[E::kRecordFirst + 2 * g + 1];
+      out[g] = t;
+    }
+  }
+
   /* the same for a state vector whose precomputed values and Riemann records were left behind by the last sweep of
    * the step that produced it (FusedPrecompute, kernels_limiter.hpp): those of the boundary rows are redone from
    * the state the boundary conditions leave */
@@ -753,14 +806,7 @@ namespace ryujin_hip
     const double2 prec_i = E::precompute(P, U_i);
     reinterpret_cast<double2 *>(prec)[i] = prec_i;
     E::node_record(P, U_i, prec_i, r);
-    double2 *out = reinterpret_cast<double2 *>(rec + (size_t)i * RS);
-#pragma unroll
-    for (int q = 0; q < RS / 2; ++q) {
-      double2 t;
-      t.x = r[2 * q];
-      t.y = r[2 * q + 1];
-      out[q] = t;
-    }
+    store_record<E>(rec, i, r);
   }
 
   /* precomputation_loop (source/euler/hyperbolic_system.h:702-737, shallow_water/hyperbolic_system.h:676-716):
@@ -783,14 +829,7 @@ namespace ryujin_hip
     const double2 prec_i = E::precompute(P, U_i);
     reinterpret_cast<double2 *>(prec)[i] = prec_i;
     E::node_record(P, U_i, prec_i, r);
-    double2 *out = reinterpret_cast<double2 *>(rec + (size_t)i * RS);
-#pragma unroll
-    for (int g = 0; g < RS / 2; ++g) {
-      double2 t;
-      t.x = r[2 * g];
-      t.y = r[2 * g + 1];
-      out[g] = t;
-    }
+    store_record<E>(rec, i, r);
   }
 
   /* the same pair for the ghost rows [first, last): computed locally from the exchanged ghost states (both
@@ -812,22 +851,7 @@ namespace ryujin_hip
     const double2 prec_i = E::precompute(P, U_i);
     reinterpret_cast<double2 *>(prec)[i] = prec_i;
     E::node_record(P, U_i, prec_i, r);
-#pragma unroll
-    for (int g = 0; g < RS; ++g)
-      rec[(size_t)i * RS + g] = r[g];
-  }
-
-  /* a node record (E::node_record / E::riemann_record) as 16-byte loads */
-  template <int RS>
-  RYUJIN_DEV void load_record(const double *__restrict__ rec, const uint32_t i, double (&r)[RS])
-  {
-    const double2 *b = reinterpret_cast<const double2 *>(rec + (size_t)i * RS);
-#pragma unroll
-    for (int g = 0; g < RS / 2; ++g) {
-      const double2 t = b[g];
-      r[2 * g] = t.x;
-      r[2 * g + 1] = t.y;
-    }
+    store_record<E>(rec, i, r);
   }
 
   /* ------------------------------------------------------------------ step 2 */
@@ -937,7 +961,7 @@ namespace ryujin_hip
   template <typename E, bool GENERAL>
   __global__ void __launch_bounds__(kBlock, RYUJIN_OCC_DIJ)
   k_dij_records(const typename E::Params P, const DeviceMesh M, const uint32_t *__restrict__ lower_mask,
-                const double *__restrict__ rec, double *__restrict__ dij)
+                const double *__restrict__ rec, const double *__restrict__ U, double *__restrict__ dij)
   {
     constexpr int DIM = E::DIMENSION;
     constexpr int RS = E::RS;
@@ -952,15 +976,7 @@ namespace ryujin_hip
         row_active ? (~lower_mask[r.row] & (r.len >= 32 ? 0xFFFFFFFFu : ((1u << r.len) - 1u)) & ~1u) : 0u;
 
     double rec_i[RS];
-    {
-      const double2 *b = reinterpret_cast<const double2 *>(rec + (size_t)i * RS);
-#pragma unroll
-      for (int g = 0; g < RS / 2; ++g) {
-        const double2 t = b[g];
-        rec_i[2 * g] = t.x;
-        rec_i[2 * g + 1] = t.y;
-      }
-    }
+    load_whole_record<E>(P, rec, U, i, rec_i);
     for (uint32_t c = 1; c < r.width; ++c) {
       const bool mine = (upper >> c) & 1u;
       if (!__any(mine))
@@ -970,13 +986,7 @@ namespace ryujin_hip
       const uint32_t j = ld_stream(cols + (pos));
       double c_ij[DIM], rec_j[RS];
       load_entry<DIM>(cij, colbase, r.lane, c_ij);
-      const double2 *b = reinterpret_cast<const double2 *>(rec + (size_t)j * RS);
-#pragma unroll
-      for (int g = 0; g < RS / 2; ++g) {
-        const double2 t = b[g];
-        rec_j[2 * g] = t.x;
-        rec_j[2 * g + 1] = t.y;
-      }
+      load_whole_record<E>(P, rec, U, j, rec_j);
       if (mine)
         dij[pos] = E::template dij_from_records<GENERAL>(P, rec_i, rec_j, c_ij);
     }
@@ -1004,7 +1014,7 @@ namespace ryujin_hip
     const double *__restrict__ cij = M.cij;
 
     double rec_i[RS];
-    load_record<RS>(rec, i, rec_i);
+    load_record<E>(rec, i, rec_i);
 
     if constexpr (E::kRecordHoldsState) {
       /* Euler: the record is all the indicator needs of a node as well (E::node_record) -- one gather of RS doubles
@@ -1016,7 +1026,7 @@ namespace ryujin_hip
       uint32_t j_nn = r.width > 1 ? ld_stream(cols + (((uint64_t)r.base + 1) * 64 + r.lane)) : i;
       double c_n[DIM], rec_n[RS];
       load_entry<DIM>(cij, r.base, r.lane, c_n);
-      load_record<RS>(rec, j_n, rec_n);
+      load_record<E>(rec, j_n, rec_n);
       double d_pending = 0.; /* the d_ij of the column before, stored behind this column's loads (see arrived()) */
       bool d_pending_on = false;
       for (uint32_t c = 0; c < r.width; ++c) {
@@ -1035,7 +1045,7 @@ namespace ryujin_hip
         if (c + 1 < r.width) {
           j_n = j_nn;
           load_entry<DIM>(cij, colbase + 1, r.lane, c_n);
-          load_record<RS>(rec, j_n, rec_n);
+          load_record<E>(rec, j_n, rec_n);
           j_nn = (c + 2 < r.width) ? ld_stream(cols + ((colbase + 2) * 64 + r.lane)) : i;
         }
         if (d_pending_on)
@@ -1060,6 +1070,8 @@ namespace ryujin_hip
       load_state<K>(U, i, U_i);
       typename E::Indicator indicator;
       indicator.reset(P, U_i, prec2[i]);
+      if constexpr (E::kRecordNeedsState)
+        E::complete_record(U_i, E::state_values(P, U_i), rec_i);
 
       /* (the column loop exists twice -- stencil classes, above: UNIFORM takes c_ij of column c from the class entry
        * of the slice, which has no padding; one wave-uniform branch behind the lambda chooses) */
@@ -1107,15 +1119,41 @@ namespace ryujin_hip
             j_nn = (c + 2 < r.width) ? column(colbase + 2) : i;
           }
           const bool active = UNIFORM ? row_active : (row_active && c < r.len);
-          if (active && (c > 0 || !E::kIndicatorDiagonalIsZero))
-            indicator.accumulate(P, U_j, prec_j, c_ij);
           /* upper triangle only (:394-408) */
           const bool mine = active && c > 0 && j > i;
-          if (__any(mine)) {
-            double rec_j[RS];
-            load_record<RS>(rec, j, rec_j);
-            if (mine)
-              dij[colbase * 64 + r.lane] = E::template dij_from_records<GENERAL>(P, rec_i, rec_j, c_ij);
+          if constexpr (E::kRecordNeedsState) {
+            /* 1 / rho_j and p_j once per column, for the indicator's flux and for the Riemann solve: the stored
+             * record holds neither (E::complete_record) */
+            if (c > 0 || !E::kIndicatorDiagonalIsZero) {
+              const typename E::StateValues s_j = E::state_values(P, U_j);
+              if (active)
+                indicator.accumulate(U_j, prec_j, s_j, c_ij);
+              if (__any(mine)) {
+                double rec_j[RS];
+                load_record<E>(rec, j, rec_j);
+                E::complete_record(U_j, s_j, rec_j);
+                /* |c_ij| and its inverse: mesh constants, in a uniform slice one value for the wave -- from the
+                 * table next to the class entries (the same operations on the host: the same bits), one branch of
+                 * scalar code in front of ONE copy of the solver */
+                double norm, inverse_norm;
+                if (UNIFORM && M.class_norms != nullptr)
+                  class_norm(M, cls + c, norm, inverse_norm);
+                else
+                  E::cij_norm(c_ij, norm, inverse_norm);
+                if (mine)
+                  dij[colbase * 64 + r.lane] =
+                      E::template dij_from_records<GENERAL>(P, rec_i, rec_j, c_ij, norm, inverse_norm);
+              }
+            }
+          } else {
+            if (active && (c > 0 || !E::kIndicatorDiagonalIsZero))
+              indicator.accumulate(P, U_j, prec_j, c_ij);
+            if (__any(mine)) {
+              double rec_j[RS];
+              load_record<E>(rec, j, rec_j);
+              if (mine)
+                dij[colbase * 64 + r.lane] = E::template dij_from_records<GENERAL>(P, rec_i, rec_j, c_ij);
+            }
           }
         }
       };

@@ -692,14 +692,7 @@ namespace ryujin_hip
       const double2 prec_i = E::precompute(P, U_i);
       reinterpret_cast<double2 *>(FP.prec)[i] = prec_i;
       E::node_record(P, U_i, prec_i, r);
-      double2 *out = reinterpret_cast<double2 *>(FP.rec + (size_t)i * RS);
-#pragma unroll
-      for (int g = 0; g < RS / 2; ++g) {
-        double2 t;
-        t.x = r[2 * g];
-        t.y = r[2 * g + 1];
-        out[g] = t;
-      }
+      store_record<E>(FP.rec, i, r); /* (Euler in 1-D and 2-D: 32 of its 64 bytes, E::kRecordNeedsState) */
     }
   }
 

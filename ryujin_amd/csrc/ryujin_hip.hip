@@ -338,7 +338,7 @@ struct ryujin_hip_comm {
 
 struct ryujin_hip_ctx {
   ryujin_hip_params params{};
-  int dim = 0, K = 0, KP = 0, NB = 3, NPREC = 2, RS = 0; /* system_shape() */
+  int dim = 0, K = 0, KP = 0, NB = 3, NPREC = 2, RS = 0, RS_stored = 0; /* system_shape() */
   int device = 0;
   ryujin_hip_comm *comm = nullptr;
   hipStream_t stream = nullptr;      /* compute */
@@ -398,6 +398,7 @@ struct ryujin_hip_ctx {
   /* the stencil classes (host_layout.hpp); empty where no slice is uniform, in 3-D and with debug_stencil_classes < 0 */
   DeviceBuffer<uint32_t> d_slice_class;
   DeviceBuffer<uint64_t> d_class_table;
+  DeviceBuffer<double> d_class_norms; /* SellLayout::class_norms; empty with debug_stencil_classes = 1 */
   DeviceBuffer<uint16_t> d_row_len;
   DeviceBuffer<double> d_cij, d_mij, d_mi, d_mi_inv;
   bool dg = false; /* discontinuous ansatz */
@@ -766,6 +767,7 @@ void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params
   NB = shape.NB;
   NPREC = shape.NPREC;
   RS = shape.RS;
+  RS_stored = shape.RS_stored;
   dg = o.discontinuous_ansatz != 0;
 
   /* ---- streams and events -------------------------------------------------- */
@@ -847,6 +849,8 @@ void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params
     if (L.n_uniform_slices != 0) {
       d_slice_class.upload(L.slice_class);
       d_class_table.upload(L.class_table);
+      if (p.debug_stencil_classes != 1) /* 1: the classes without the table of norms (A/B) */
+        d_class_norms.upload(L.class_norms);
     }
   }
   d_lower_mask.upload(lower_mask(L));
@@ -893,6 +897,7 @@ void ryujin_hip_ctx::create(const ryujin_hip_offline &o, const ryujin_hip_params
   mesh.chain_loads = d_chain_loads.n != 0 ? d_chain_loads.ptr : nullptr;
   mesh.slice_class = d_slice_class.n != 0 ? d_slice_class.ptr : nullptr;
   mesh.class_table = d_class_table.n != 0 ? reinterpret_cast<const StencilClassEntry *>(d_class_table.ptr) : nullptr;
+  mesh.class_norms = d_class_norms.n != 0 ? d_class_norms.ptr : nullptr;
   mesh.tail_queue_columns = knobs.tail_queue_columns;
   mesh.band_stride = knobs.band_stride;
   mesh.xcd_chunk = knobs.xcd_chunk;
@@ -1576,7 +1581,7 @@ void ryujin_hip_ctx::step2_dij_alpha(const StepPlan &plan, const State &old)
       if constexpr (is_euler_v<E>)
         with_bool(!plan.fast_riemann, [&](auto newton) {
           hipLaunchKernelGGL((k_dij_records<E, decltype(newton)::value>), grid, block, 0, launch_stream, eparams, mm,
-                             d_lower_mask.ptr, old.rrec.ptr, d_dij.ptr);
+                             d_lower_mask.ptr, old.rrec.ptr, old.U.ptr, d_dij.ptr);
         });
     });
   } else {
@@ -2558,9 +2563,13 @@ namespace
     const SystemShape s = system_shape(equation, E::DIMENSION);
     bool ok = s.K == E::K && s.KP == StatePad<E::K>::KP && s.NB == E::NB;
     if constexpr (is_scalar_v<E>)
-      ok = ok && s.NPREC == E::NPREC && s.RS == 0;
+      ok = ok && s.NPREC == E::NPREC && s.RS == 0 && s.RS_stored == 0;
     else
       ok = ok && s.RS == E::RS;
+    if constexpr (is_euler_v<E> || is_sw_v<E>) /* the generic kernels: load_record(), store_record() */
+      ok = ok && s.RS_stored == E::kRecordStored;
+    else if constexpr (is_aeos_v<E>)
+      ok = ok && s.RS_stored == E::RS;
     if constexpr (is_aeos_v<E>)
       ok = ok && s.NPREC == E::NPREC;
     return ok;
@@ -2838,8 +2847,8 @@ int ryujin_hip_state_alloc(ryujin_hip_ctx *ctx, int *handle)
       h = (int)ctx->states.size() - 1;
       ctx->states[h]->U.alloc((size_t)ctx->L.n_relevant * ctx->KP);
       ctx->states[h]->prec.alloc((size_t)ctx->L.n_relevant * ctx->NPREC);
-      if (ctx->RS != 0) /* E::RS; scalar conservation keeps no node records */
-        ctx->states[h]->rrec.alloc((size_t)ctx->L.n_relevant * ctx->RS);
+      if (ctx->RS_stored != 0) /* E::kRecordStored; scalar conservation keeps no node records */
+        ctx->states[h]->rrec.alloc((size_t)ctx->L.n_relevant * ctx->RS_stored);
     }
     ctx->states[h]->used = true;
     ctx->states[h]->precomputed = false;

@@ -418,6 +418,9 @@ namespace ryujin_hip
 
     /* (the record holds the Riemann data only: step 2 reads the state and the precomputed values next to it) */
     static constexpr bool kRecordHoldsState = false;
+    /* ... and memory holds all of it (Euler<DIM>::kRecordNeedsState) */
+    static constexpr bool kRecordNeedsState = false;
+    static constexpr int kRecordFirst = 0, kRecordStored = RS;
     static RYUJIN_DEV void node_record(const Params &P, const double (&U)[K], const double2, double (&rec)[RS])
     {
       riemann_record(P, U, rec);
