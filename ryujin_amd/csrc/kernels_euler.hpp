@@ -1315,6 +1315,45 @@ namespace ryujin_hip
     double w[4];
   };
 
+  /* Three statements that the step 4 of every Description shares, each with the reference's operation order. They take
+   * and return scalars: k_low_order, k_low_order_aeos and k_low_order_sc compile to the instruction streams they had
+   * with the statements written out (k_low_order_aeos keeps its viscosity factor written out for that reason). */
+
+  /* Limiter::bounds: hd_i^(3 / (2 dim)), the radius that the caller scales by its relaxation factor */
+  template <int DIM>
+  RYUJIN_DEV double relaxation_radius(const double hd_i)
+  {
+    double r_i = sqrt(hd_i);
+    if constexpr (DIM == 2) {
+      const double t = sqrt(r_i);
+      r_i = t * t * t;
+    } else if constexpr (DIM == 1) {
+      r_i = r_i * r_i * r_i;
+    }
+    return r_i;
+  }
+
+  /* scaled_c_ij = c_ij * this: 1 / max(d_ij, 100 DBL_MIN) (dealii::Tensor / scalar multiplies by the inverse). A
+   * scalar in and out: with the arrays handed to a helper the compiler orders the operands of the multiplications that
+   * take scaled_c_ij differently, and no step-4 kernel keeps its instruction stream */
+  RYUJIN_DEV double inverse_regularized(const double d_ij)
+  {
+    const double denom = fmax(d_ij, 100. * DBL_MIN);
+    return 1. / denom;
+  }
+
+  /* d_ijH / d_ij of the stencil entry at `pos`; DG: the incidence matrix enters the high-order viscosity
+   * (hyperbolic_module.template.h:733-737) */
+  template <bool DG>
+  RYUJIN_DEV double high_order_factor(const double alpha_i, const double alpha_j, const double *incidence,
+                                      const uint64_t pos)
+  {
+    double factor = (alpha_i + alpha_j) * .5;
+    if constexpr (DG)
+      factor = fmax(factor, incidence[pos]);
+    return factor;
+  }
+
   /* STORE_P = false: the first part of P_ij is not written here but recomputed -- with the identical
    * operation sequence, hence bit-identical -- by k_pij_lij_recompute (saves the 8kS B/row store of
    * this sweep and the 8kS B/row load of step 5 for 8dS+8S B/row of c_ij, d_ij loads there).
@@ -1421,15 +1460,9 @@ namespace ryujin_hip
         if (!active)
           continue;
 
-        double factor = (alpha_i + alpha_j) * .5;
-        if constexpr (DG) /* hyperbolic_module.template.h:733-737 */
-          factor = fmax(factor, M.incidence[colbase * 64 + r.lane]);
-        const double d_ijH = d_ij * factor;
-
-        const double regularization = 100. * DBL_MIN;
-        const double denom = fmax(d_ij, regularization);
+        const double d_ijH = d_ij * high_order_factor<DG>(alpha_i, alpha_j, M.incidence, colbase * 64 + r.lane);
         double scaled_c_ij[DIM];
-        const double inverse_denom = 1. / denom; /* dealii::Tensor / scalar multiplies by the inverse */
+        const double inverse_denom = inverse_regularized(d_ij);
 #pragma unroll
         for (int d = 0; d < DIM; ++d)
           scaled_c_ij[d] = c_ij[d] * inverse_denom;
@@ -1531,14 +1564,7 @@ namespace ryujin_hip
 
     /* Limiter::bounds (limiter.h:330-363) */
     const double hd_i = m_i * M.measure_of_omega_inverse;
-    double r_i = sqrt(hd_i);
-    if constexpr (DIM == 2) {
-      const double t = sqrt(r_i);
-      r_i = t * t * t;
-    } else if constexpr (DIM == 1) {
-      r_i = r_i * r_i * r_i;
-    }
-    r_i *= P.lim_relaxation_factor;
+    const double r_i = relaxation_radius<DIM>(hd_i) * P.lim_relaxation_factor;
     const double rho_relaxation =
         fabs(rho_relaxation_numerator) / (fabs(rho_relaxation_denominator) + DBL_EPSILON);
     const double relaxation = (2. * P.lim_relaxation_factor) * rho_relaxation;

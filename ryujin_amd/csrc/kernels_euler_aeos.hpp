@@ -344,15 +344,13 @@ namespace ryujin_hip
       if (!active)
         continue;
 
+      /* (written out: with high_order_factor<DG> the DG instantiations do not keep their instruction stream) */
       double factor = (alpha_i + alpha_j) * .5;
       if constexpr (DG)
         factor = fmax(factor, M.incidence[colbase * 64 + r.lane]);
       const double d_ijH = d_ij * factor;
-
-      const double regularization = 100. * DBL_MIN;
-      const double denom = fmax(d_ij, regularization);
       double scaled_c_ij[DIM];
-      const double inverse_denom = 1. / denom; /* dealii::Tensor / scalar multiplies by the inverse */
+      const double inverse_denom = inverse_regularized(d_ij);
 #pragma unroll
       for (int d = 0; d < DIM; ++d)
         scaled_c_ij[d] = c_ij[d] * inverse_denom;
@@ -448,14 +446,7 @@ namespace ryujin_hip
 
     /* Limiter::bounds (limiter.h:356-410) */
     const double hd_i = m_i * M.measure_of_omega_inverse;
-    double r_i = sqrt(hd_i);
-    if constexpr (DIM == 2) {
-      const double t = sqrt(r_i);
-      r_i = t * t * t;
-    } else if constexpr (DIM == 1) {
-      r_i = r_i * r_i * r_i;
-    }
-    r_i *= P.lim_relaxation_factor;
+    const double r_i = relaxation_radius<DIM>(hd_i) * P.lim_relaxation_factor;
     const double rho_relaxation =
         fabs(rho_relaxation_numerator) / (fabs(rho_relaxation_denominator) + DBL_EPSILON);
     const double relaxation = (2. * P.lim_relaxation_factor) * rho_relaxation;

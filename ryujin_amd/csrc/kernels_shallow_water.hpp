@@ -15,6 +15,261 @@
 
 namespace ryujin_hip
 {
+  /* |v|^2 with the mollified inverse water depth (shallow_water/limiter.h:286-289) */
+  template <int DIM>
+  RYUJIN_DEV double sw_velocity_squared(const ShallowWaterParams &P, const double (&U)[DIM + 1])
+  {
+    const double ihm = ShallowWater<DIM>::inverse_water_depth_mollified(P, U);
+    const double v = U[1] * ihm;
+    double v2 = v * v;
+#pragma unroll
+    for (int d = 1; d < DIM; ++d) {
+      const double vd = U[1 + d] * ihm;
+      v2 += vd * vd;
+    }
+    return v2;
+  }
+
+  /* Limiter::reset / accumulate / bounds of shallow_water/limiter.h. accumulate() comes in two pieces because the
+   * single walk knows U_ij_bar only once the affine shift is complete. */
+  template <int DIM>
+  struct SwLimiter {
+    using E = ShallowWater<DIM>;
+    static constexpr int K = E::K;
+
+    double h_min, h_max, kin_max, v2_max;
+    double h_relaxation_numerator, kin_relaxation_numerator, v2_relaxation_numerator, relaxation_denominator;
+    double kin_i, v2_i;
+
+    /* :247-268 */
+    RYUJIN_DEV void reset(const ShallowWaterParams &P, const double (&U_i)[K])
+    {
+      h_min = DBL_MAX;
+      h_max = kin_max = v2_max = 0.;
+      h_relaxation_numerator = kin_relaxation_numerator = v2_relaxation_numerator = relaxation_denominator = 0.;
+      kin_i = E::kinetic_energy(P, U_i);
+      v2_i = sw_velocity_squared<DIM>(P, U_i);
+    }
+
+    /* :271-330, the minima and maxima over one U_ij_bar */
+    RYUJIN_DEV void accumulate(const ShallowWaterParams &P, const double (&U_ij_bar)[K])
+    {
+      const double h_bar_ij = U_ij_bar[0];
+      h_min = fmin(h_min, h_bar_ij);
+      h_max = fmax(h_max, h_bar_ij);
+      kin_max = fmax(kin_max, E::kinetic_energy(P, U_ij_bar));
+      v2_max = fmax(v2_max, sw_velocity_squared<DIM>(P, U_ij_bar));
+    }
+
+    /* :271-330, the relaxation sums of the pair (i, j) */
+    RYUJIN_DEV void accumulate_relaxation(const ShallowWaterParams &P, const double (&U_i)[K], const double (&U_j)[K])
+    {
+      relaxation_denominator += 1.;
+      h_relaxation_numerator += 1. * (U_i[0] + U_j[0]);
+      kin_relaxation_numerator += 1. * (kin_i + E::kinetic_energy(P, U_j));
+      const double v2_j = sw_velocity_squared<DIM>(P, U_j);
+      v2_relaxation_numerator += 1. * (-v2_i + v2_j);
+    }
+
+    /* :333-377, relaxed and stored SoA: [NB][rows_padded] */
+    RYUJIN_DEV void bounds(const ShallowWaterParams &P, const DeviceMesh &M, const double m_i, const uint32_t i,
+                           double *out) const
+    {
+      const double hd_i = m_i * M.measure_of_omega_inverse;
+      const double r_i = relaxation_radius<DIM>(hd_i) * P.lim_relaxation_factor;
+      const double h_relaxed = 2. * fabs(h_relaxation_numerator) / (relaxation_denominator + DBL_EPSILON);
+      const double h_min_r = fmax((1. - r_i) * h_min, h_min - h_relaxed);
+      const double h_max_r = fmin((1. + r_i) * h_max, h_max + h_relaxed);
+      const double kin_relaxed = 2. * fabs(kin_relaxation_numerator) / (relaxation_denominator + DBL_EPSILON);
+      const double kin_max_r = fmin((1. + r_i) * kin_max, kin_max + kin_relaxed);
+      const double v2_relaxed = 2. * fabs(v2_relaxation_numerator) / (relaxation_denominator + DBL_EPSILON);
+      const double v2_max_r = fmin((1. + r_i) * v2_max, v2_max + v2_relaxed);
+      double r2 = hd_i;
+      if constexpr (DIM == 2)
+        r2 = sqrt(hd_i);
+      r2 *= P.dry_state_relaxation_factor;
+      const double h_small = P.reference_water_depth * r2;
+
+      const size_t stride = M.bounds_stride;
+      out[i] = h_min_r;
+      out[stride + i] = h_max_r;
+      out[2 * stride + i] = h_small;
+      out[3 * stride + i] = kin_max_r;
+      out[4 * stride + i] = v2_max_r;
+    }
+  };
+
+  /* The row's Manning sources S_i (of U_i) and S_iH (weighted over U_i and the stage vectors) and the initial
+   * U_i_new and F_iH (:660-699). FRICTION = false (Manning coefficient 0, the reference's default and BASELINE
+   * configs[4]): every source term of the sweep is (+-)0 times something finite -- S_i, S_iH, the m_ij weighted
+   * neighbour sources -- and only ever added to something; the kernel then holds no registers for them and issues
+   * none of their multiply-adds. Exact up to the sign of a zero. */
+  template <int DIM, bool HAS_STAGES, bool FRICTION>
+  RYUJIN_DEV void sw_row_prologue(const ShallowWaterParams &P, const StageArgs<DIM> &S, const double *prec,
+                                  const uint32_t i, const double tau, const double weight, const double m_i,
+                                  const double (&U_i)[DIM + 1], double (&S_i)[DIM + 1], double (&S_iH)[DIM + 1],
+                                  double (&U_i_new)[DIM + 1], double (&F_iH)[DIM + 1])
+  {
+    using E = ShallowWater<DIM>;
+    constexpr int K = E::K;
+#pragma unroll
+    for (int q = 0; q < K; ++q)
+      S_iH[q] = S_i[q] = 0.;
+    if constexpr (FRICTION) {
+      if constexpr (HAS_STAGES) {
+        for (int s = 0; s < S.stages; ++s) {
+          double U_iHs[K], Ss[K];
+          load_state<K>(S.U[s], i, U_iHs);
+          E::manning_friction(P, U_iHs, S.prec[s][(size_t)i * 2 + 1], tau, Ss);
+#pragma unroll
+          for (int q = 0; q < K; ++q)
+            S_iH[q] += S.w[s] * Ss[q];
+        }
+      }
+      E::manning_friction(P, U_i, prec[(size_t)i * 2 + 1], tau, S_i);
+    }
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+      U_i_new[q] = U_i[q];
+      F_iH[q] = 0.;
+      if constexpr (FRICTION) {
+        S_iH[q] += weight * S_i[q];
+        U_i_new[q] += tau * S_i[q];
+        F_iH[q] += m_i * S_iH[q];
+      }
+    }
+  }
+
+  /* affine shift, the term of one column (:700-720, shallow_water/hyperbolic_system.h:1176-1191) */
+  template <int DIM>
+  RYUJIN_DEV void sw_affine_shift_term(const double (&U_i)[DIM + 1], const double h_inverse_i,
+                                       const double (&U_star_ij)[DIM + 1], const double (&c_ij)[DIM],
+                                       const double d_ij, double (&affine_shift)[DIM + 1])
+  {
+    double m_c = U_i[1] * c_ij[0];
+#pragma unroll
+    for (int d = 1; d < DIM; ++d)
+      m_c += U_i[1 + d] * c_ij[d];
+    const double factor = 2. * (d_ij + h_inverse_i * m_c);
+#pragma unroll
+    for (int q = 0; q < DIM + 1; ++q)
+      affine_shift[q] += -factor * (U_star_ij[q] - U_i[q]);
+  }
+
+  /* One pair (i, j) of the walk, given the column's operands and the two star states. Its first half (:722-795):
+   * the low-order update of U_i_new, the viscous parts of F_iH and P_ij, and `bar`, the part
+   * 1/2 (U*_ij + U*_ji + (f*_ij - f*_ji) c_ij / d_ij) of U_ij_bar that is free of the affine shift.
+   * pos: the entry's place in the SELL-64 streams. */
+  template <int DIM, bool DG>
+  RYUJIN_DEV void sw_pair_fluxes(const ShallowWaterParams &P, const DeviceMesh &M, const double tau, const uint64_t pos,
+                                 const double (&U_i)[DIM + 1], const double alpha_i, const double m_i_inv,
+                                 const double alpha_j, const double (&c_ij)[DIM], const double d_ij,
+                                 const double (&U_star_ij)[DIM + 1], const double (&U_star_ji)[DIM + 1],
+                                 double (&U_i_new)[DIM + 1], double (&F_iH)[DIM + 1], double (&P_ij)[DIM + 1],
+                                 double (&bar)[DIM + 1])
+  {
+    using E = ShallowWater<DIM>;
+    constexpr int K = E::K;
+    const double d_ijH = d_ij * high_order_factor<DG>(alpha_i, alpha_j, M.incidence, pos);
+    double scaled_c_ij[DIM];
+    const double inverse_denom = inverse_regularized(d_ij);
+#pragma unroll
+    for (int d = 0; d < DIM; ++d)
+      scaled_c_ij[d] = c_ij[d] * inverse_denom;
+
+    double flux_ij[K];
+    E::flux_divergence(P, U_i, U_star_ij, U_star_ji, c_ij, flux_ij);
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+      U_i_new[q] += tau * m_i_inv * flux_ij[q];
+      P_ij[q] = -flux_ij[q];
+    }
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+      const double dU = U_star_ji[q] - U_star_ij[q];
+      U_i_new[q] += tau * m_i_inv * d_ij * dU;
+      F_iH[q] += d_ijH * dU;
+      P_ij[q] += (d_ijH - d_ij) * dU;
+    }
+
+    {
+      double f_star_ij[K][DIM], f_star_ji[K][DIM];
+      E::f(P, U_star_ij, f_star_ij);
+      E::f(P, U_star_ji, f_star_ji);
+#pragma unroll
+      for (int q = 0; q < K; ++q) {
+        double s = (f_star_ij[q][0] + (-f_star_ji[q][0])) * scaled_c_ij[0];
+#pragma unroll
+        for (int d = 1; d < DIM; ++d)
+          s += (f_star_ij[q][d] + (-f_star_ji[q][d])) * scaled_c_ij[d];
+        bar[q] = 0.5 * (U_star_ij[q] + U_star_ji[q] + s);
+      }
+    }
+  }
+
+  /* ... and its second half (:797-846), the source terms and the high-order flux of the pair. It is a function of
+   * its own because both kernels consume `bar` in between, while the star states are still in registers: taken
+   * behind the stage loop the consumption costs the single walk up to 34 registers and one of its three waves. */
+  template <int DIM, bool HAS_STAGES, bool FRICTION>
+  RYUJIN_DEV void sw_pair_sources(const ShallowWaterParams &P, const StageArgs<DIM> &S, const double tau,
+                                  const double weight, const uint32_t i, const uint32_t j,
+                                  const double (&U_i)[DIM + 1], const double Z_i, const double (&S_i)[DIM + 1],
+                                  const double (&S_iH)[DIM + 1], const double (&U_j)[DIM + 1], const double Z_j,
+                                  const double (&c_ij)[DIM], const double m_ij, const double h_star_j,
+                                  double (&F_iH)[DIM + 1], double (&P_ij)[DIM + 1])
+  {
+    using E = ShallowWater<DIM>;
+    constexpr int K = E::K;
+    if constexpr (FRICTION) {
+#pragma unroll
+      for (int q = 0; q < K; ++q) {
+        F_iH[q] -= m_ij * S_iH[q];
+        P_ij[q] -= m_ij * /*sic!*/ S_i[q];
+      }
+    }
+    {
+      double hof[K];
+      E::high_order_flux_divergence(P, U_i, Z_i, U_j, Z_j, c_ij, hof);
+#pragma unroll
+      for (int q = 0; q < K; ++q) {
+        F_iH[q] += weight * hof[q];
+        P_ij[q] += weight * hof[q];
+      }
+    }
+    if constexpr (FRICTION) {
+      double S_j[K];
+      E::manning_friction(P, U_j, h_star_j, tau, S_j);
+#pragma unroll
+      for (int q = 0; q < K; ++q) {
+        F_iH[q] += weight * m_ij * S_j[q];
+        P_ij[q] += weight * m_ij * S_j[q];
+      }
+    }
+    if constexpr (HAS_STAGES) {
+      for (int s = 0; s < S.stages; ++s) {
+        double U_iHs[K], U_jHs[K], hof_s[K];
+        load_state<K>(S.U[s], i, U_iHs);
+        load_state<K>(S.U[s], j, U_jHs);
+        E::high_order_flux_divergence(P, U_iHs, Z_i, U_jHs, Z_j, c_ij, hof_s);
+        const double w = S.w[s];
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+          F_iH[q] += w * hof_s[q];
+          P_ij[q] += w * hof_s[q];
+        }
+        if constexpr (FRICTION) {
+          double S_js[K];
+          E::manning_friction(P, U_jHs, S.prec[s][(size_t)j * 2 + 1], tau, S_js);
+#pragma unroll
+          for (int q = 0; q < K; ++q) {
+            F_iH[q] += w * m_ij * S_js[q];
+            P_ij[q] += w * m_ij * S_js[q];
+          }
+        }
+      }
+    }
+  }
+
   /* DG: discontinuous ansatz, the incidence matrix enters the high-order viscosity (:733-737) */
   template <int DIM, bool HAS_STAGES, bool DG = false>
   __global__ void __launch_bounds__(kBlock, RYUJIN_OCC_LOW_SW)
@@ -45,28 +300,8 @@ namespace ryujin_hip
     const double m_i_inv = M.mi_inv[i];
     const double Z_i = Z[i];
 
-#pragma unroll
-    for (int q = 0; q < K; ++q)
-      S_iH[q] = 0.;
-    if constexpr (HAS_STAGES) {
-      for (int s = 0; s < S.stages; ++s) {
-        double U_iHs[K], Ss[K];
-        load_state<K>(S.U[s], i, U_iHs);
-        E::manning_friction(P, U_iHs, S.prec[s][(size_t)i * 2 + 1], tau, Ss);
-#pragma unroll
-        for (int q = 0; q < K; ++q)
-          S_iH[q] += S.w[s] * Ss[q];
-      }
-    }
-    E::manning_friction(P, U_i, prec[(size_t)i * 2 + 1], tau, S_i);
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-      S_iH[q] += weight * S_i[q];
-      U_i_new[q] = U_i[q];
-      U_i_new[q] += tau * S_i[q];
-      F_iH[q] = 0.;
-      F_iH[q] += m_i * S_iH[q];
-    }
+    /* (this walk always evaluates the sources) */
+    sw_row_prologue<DIM, HAS_STAGES, true>(P, S, prec, i, tau, weight, m_i, U_i, S_i, S_iH, U_i_new, F_iH);
 
     /* affine shift pre-loop (:700-720, shallow_water/hyperbolic_system.h:1176-1191) */
     double affine_shift[K];
@@ -99,14 +334,7 @@ namespace ryujin_hip
           continue;
         double U_star_ij[K];
         E::star_state(P, U_i, Z_i, Z_j, U_star_ij);
-        double m_c = U_i[1] * c_ij[0];
-#pragma unroll
-        for (int d = 1; d < DIM; ++d)
-          m_c += U_i[1 + d] * c_ij[d];
-        const double factor = 2. * (d_ij + h_inverse * m_c);
-#pragma unroll
-        for (int q = 0; q < K; ++q)
-          affine_shift[q] += -factor * (U_star_ij[q] - U_i[q]);
+        sw_affine_shift_term<DIM>(U_i, h_inverse, U_star_ij, c_ij, d_ij, affine_shift);
       }
     }
 #pragma unroll
@@ -115,22 +343,8 @@ namespace ryujin_hip
       affine_shift[q] += tau * S_i[q];
     }
 
-    /* Limiter::reset (shallow_water/limiter.h:247-268) */
-    double h_min = DBL_MAX, h_max = 0., kin_max = 0., v2_max = 0.;
-    double h_relaxation_numerator = 0., kin_relaxation_numerator = 0., v2_relaxation_numerator = 0.,
-           relaxation_denominator = 0.;
-    const double kin_i = E::kinetic_energy(P, U_i);
-    double v2_i;
-    {
-      const double ihm_i = E::inverse_water_depth_mollified(P, U_i);
-      const double v = U_i[1] * ihm_i;
-      v2_i = v * v;
-#pragma unroll
-      for (int d = 1; d < DIM; ++d) {
-        const double vd = U_i[1 + d] * ihm_i;
-        v2_i += vd * vd;
-      }
-    }
+    SwLimiter<DIM> limiter;
+    limiter.reset(P, U_i);
 
     uint32_t j_n = ld_stream(cols + ((uint64_t)r.base * 64 + r.lane));
     uint32_t j_nn = r.width > 1 ? ld_stream(cols + (((uint64_t)r.base + 1) * 64 + r.lane)) : i;
@@ -169,126 +383,20 @@ namespace ryujin_hip
       if (!active)
         continue;
 
-      double factor = (alpha_i + alpha_j) * .5;
-      if constexpr (DG)
-        factor = fmax(factor, M.incidence[colbase * 64 + r.lane]);
-      const double d_ijH = d_ij * factor;
-      const double denom = fmax(d_ij, 100. * DBL_MIN);
-      double scaled_c_ij[DIM];
-      const double inverse_denom = 1. / denom; /* dealii::Tensor / scalar multiplies by the inverse */
-#pragma unroll
-      for (int d = 0; d < DIM; ++d)
-        scaled_c_ij[d] = c_ij[d] * inverse_denom;
-
       double U_star_ij[K], U_star_ji[K];
       E::star_state(P, U_i, Z_i, Z_j, U_star_ij);
       E::star_state(P, U_j, Z_j, Z_i, U_star_ji);
 
-      double flux_ij[K];
-      E::flux_divergence(P, U_i, U_star_ij, U_star_ji, c_ij, flux_ij);
-
-      double P_ij[K];
+      double P_ij[K], U_ij_bar[K];
+      sw_pair_fluxes<DIM, DG>(P, M, tau, colbase * 64 + r.lane, U_i, alpha_i, m_i_inv, alpha_j, c_ij, d_ij, U_star_ij,
+                              U_star_ji, U_i_new, F_iH, P_ij, U_ij_bar);
 #pragma unroll
-      for (int q = 0; q < K; ++q) {
-        U_i_new[q] += tau * m_i_inv * flux_ij[q];
-        P_ij[q] = -flux_ij[q];
-      }
-#pragma unroll
-      for (int q = 0; q < K; ++q) {
-        const double dU = U_star_ji[q] - U_star_ij[q];
-        U_i_new[q] += tau * m_i_inv * d_ij * dU;
-        F_iH[q] += d_ijH * dU;
-        P_ij[q] += (d_ijH - d_ij) * dU;
-      }
-
-      /* Limiter::accumulate (shallow_water/limiter.h:271-330) */
-      {
-        double f_star_ij[K][DIM], f_star_ji[K][DIM], U_ij_bar[K];
-        E::f(P, U_star_ij, f_star_ij);
-        E::f(P, U_star_ji, f_star_ji);
-#pragma unroll
-        for (int q = 0; q < K; ++q) {
-          double s = (f_star_ij[q][0] + (-f_star_ji[q][0])) * scaled_c_ij[0];
-#pragma unroll
-          for (int d = 1; d < DIM; ++d)
-            s += (f_star_ij[q][d] + (-f_star_ji[q][d])) * scaled_c_ij[d];
-          U_ij_bar[q] = 0.5 * (U_star_ij[q] + U_star_ji[q] + s) + affine_shift[q];
-        }
-        const double h_bar_ij = U_ij_bar[0];
-        h_min = fmin(h_min, h_bar_ij);
-        h_max = fmax(h_max, h_bar_ij);
-        kin_max = fmax(kin_max, E::kinetic_energy(P, U_ij_bar));
-        {
-          const double ihm = E::inverse_water_depth_mollified(P, U_ij_bar);
-          const double v = U_ij_bar[1] * ihm;
-          double v2 = v * v;
-#pragma unroll
-          for (int d = 1; d < DIM; ++d) {
-            const double vd = U_ij_bar[1 + d] * ihm;
-            v2 += vd * vd;
-          }
-          v2_max = fmax(v2_max, v2);
-        }
-        relaxation_denominator += 1.;
-        h_relaxation_numerator += 1. * (U_i[0] + U_j[0]);
-        kin_relaxation_numerator += 1. * (kin_i + E::kinetic_energy(P, U_j));
-        double v2_j;
-        {
-          const double ihm_j = E::inverse_water_depth_mollified(P, U_j);
-          const double v = U_j[1] * ihm_j;
-          v2_j = v * v;
-#pragma unroll
-          for (int d = 1; d < DIM; ++d) {
-            const double vd = U_j[1 + d] * ihm_j;
-            v2_j += vd * vd;
-          }
-        }
-        v2_relaxation_numerator += 1. * (-v2_i + v2_j);
-      }
-
-#pragma unroll
-      for (int q = 0; q < K; ++q) {
-        F_iH[q] -= m_ij * S_iH[q];
-        P_ij[q] -= m_ij * /*sic!*/ S_i[q];
-      }
-      {
-        double hof[K];
-        E::high_order_flux_divergence(P, U_i, Z_i, U_j, Z_j, c_ij, hof);
-#pragma unroll
-        for (int q = 0; q < K; ++q) {
-          F_iH[q] += weight * hof[q];
-          P_ij[q] += weight * hof[q];
-        }
-      }
-      {
-        double S_j[K];
-        E::manning_friction(P, U_j, h_star_j, tau, S_j);
-#pragma unroll
-        for (int q = 0; q < K; ++q) {
-          F_iH[q] += weight * m_ij * S_j[q];
-          P_ij[q] += weight * m_ij * S_j[q];
-        }
-      }
-      if constexpr (HAS_STAGES) {
-        for (int s = 0; s < S.stages; ++s) {
-          double U_iHs[K], U_jHs[K], hof_s[K], S_js[K];
-          load_state<K>(S.U[s], i, U_iHs);
-          load_state<K>(S.U[s], j, U_jHs);
-          E::high_order_flux_divergence(P, U_iHs, Z_i, U_jHs, Z_j, c_ij, hof_s);
-          E::manning_friction(P, U_jHs, S.prec[s][(size_t)j * 2 + 1], tau, S_js);
-          const double w = S.w[s];
-#pragma unroll
-          for (int q = 0; q < K; ++q) {
-            F_iH[q] += w * hof_s[q];
-            P_ij[q] += w * hof_s[q];
-          }
-#pragma unroll
-          for (int q = 0; q < K; ++q) {
-            F_iH[q] += w * m_ij * S_js[q];
-            P_ij[q] += w * m_ij * S_js[q];
-          }
-        }
-      }
+      for (int q = 0; q < K; ++q)
+        U_ij_bar[q] += affine_shift[q];
+      limiter.accumulate(P, U_ij_bar);
+      limiter.accumulate_relaxation(P, U_i, U_j);
+      sw_pair_sources<DIM, HAS_STAGES, true>(P, S, tau, weight, i, j, U_i, Z_i, S_i, S_iH, U_j, Z_j, c_ij, m_ij,
+                                             h_star_j, F_iH, P_ij);
       store_entry<K>(pij, colbase, r.lane, P_ij);
     }
 
@@ -298,37 +406,7 @@ namespace ryujin_hip
     store_state<K>(new_U, i, U_i_new);
     store_state<K>(r_out, i, F_iH);
 
-    /* Limiter::bounds (shallow_water/limiter.h:333-377) */
-    const double hd_i = m_i * M.measure_of_omega_inverse;
-    double r_i = sqrt(hd_i);
-    if constexpr (DIM == 2) {
-      const double t = sqrt(r_i);
-      r_i = t * t * t;
-    } else if constexpr (DIM == 1) {
-      r_i = r_i * r_i * r_i;
-    }
-    r_i *= P.lim_relaxation_factor;
-    const double h_relaxed = 2. * fabs(h_relaxation_numerator) / (relaxation_denominator + DBL_EPSILON);
-    const double h_min_r = fmax((1. - r_i) * h_min, h_min - h_relaxed);
-    const double h_max_r = fmin((1. + r_i) * h_max, h_max + h_relaxed);
-    const double kin_relaxed =
-        2. * fabs(kin_relaxation_numerator) / (relaxation_denominator + DBL_EPSILON);
-    const double kin_max_r = fmin((1. + r_i) * kin_max, kin_max + kin_relaxed);
-    const double v2_relaxed =
-        2. * fabs(v2_relaxation_numerator) / (relaxation_denominator + DBL_EPSILON);
-    const double v2_max_r = fmin((1. + r_i) * v2_max, v2_max + v2_relaxed);
-    double r2 = hd_i;
-    if constexpr (DIM == 2)
-      r2 = sqrt(hd_i);
-    r2 *= P.dry_state_relaxation_factor;
-    const double h_small = P.reference_water_depth * r2;
-
-    const size_t stride = M.bounds_stride;
-    bounds[i] = h_min_r;
-    bounds[stride + i] = h_max_r;
-    bounds[2 * stride + i] = h_small;
-    bounds[3 * stride + i] = kin_max_r;
-    bounds[4 * stride + i] = v2_max_r;
+    limiter.bounds(P, M, m_i, i, bounds);
   }
   /* The same sweep with ONE walk over the stencil (rows of at most MAXW columns). The reference walks the
    * stencil twice because the limiter bounds need U_ij_bar = 1/2 (U*_ij + U*_ji + (f*_ij - f*_ji) c_ij / d_ij)
@@ -367,36 +445,7 @@ namespace ryujin_hip
     const double m_i_inv = M.mi_inv[i];
     const double Z_i = Z[i];
 
-    /* FRICTION = false (Manning coefficient 0, the reference's default and BASELINE configs[4]): every source
-     * term of this sweep is (+-)0 times something finite -- S_i, S_iH, the m_ij weighted neighbour sources -- and
-     * only ever added to something; the kernel then holds no registers for them, issues none of their
-     * multiply-adds and does not read m_ij at all (8 B per stencil entry). Exact up to the sign of a zero. */
-#pragma unroll
-    for (int q = 0; q < K; ++q)
-      S_iH[q] = S_i[q] = 0.;
-    if constexpr (FRICTION) {
-      if constexpr (HAS_STAGES) {
-        for (int s = 0; s < S.stages; ++s) {
-          double U_iHs[K], Ss[K];
-          load_state<K>(S.U[s], i, U_iHs);
-          E::manning_friction(P, U_iHs, S.prec[s][(size_t)i * 2 + 1], tau, Ss);
-#pragma unroll
-          for (int q = 0; q < K; ++q)
-            S_iH[q] += S.w[s] * Ss[q];
-        }
-      }
-      E::manning_friction(P, U_i, prec[(size_t)i * 2 + 1], tau, S_i);
-    }
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-      U_i_new[q] = U_i[q];
-      F_iH[q] = 0.;
-      if constexpr (FRICTION) {
-        S_iH[q] += weight * S_i[q];
-        U_i_new[q] += tau * S_i[q];
-        F_iH[q] += m_i * S_iH[q];
-      }
-    }
+    sw_row_prologue<DIM, HAS_STAGES, FRICTION>(P, S, prec, i, tau, weight, m_i, U_i, S_i, S_iH, U_i_new, F_iH);
 
     /* affine shift (:700-720, shallow_water/hyperbolic_system.h:1176-1191): accumulated by the walk below */
     /* (the diagonal column stays in registers: MAXW - 1 columns of K doubles per lane = 48 KiB per block in
@@ -413,28 +462,15 @@ namespace ryujin_hip
       affine_shift[q] = 0.;
     const double h_inverse_i = E::inverse_water_depth_sharp(P, U_i);
 
-    /* Limiter::reset (shallow_water/limiter.h:247-268) */
-    double h_min = DBL_MAX, h_max = 0., kin_max = 0., v2_max = 0.;
-    double h_relaxation_numerator = 0., kin_relaxation_numerator = 0., v2_relaxation_numerator = 0.,
-           relaxation_denominator = 0.;
-    const double kin_i = E::kinetic_energy(P, U_i);
-    double v2_i;
-    {
-      const double ihm_i = E::inverse_water_depth_mollified(P, U_i);
-      const double v = U_i[1] * ihm_i;
-      v2_i = v * v;
-#pragma unroll
-      for (int d = 1; d < DIM; ++d) {
-        const double vd = U_i[1 + d] * ihm_i;
-        v2_i += vd * vd;
-      }
-    }
+    SwLimiter<DIM> limiter;
+    limiter.reset(P, U_i);
 
     uint32_t j_n = ld_stream(cols + ((uint64_t)r.base * 64 + r.lane));
     uint32_t j_nn = r.width > 1 ? ld_stream(cols + (((uint64_t)r.base + 1) * 64 + r.lane)) : i;
     double c_n[DIM], U_n[K];
     load_entry<DIM>(cij, r.base, r.lane, c_n);
     double d_n = dij[(uint64_t)r.base * 64 + r.lane];
+    /* FRICTION = false does not read m_ij at all (8 B per stencil entry) */
     double m_n = FRICTION ? ld_stream(mij + ((uint64_t)r.base * 64 + r.lane)) : 0.;
     load_state<K>(U, j_n, U_n);
     double alpha_n = alpha[j_n];
@@ -487,129 +523,24 @@ namespace ryujin_hip
       if (!active)
         continue;
 
-      const double factor = (alpha_i + alpha_j) * .5;
-      const double d_ijH = d_ij * factor;
-      const double denom = fmax(d_ij, 100. * DBL_MIN);
-      double scaled_c_ij[DIM];
-      const double inverse_denom = 1. / denom; /* dealii::Tensor / scalar multiplies by the inverse */
-#pragma unroll
-      for (int d = 0; d < DIM; ++d)
-        scaled_c_ij[d] = c_ij[d] * inverse_denom;
-
       double U_star_ij[K], U_star_ji[K];
       E::star_state(P, U_i, Z_i, Z_j, U_star_ij);
       E::star_state(P, U_j, Z_j, Z_i, U_star_ji);
+      sw_affine_shift_term<DIM>(U_i, h_inverse_i, U_star_ij, c_ij, d_ij, affine_shift);
 
-      {
-        double m_c = U_i[1] * c_ij[0];
-#pragma unroll
-        for (int d = 1; d < DIM; ++d)
-          m_c += U_i[1 + d] * c_ij[d];
-        const double shift_factor = 2. * (d_ij + h_inverse_i * m_c);
-#pragma unroll
-        for (int q = 0; q < K; ++q)
-          affine_shift[q] += -shift_factor * (U_star_ij[q] - U_i[q]);
-      }
-
-      double flux_ij[K];
-      E::flux_divergence(P, U_i, U_star_ij, U_star_ji, c_ij, flux_ij);
-
-      double P_ij[K];
+      double P_ij[K], parked[K]; /* + affine_shift: second pass */
+      sw_pair_fluxes<DIM, false>(P, M, tau, colbase * 64 + r.lane, U_i, alpha_i, m_i_inv, alpha_j, c_ij, d_ij, U_star_ij,
+                                 U_star_ji, U_i_new, F_iH, P_ij, parked);
 #pragma unroll
       for (int q = 0; q < K; ++q) {
-        U_i_new[q] += tau * m_i_inv * flux_ij[q];
-        P_ij[q] = -flux_ij[q];
+        if (c == 0)
+          bar_diag[q] = parked[q];
+        else
+          bar[c - 1][q][r.lane] = parked[q];
       }
-#pragma unroll
-      for (int q = 0; q < K; ++q) {
-        const double dU = U_star_ji[q] - U_star_ij[q];
-        U_i_new[q] += tau * m_i_inv * d_ij * dU;
-        F_iH[q] += d_ijH * dU;
-        P_ij[q] += (d_ijH - d_ij) * dU;
-      }
-
-      /* Limiter::accumulate (shallow_water/limiter.h:271-330) */
-      {
-        double f_star_ij[K][DIM], f_star_ji[K][DIM];
-        E::f(P, U_star_ij, f_star_ij);
-        E::f(P, U_star_ji, f_star_ji);
-#pragma unroll
-        for (int q = 0; q < K; ++q) {
-          double s = (f_star_ij[q][0] + (-f_star_ji[q][0])) * scaled_c_ij[0];
-#pragma unroll
-          for (int d = 1; d < DIM; ++d)
-            s += (f_star_ij[q][d] + (-f_star_ji[q][d])) * scaled_c_ij[d];
-          const double parked = 0.5 * (U_star_ij[q] + U_star_ji[q] + s); /* + affine_shift: second pass */
-          if (c == 0)
-            bar_diag[q] = parked;
-          else
-            bar[c - 1][q][r.lane] = parked;
-        }
-        relaxation_denominator += 1.;
-        h_relaxation_numerator += 1. * (U_i[0] + U_j[0]);
-        kin_relaxation_numerator += 1. * (kin_i + E::kinetic_energy(P, U_j));
-        double v2_j;
-        {
-          const double ihm_j = E::inverse_water_depth_mollified(P, U_j);
-          const double v = U_j[1] * ihm_j;
-          v2_j = v * v;
-#pragma unroll
-          for (int d = 1; d < DIM; ++d) {
-            const double vd = U_j[1 + d] * ihm_j;
-            v2_j += vd * vd;
-          }
-        }
-        v2_relaxation_numerator += 1. * (-v2_i + v2_j);
-      }
-
-      if constexpr (FRICTION) {
-#pragma unroll
-        for (int q = 0; q < K; ++q) {
-          F_iH[q] -= m_ij * S_iH[q];
-          P_ij[q] -= m_ij * /*sic!*/ S_i[q];
-        }
-      }
-      {
-        double hof[K];
-        E::high_order_flux_divergence(P, U_i, Z_i, U_j, Z_j, c_ij, hof);
-#pragma unroll
-        for (int q = 0; q < K; ++q) {
-          F_iH[q] += weight * hof[q];
-          P_ij[q] += weight * hof[q];
-        }
-      }
-      if constexpr (FRICTION) {
-        double S_j[K];
-        E::manning_friction(P, U_j, h_star_j, tau, S_j);
-#pragma unroll
-        for (int q = 0; q < K; ++q) {
-          F_iH[q] += weight * m_ij * S_j[q];
-          P_ij[q] += weight * m_ij * S_j[q];
-        }
-      }
-      if constexpr (HAS_STAGES) {
-        for (int s = 0; s < S.stages; ++s) {
-          double U_iHs[K], U_jHs[K], hof_s[K];
-          load_state<K>(S.U[s], i, U_iHs);
-          load_state<K>(S.U[s], j, U_jHs);
-          E::high_order_flux_divergence(P, U_iHs, Z_i, U_jHs, Z_j, c_ij, hof_s);
-          const double w = S.w[s];
-#pragma unroll
-          for (int q = 0; q < K; ++q) {
-            F_iH[q] += w * hof_s[q];
-            P_ij[q] += w * hof_s[q];
-          }
-          if constexpr (FRICTION) {
-            double S_js[K];
-            E::manning_friction(P, U_jHs, S.prec[s][(size_t)j * 2 + 1], tau, S_js);
-#pragma unroll
-            for (int q = 0; q < K; ++q) {
-              F_iH[q] += w * m_ij * S_js[q];
-              P_ij[q] += w * m_ij * S_js[q];
-            }
-          }
-        }
-      }
+      limiter.accumulate_relaxation(P, U_i, U_j);
+      sw_pair_sources<DIM, HAS_STAGES, FRICTION>(P, S, tau, weight, i, j, U_i, Z_i, S_i, S_iH, U_j, Z_j, c_ij, m_ij,
+                                                 h_star_j, F_iH, P_ij);
 #pragma unroll
       for (int q = 0; q < K; ++q)
         P_pending[q] = P_ij[q];
@@ -633,57 +564,13 @@ namespace ryujin_hip
 #pragma unroll
       for (int q = 0; q < K; ++q)
         U_ij_bar[q] = (c == 0 ? bar_diag[q] : bar[c > 0 ? c - 1 : 0][q][r.lane]) + affine_shift[q];
-      const double h_bar_ij = U_ij_bar[0];
-      h_min = fmin(h_min, h_bar_ij);
-      h_max = fmax(h_max, h_bar_ij);
-      kin_max = fmax(kin_max, E::kinetic_energy(P, U_ij_bar));
-      {
-        const double ihm = E::inverse_water_depth_mollified(P, U_ij_bar);
-        const double v = U_ij_bar[1] * ihm;
-        double v2 = v * v;
-#pragma unroll
-        for (int d = 1; d < DIM; ++d) {
-          const double vd = U_ij_bar[1 + d] * ihm;
-          v2 += vd * vd;
-        }
-        v2_max = fmax(v2_max, v2);
-      }
+      limiter.accumulate(P, U_ij_bar);
     }
 
     store_state<K>(new_U, i, U_i_new);
     store_state<K>(r_out, i, F_iH);
 
-    /* Limiter::bounds (shallow_water/limiter.h:333-377) */
-    const double hd_i = m_i * M.measure_of_omega_inverse;
-    double r_i = sqrt(hd_i);
-    if constexpr (DIM == 2) {
-      const double t = sqrt(r_i);
-      r_i = t * t * t;
-    } else if constexpr (DIM == 1) {
-      r_i = r_i * r_i * r_i;
-    }
-    r_i *= P.lim_relaxation_factor;
-    const double h_relaxed = 2. * fabs(h_relaxation_numerator) / (relaxation_denominator + DBL_EPSILON);
-    const double h_min_r = fmax((1. - r_i) * h_min, h_min - h_relaxed);
-    const double h_max_r = fmin((1. + r_i) * h_max, h_max + h_relaxed);
-    const double kin_relaxed =
-        2. * fabs(kin_relaxation_numerator) / (relaxation_denominator + DBL_EPSILON);
-    const double kin_max_r = fmin((1. + r_i) * kin_max, kin_max + kin_relaxed);
-    const double v2_relaxed =
-        2. * fabs(v2_relaxation_numerator) / (relaxation_denominator + DBL_EPSILON);
-    const double v2_max_r = fmin((1. + r_i) * v2_max, v2_max + v2_relaxed);
-    double r2 = hd_i;
-    if constexpr (DIM == 2)
-      r2 = sqrt(hd_i);
-    r2 *= P.dry_state_relaxation_factor;
-    const double h_small = P.reference_water_depth * r2;
-
-    const size_t stride = M.bounds_stride;
-    bounds[i] = h_min_r;
-    bounds[stride + i] = h_max_r;
-    bounds[2 * stride + i] = h_small;
-    bounds[3 * stride + i] = kin_max_r;
-    bounds[4 * stride + i] = v2_max_r;
+    limiter.bounds(P, M, m_i, i, bounds);
   }
   /* Discontinuous ansatz: extend the limiter bounds over the stencil (hyperbolic_module.template.h:938-948) with
    * Limiter::combine_bounds AS WRITTEN in shallow_water/limiter.h:386-397:

@@ -399,13 +399,9 @@ namespace ryujin_hip
       if (!(row_active && c < r.len))
         continue;
 
-      double factor = (alpha_i + alpha_j) * .5;
-      if constexpr (DG) /* hyperbolic_module.template.h:733-737 */
-        factor = fmax(factor, M.incidence[colbase * 64 + r.lane]);
-      const double d_ijH = d_ij * factor;
-      const double denom = fmax(d_ij, 100. * DBL_MIN);
+      const double d_ijH = d_ij * high_order_factor<DG>(alpha_i, alpha_j, M.incidence, pos);
       double scaled_c_ij[DIM];
-      const double inverse_denom = 1. / denom; /* dealii::Tensor / scalar multiplies by the inverse */
+      const double inverse_denom = inverse_regularized(d_ij);
 #pragma unroll
       for (int d = 0; d < DIM; ++d)
         scaled_c_ij[d] = c_ij[d] * inverse_denom;
@@ -467,14 +463,7 @@ namespace ryujin_hip
 
     /* Limiter::bounds */
     const double hd_i = m_i * M.measure_of_omega_inverse;
-    double r_i = sqrt(hd_i);
-    if constexpr (DIM == 2) {
-      const double t = sqrt(r_i);
-      r_i = t * t * t;
-    } else if constexpr (DIM == 1) {
-      r_i = r_i * r_i * r_i;
-    }
-    r_i *= P.lim_relaxation_factor;
+    const double r_i = relaxation_radius<DIM>(hd_i) * P.lim_relaxation_factor;
     const double u_relaxation =
         fabs(u_relaxation_numerator) / (fabs(u_relaxation_denominator) + DBL_EPSILON);
     const double u_min_r =

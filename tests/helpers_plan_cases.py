@@ -205,12 +205,13 @@ def _synthetic(spec):
 
 
 def _case(mesh, equation, data, n_points, plan, launches, *, warm, edit=None, cfl=0.9, limited_fraction=1.0, stages=0,
-          second_update=None):
+          second_update=None, options=()):
+    """options: what the plan mode of the CPU checker is told besides the mesh (tests/test_step_plan.py)"""
     names = {"euler": capi.EQ_EULER, "euler_aeos": capi.EQ_EULER_AEOS, "scalar": capi.EQ_SCALAR_CONSERVATION,
              "shallow_water": capi.EQ_SHALLOW_WATER}
     return dict(mesh=mesh, equation=equation, eq=names[equation], data=data, n_points=n_points, plan=plan, warm=warm,
                 edit=edit, cfl=cfl, limited_fraction=limited_fraction, stages=stages, second_update=second_update,
-                **launches)
+                options=tuple(options), **launches)
 
 
 CASES = {}
@@ -313,6 +314,52 @@ ERK33_CASES = {
         _plan("alpha_then_dij", 27, "pij_lij", 1, True, 1, "cached", True, step2_split=True, step4_has_stages=True),
         _one(562, 1, False), warm=2, edit=_aeos_edit, stages=1),
 }
+
+# ... and on shallow water with Manning friction over an uneven, partly dry bed: the plain update of stage 0 runs
+# k_low_order_sw_single_walk<1 | 2, false, 3 | 9, true>, step<1> and step<2> run <1 | 2, true, 3 | 9, true>. A Q1
+# rectangle of 13 x 7 gridpoints (one full slice and 27 rows of a second one, boundary rows in both) and an interval
+# of 100 gridpoints
+def _uneven_bed(positions):
+    """a bed that rises through the free surface of _over_uneven_bed towards the upper end of x: a dry shore"""
+    x = positions[:, 0]
+    Z = 0.15 * x + 0.1 * np.sin(2.0 * x)
+    return Z + 0.1 * np.cos(1.5 * positions[:, 1]) if positions.shape[1] > 1 else Z
+
+
+def _over_uneven_bed(spec):
+    def mesh():
+        off = offline.SyntheticOffline(spec)
+        off.set_initial_precomputed(_uneven_bed(off.positions))
+        return off
+    return mesh
+
+
+def _dam_break_over_uneven_bed(off):
+    """water at rest with its surface at 1 left of x = 0 and at 0.6 right of it, dry where the bed is higher"""
+    x = off.positions
+    U0 = np.zeros((off.n_relevant, off.dim + 1))
+    U0[:, 0] = np.maximum(np.where(x[:, 0] < 0.0, 1.0, 0.6) - _uneven_bed(x), 0.0)
+    return dict(U0=U0, dirichlet=None)
+
+
+def _manning_edit(p):
+    p.manning_friction_coefficient = 0.03
+
+
+ERK33_SW_FRICTION_CASES = {
+    "erk33_sw_friction_2d_13x7": _case(
+        _over_uneven_bed(offline.rectangle_2d(12, (-5.0, -2.5), (5.0, 2.5), ny=6, bc=capi.BC_SLIP)), "shallow_water",
+        _dam_break_over_uneven_bed, 13 * 7,
+        _stored_everywhere("records", step4_single_walk=True, step4_has_stages=True, step4_friction=True),
+        _one(2, 1, True), warm=4, edit=_manning_edit, stages=1, options=("friction=1",)),
+    "erk33_sw_friction_1d_100": _case(
+        _over_uneven_bed(offline.MeshSpec(1, (99,), (-5.0,), (5.0,), (capi.BC_SLIP, capi.BC_SLIP))), "shallow_water",
+        _dam_break_over_uneven_bed, 100,
+        _plan("records", 3, "pij_lij", 1, True, 1, "cached", True, step4_single_walk=True, step4_has_stages=True,
+              step4_friction=True),
+        _one(2, 1, True), warm=4, edit=_manning_edit, stages=1, options=("friction=1",)),
+}
+ERK33_CASES.update(ERK33_SW_FRICTION_CASES)
 
 # shallow water on two ranks (x slabs of a 381 x 381 point box): the export part of a rank is a few slices and shares
 # them in step 6, the interior part has more than 1024 and does not

@@ -29,6 +29,8 @@ block share a slice in step 6):
   erk33 (896 slices)                       step<1>, step<2>: k_pij_lij, step 6 shared
   erk33_aeos_1d_681, erk33_aeos_3d_box_562 step<1>, step<2>: k_low_order_aeos<1 | 3, true, ...>, k_pij_lij<EulerAeos<1 | 3> >,
                                            step 6 shared in 1-D, not shared in 3-D
+  erk33_sw_friction_1d_100 / 2d_13x7       stage 0: k_low_order_sw_single_walk<1 | 2, false, 3 | 9, true>; step<1>, step<2>:
+                                           <1 | 2, true, 3 | 9, true> (Manning friction, uneven and partly dry bed)
   two ranks, shallow water                 step 6 shared in the export part, not shared in the interior part"""
 import numpy as np
 import pytest
@@ -98,14 +100,23 @@ def test_erk33_stages_with_stage_vectors_share_slices_in_step_6(oracle):
     _erk33_stages(oracle, cases.ERK33_CASE, "erk33")
 
 
-@pytest.mark.parametrize("name", sorted(set(cases.ERK33_CASES) - {"erk33"}))
+@pytest.mark.parametrize("name", sorted(set(cases.ERK33_CASES) - {"erk33"} - set(cases.ERK33_SW_FRICTION_CASES)))
 def test_erk33_stages_with_stage_vectors_on_euler_aeos(oracle, name):
     """the same on EulerAEOS in 1-D (681 slices: step 6 shares slices) and 3-D (562 slices): k_low_order_aeos with stage
     vectors -- the stage vectors' precomputed pressures enter the fluxes --, step 5 is k_pij_lij"""
     _erk33_stages(oracle, cases.ERK33_CASES[name], name)
 
 
-def _erk33_stages(oracle, case, name):
+@pytest.mark.parametrize("name", sorted(cases.ERK33_SW_FRICTION_CASES))
+def test_erk33_stages_on_shallow_water_with_friction(oracle, name):
+    """the same on shallow water with a Manning coefficient over an uneven, partly dry bed, in 1-D and 2-D: the plain
+    update of stage 0 is k_low_order_sw_single_walk<dim, false, 3 | 9, true>, step<1> and step<2> are
+    <dim, true, 3 | 9, true> -- the row's and the neighbours' friction sources of the stage vectors enter F_iH and P_ij"""
+    case = cases.ERK33_SW_FRICTION_CASES[name]
+    _erk33_stages(oracle, case, name, stage0_plan=dict(case["plan"], step4_has_stages=False))
+
+
+def _erk33_stages(oracle, case, name, stage0_plan=None):
     off, U0, dirichlet, after_warm = cases.build(case)
     assert off.n_owned == case["n_points"]
     U_start = cases.warm_up(case, oracle, off, U0, dirichlet, after_warm)
@@ -127,6 +138,8 @@ def _erk33_stages(oracle, case, name):
         _print_measured(f"{name} stage {stage}", g)
         assert g["status"] == 0
         tau = c["tau"]
+        if stage == 0 and stage0_plan:
+            _assert_plan(mg, stage0_plan, case["step5_launches"], case["step6_launches"], f"{name} stage 0")
         if stage > 0:
             _assert_coverage(off, c["lij_next"], f"{name} stage {stage}")
             _assert_plan(mg, case["plan"], case["step5_launches"], case["step6_launches"], f"{name} stage {stage}")

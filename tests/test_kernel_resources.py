@@ -25,6 +25,8 @@ CONTRACT = {
     "k_high_order_last_cached<Euler<2>, 9, 3>": (84, 0, 6),   # step 7, C2
     "k_dij_diag_unrolled<9>": (32, 0, 8),                     # step 3, C2
     "k_pij_lij<ShallowWater<2>, false, false>": (128, 0, 4),  # step 5, C5
+    "k_low_order_sw_single_walk<2, false, 9, false>": (256, 0, 2),  # step 4, C5 (48 KiB of LDS per block)
+    "k_low_order_sw_single_walk<1, false, 3, false>": (168, 0, 3),  # step 4, shallow water 1-D
 }
 
 
@@ -32,7 +34,7 @@ CONTRACT = {
 def table():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "kernel_resources.py"), "k_lij_stage0<Euler",
                           "k_dij_alpha_records<Euler", "k_low_order<", "k_high_order_next_cached<Euler<2>",
-                          "k_high_order_last_cached<Euler<2>", "k_dij_diag_unrolled", "k_pij_lij<ShallowWater<2>"],
+                          "k_high_order_last_cached<Euler<2>", "k_dij_diag_unrolled", "k_pij_lij<ShallowWater<2>", "k_low_order_sw"],
                          capture_output=True, text=True, timeout=1200)
     rows = {}
     for line in out.stdout.splitlines():

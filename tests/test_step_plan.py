@@ -124,9 +124,11 @@ def test_kernel_path_of_the_benchmark_configurations(checker, key):
 import helpers_plan_cases as plan_cases  # noqa: E402
 
 
-def _checked_plan(checker, equation, off_dim, widths, n_owned, limited_fraction, stages, launch_sizes):
+def _checked_plan(checker, equation, off_dim, widths, n_owned, limited_fraction, stages, launch_sizes, options=()):
+    """launch_sizes may end in options ("key=value") as well"""
     n_slices = (n_owned + 63) // 64  # host_layout.hpp: n_slices = ceil(n_owned / 64)
-    r = _run(checker, "plan", equation, off_dim, int(widths.max()), n_slices, limited_fraction, stages, *launch_sizes)
+    r = _run(checker, "plan", equation, off_dim, int(widths.max()), n_slices, limited_fraction, stages, *launch_sizes,
+             *options)
     return n_slices, r
 
 
@@ -153,7 +155,7 @@ def test_case_table_of_the_gpu_variants_is_what_plan_step_decides(checker, name)
             continue
         sizes = [q["n_slices"] for q in update["step5_launches"]]
         n_slices, r = _checked_plan(checker, case["equation"], off.dim, widths, off.n_owned, update["limited_fraction"],
-                                    case["stages"], sizes)
+                                    case["stages"], sizes, case["options"])
         _assert_table_entry(r, n_slices, update["plan"], update["step5_launches"], update["step6_launches"])
 
 
